@@ -8,12 +8,17 @@ One "step" = one pass of the whole hot path over one batch that is already resid
 `value` = level-0 points of all ranks per second (weak scaling: every rank owns its own batch of
 8 x 50k-point spheres, BASELINE.json configs[2]; configs[3] is the same per rank on 8 GPUs).
 
-Besides the contract line this prints, in the same JSON object:
+A plain run sets up, warms up, times the --steps steps and prints the contract line.  With --full it also measures,
+in the same JSON object:
   roofline      the fused KPConv gather kernel (K3) of the largest layer (enc1: N=400k, H=59, 32->32):
                 algorithmic bytes B_fwd / average launch duration measured with
-                HIP events on the launch stream inside the timed region, against the 8 TB/s HBM peak.
+                HIP events on the launch stream inside the timed region, against the 8 TB/s HBM peak;
+                kernels_ms, the per-launch means of the KPConv gather kernels by layer.
   cpu_baseline  the CPU path (reference geometry core from oracle/_ref when present, else the port;
-                plain-torch KPConv restatement) timed on this box's host cores on ONE sphere.
+                plain-torch KPConv restatement) timed on this box's host cores on ONE sphere (--no-cpu-baseline: left out).
+
+--dump-outputs DIR writes what the last timed step computed as float32 DIR/<name>.npy (see dump_outputs); the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 Launch: `python bench.py` (1 GPU), or for N ranks either
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -36,6 +41,20 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 60 * 1000 * 1000      # --dump-outputs: array bytes in all, under 64 MB with the .npy headers
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> tensor, written as float32 <path>/<name>.npy.  Each array gets an equal share of DUMP_BYTES; one
+    larger than its share is replaced by a fixed sample of its flattened elements (seeded, ascending indices), so that the
+    same arguments always select the same elements."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def b_fwd(n, h, ci, co, es=4):
@@ -224,7 +243,12 @@ def main():
                     help="1: opt-in nearest-only upsampling searches (the [N, 1] matrices KP-FCNN actually reads; the reference's "
                          "batch carries the full rows, which stays the default and the contract line)")
     ap.add_argument("--workload", default="dales", choices=["dales", "vaihingen", "dales_deform", "dales_deform_f32", "vaihingen_wl"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the K3 roofline and per-kernel HIP-event times "
+                         "(events inside the timed steps) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as float32 DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--distinct-batches", type=int, default=4)
     ap.add_argument("--dp-buckets", type=int, default=int(os.environ.get("WEASAL_DP_BUCKETS", "1")),
                     help="N > 1 only: >1 cuts the gradient buffer into that many ranges whose all-reduce is launched "
@@ -241,6 +265,8 @@ def main():
                          "current step trains (weasal_amd.prefetch, the GPU counterpart of the reference's DataLoader "
                          "workers); 0: pyramid and training strictly one after the other on one stream")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
 
@@ -277,7 +303,7 @@ def main():
     opt = make_optimizer(net, cfg)
     sync = dp.GradSync(buckets=args.dp_buckets) if world > 1 else None
     if sync is not None:
-        sync.timed = True          # HIP events around the exchange (reported as config.allreduce_ms)
+        sync.timed = args.full     # HIP events around the exchange (reported as config.allreduce_ms)
 
     # inputs resident in HBM before the timed region (seed = 1000*rank + step)
     nd = max(1, min(args.distinct_batches, args.steps + args.warmup))
@@ -316,6 +342,8 @@ def main():
     served = [0]
 
     def step(i):
+        """-> (loss, out): out is what the step hands its caller besides the loss (logits, or the weak-label model's
+        (logits, class_logits, cam))"""
         if prefetcher is not None:
             tw0 = time.perf_counter()
             batch = next(prefetcher)              # blocks while the side stream is still building this batch
@@ -331,13 +359,13 @@ def main():
             loss = out[0].sum() if isinstance(out, tuple) else out.sum()      # (something to read back at the end)
         elif weak:
             batch.region, batch.region_lb, batch.cloud_lb, batch.center_pts = weak_labels[i % nd]
-            loss, _ = train_step_weak(net, opt, batch, cfg, grad_sync=sync)
+            loss, out = train_step_weak(net, opt, batch, cfg, grad_sync=sync)
         else:
-            loss, _ = train_step(net, opt, batch, cfg, grad_sync=sync, epoch=0 if args.contrast else None)
+            loss, out = train_step(net, opt, batch, cfg, grad_sync=sync, epoch=0 if args.contrast else None)
         tw0 = time.perf_counter()
         limiter.tick(batch)          # bounds the host's run-ahead (4 steps); checks the K4G capacity flags off the hot path
         waits["limiter"] += time.perf_counter() - tw0
-        return loss
+        return loss, out
 
     # Untimed pre-warm before the W warm-up steps (allocator caches, lazy module loads), then the training
     # loop's usual garbage-collector hygiene: without gc.freeze() CPython's full collection walks the module
@@ -362,19 +390,21 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    timer.enabled = True
+    timer.enabled = args.full
     if os.environ.get("WEASAL_STALL_DIAG"):
         pyramid.ACTIVATE_STALLS = []
     waits["prefetch"] = waits["limiter"] = 0.0
     fused.timer_reset()
-    # HIP events around the K3 launches inside the block calls (launch stream); WEASAL_TIMED_MIN_ROWS: only layers with at
-    # least that many query rows (A/B of the events' own cost)
-    fused.set_timed(True, int(os.environ.get("WEASAL_TIMED_MIN_ROWS", "0")))
+    # --full: HIP events around the K3 launches inside the block calls (launch stream); WEASAL_TIMED_MIN_ROWS: only layers
+    # with at least that many query rows (A/B of the events' own cost)
+    fused.set_timed(args.full, int(os.environ.get("WEASAL_TIMED_MIN_ROWS", "0")))
     from weasal_amd import _lib as _wlib
     launches0 = int(_wlib.lib().ws_launch_count())
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss = step(args.warmup + i)
+        loss, out = step(args.warmup + i)
+        if i + 1 < args.steps:
+            out = None                 # only the last step's outputs are kept (--dump-outputs)
     t_enqueued = time.perf_counter() - t0      # host time to issue the K steps (GPU still running)
     torch.cuda.synchronize()
     if world > 1:
@@ -390,6 +420,15 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+
+    if rank == 0 and args.dump_outputs:
+        outs = {"loss": loss} if args.mode == "train" else {}
+        for name, t in zip(("logits", "class_logits", "cam"), out if isinstance(out, tuple) else (out,)):
+            outs[name] = torch.stack(t) if isinstance(t, list) else t     # the weak-label model's four attention paths
+        if args.mode == "train":
+            # the parameters after the step's update, flattened in net.parameters() order
+            outs["parameters"] = torch.cat([p.detach().reshape(-1).float() for p in net.parameters()])
+        dump_outputs(args.dump_outputs, outs)
 
     if rank == 0 and pyramid.ACTIVATE_STALLS:
         st = [a.elapsed_time(b) for a, b in pyramid.ACTIVATE_STALLS]
@@ -445,7 +484,7 @@ def main():
             else:
                 summ[k_] = (float(np.mean(v_)), len(v_))
         fwd = {k: v for k, v in summ.items() if k[0] == "kpconv_gather_fwd" and k[3] >= 8}
-        if fwd:
+        if args.full and fwd:
             key = max(fwd, key=lambda k: b_fwd(k[1], k[2], k[3], k[3], es))     # the launch that moves the most bytes
             ms_k, count = fwd[key]
             _, nq, h, ci = key
@@ -515,7 +554,7 @@ def main():
                 a[0] += v[0] * v[1]
                 a[1] += v[1]
             res["kernels_ms"] = {k: round(a[0] / a[1], 4) for k, a in sorted(agg.items())}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 res["cpu_baseline"] = cpu_baseline(cfg_cls, wl, min(os.cpu_count() or 1, 16))
             except Exception as e:   # the baseline is a report, never a reason to lose the GPU line

@@ -1,9 +1,9 @@
 """CPU: the oracle (own restatement) against the golden vectors generated from the reference,
-and against oracle/_ref when that prebuilt library is present."""
+and against oracle/_ref as well when that library is built."""
 import numpy as np
 import pytest
 
-from conftest import assert_neighbors_equal, golden, sphere
+from conftest import assert_neighbors_equal, golden
 from oracle import geom
 
 pytestmark = pytest.mark.skipif(not geom.have_port(), reason="oracle/libws_oracle.so not built")
@@ -49,18 +49,30 @@ def test_empty_result_raises():
         geom.subsample_batch(p, [0], sampleDl=0.5)
 
 
-@pytest.mark.skipif(not geom.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 def test_port_vs_reference_build():
-    rng = np.random.default_rng(3)
-    p = np.concatenate([sphere(rng, 4000, 4.0), sphere(rng, 3000, 4.0, (0.5, 0.2, 0.1))])
-    l = np.array([4000, 3000], np.int32)
+    """the port against the reference's compiled core: its outputs on this input are stored in golden g14
+    (make_golden_port_vs_ref.py: neighbour counts, digests of the row sets and of the distance sequences, which the
+    reference orders by distance -- together what assert_neighbors_equal checks); where oracle/_ref is built, against the
+    live library as well"""
+    from golden.make_golden_port_vs_ref import digest, inputs, neighbor_digests
+    g = golden("g14_port_vs_ref.npz")
+    p, l = inputs()
+    assert digest(p, "<f4") == str(g["points_sha256"]), "the input differs from the one the golden was made from"
     for r in (0.6, 1.2):
-        a, b = geom.batch_query(p, p, l, l, r, "port"), geom.batch_query(p, p, l, l, r, "ref")
-        assert_neighbors_equal(p, p, a, b, False)
+        a = geom.batch_query(p, p, l, l, r, "port")
+        counts, sets, dists = neighbor_digests(p, a)
+        bad = np.nonzero(counts != g["counts_r%.1f" % r])[0]
+        assert len(bad) == 0, ("neighbour counts differ", r, bad[:10])
+        assert sets == str(g["sets_sha256_r%.1f" % r]), ("neighbour sets differ", r)
+        assert dists == str(g["d2_sha256_r%.1f" % r]), ("distance order differs beyond ties", r)
+        if geom.have_ref():
+            assert_neighbors_equal(p, p, a, geom.batch_query(p, p, l, l, r, "ref"), False)
     for dl in (0.48, 0.96, 1.92):
         a = geom.subsample_batch(p, l, sampleDl=dl, kind="port")
-        b = geom.subsample_batch(p, l, sampleDl=dl, kind="ref")
-        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+        assert np.array_equal(a[1], g["sub_lens_dl%.2f" % dl]) and digest(a[0], "<f4") == str(g["sub_points_sha256_dl%.2f" % dl])
+        if geom.have_ref():
+            b = geom.subsample_batch(p, l, sampleDl=dl, kind="ref")
+            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
 def test_pyramid_vs_golden():

@@ -6,11 +6,11 @@ R=$GRAFT_REPO_ROOT
 cd $R
 O=$R/gpurun_out/${1:-capture}
 mkdir -p $O
-python3 bench.py > $O/bench_dales.json 2> $O/bench_dales.err
+python3 bench.py --full > $O/bench_dales.json 2> $O/bench_dales.err
 echo bench dales done
-python3 bench.py --workload vaihingen --no-cpu-baseline > $O/bench_vaihingen.json 2> $O/bench_vaihingen.err
+python3 bench.py --full --workload vaihingen --no-cpu-baseline > $O/bench_vaihingen.json 2> $O/bench_vaihingen.err
 echo bench vaihingen done
-python3 bench.py --workload dales_deform --steps 6 --warmup 2 --no-cpu-baseline --distinct-batches 2 > $O/bench_dales_deform_bf16.json 2> $O/bench_dales_deform_bf16.err
+python3 bench.py --full --workload dales_deform --steps 6 --warmup 2 --no-cpu-baseline --distinct-batches 2 > $O/bench_dales_deform_bf16.json 2> $O/bench_dales_deform_bf16.err
 echo bench deform done
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/ks_bench.json 2> /dev/null
 cp /tmp/ks/*/*kernel_stats.csv $O/kernel_stats.csv

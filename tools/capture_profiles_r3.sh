@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 cd $R
 O=$R/gpurun_out/${1:-r03}
 mkdir -p $O
-b() { python3 bench.py "$@" 2> $O/last.err; }
+b() { python3 bench.py --full "$@" 2> $O/last.err; }
 b > $O/bench_dales_1gpu.json; echo bench dales done
 b --contrast 0 --no-cpu-baseline > $O/bench_dales_no_contrast_1gpu.json
 b --workload vaihingen --no-cpu-baseline > $O/bench_vaihingen_1gpu.json

@@ -371,7 +371,7 @@ typedef struct ws_pyramid_desc {
             off_blob[WS_PYRAMID_MAX_LEVELS], blob_bytes[WS_PYRAMID_MAX_LEVELS], grid_cells[WS_PYRAMID_MAX_LEVELS];
     int64_t off_lens, off_slots;
     int32_t max_count[3 * WS_PYRAMID_MAX_LEVELS], width[3 * WS_PYRAMID_MAX_LEVELS], final_width[3 * WS_PYRAMID_MAX_LEVELS];
-    int32_t reserved2[3 * WS_PYRAMID_MAX_LEVELS];
+    int32_t cap[3 * WS_PYRAMID_MAX_LEVELS];   /* sort slab each search was launched with (ws_radius_neighbors_async_cap then) */
     int64_t off_toffsets[3 * WS_PYRAMID_MAX_LEVELS], off_tpairs[3 * WS_PYRAMID_MAX_LEVELS];
 } ws_pyramid_desc;
 int ws_pyramid_build(ws_neighbors_ws* nws, ws_subsample_ws* sws, ws_pyramid_desc* desc, void* stream);

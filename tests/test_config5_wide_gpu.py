@@ -34,6 +34,18 @@ LIMITS = [422, 519, 472, 193, 34]
 REPORT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "config5_parity.json")
 
 
+@pytest.fixture(autouse=True)
+def _restore_wide_caps():
+    """a search that overflows its slab switches the whole process to 1024-entry slabs (ops.widen_async_slabs): restore the
+    switch after every test here, so that the tests after it still run the default 576 / 704 slabs"""
+    import ctypes as C
+    from weasal_amd import _lib
+    flag = C.c_int.in_dll(_lib.lib(), "ws_nb_wide_caps")
+    saved = flag.value
+    yield
+    flag.value = saved
+
+
 def rel(a, ref):
     a = a.detach().double().cpu()
     ref = ref.detach().double().cpu()
@@ -70,12 +82,17 @@ def _dense_clouds(seed, n=(9000, 7000), R=5.0):
     return pts, np.array(n, np.int32)
 
 
-@pytest.mark.parametrize("limit", [None, 422, 519])
-def test_wide_row_search_vs_oracle(gpu, limit):
+@pytest.mark.parametrize("limit,wide_caps", [pytest.param(None, 1, id="None"), pytest.param(422, 1, id="422"),
+                                             pytest.param(519, 1, id="519"), pytest.param(422, 0, id="422-slab1024"),
+                                             pytest.param(519, 0, id="519-slab1024")])
+def test_wide_row_search_vs_oracle(gpu, limit, wide_caps):
     """radius search whose rows hold 300-600 neighbours (17 points / m^3, r = 1.9): the full-width two-call protocol and the
-    one-pass limited search against the CPU oracle (neighbors.cpp:211-332), bit-exact"""
+    one-pass limited search against the CPU oracle (neighbors.cpp:211-332), bit-exact; the asynchronous form with the
+    width-sized slabs (576 / 704, the default) and with the 1024-entry slab a widened process uses"""
+    import ctypes as C
     from oracle import geom
-    from weasal_amd import ops
+    from weasal_amd import _lib, ops
+    C.c_int.in_dll(_lib.lib(), "ws_nb_wide_caps").value = wide_caps
     pts, lens = _dense_clouds(1)
     r = 1.9
     want = geom.batch_query(pts, pts, lens, lens, r, kind="ref" if geom.have_ref() else "port")

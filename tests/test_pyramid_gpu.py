@@ -11,6 +11,18 @@ from conftest import assert_neighbors_equal, golden
 pytestmark = pytest.mark.gpu
 
 
+@pytest.fixture(autouse=True)
+def _restore_wide_caps():
+    """a search that overflows its slab switches the whole process to 1024-entry slabs (ops.widen_async_slabs): restore the
+    switch after every test here, so that the tests after it still run the default 576 / 704 slabs"""
+    import ctypes as C
+    from weasal_amd import _lib
+    flag = C.c_int.in_dll(_lib.lib(), "ws_nb_wide_caps")
+    saved = flag.value
+    yield
+    flag.value = saved
+
+
 def _cfg():
     from test_oracle_cpu_kpconv import _small_config
     return _small_config()

@@ -150,7 +150,7 @@ class KPFCNN(nn.Module):
         if hasattr(batch, "activate"):
             batch.activate()     # stream hand-over, scheduling hints and pre-built tables of the batch
         else:
-            ops.clear_table_cache()          # transposed tables belong to one batch
+            ops.clear_batch_hints()          # tables, grids and sorted rows belong to one batch
         x = batch.features.clone().detach()
         skips = []
         slots = []
@@ -425,7 +425,7 @@ class KPFCNN_mprm(nn.Module):
         if hasattr(batch, "activate"):
             batch.activate()
         else:
-            ops.clear_table_cache()
+            ops.clear_batch_hints()
         x = batch.features.clone().detach()
         ele_down = batch.points[2][:, -1].unsqueeze(-1).clone().detach()     # heights at the attention level (:672)
         for block_i, block_op in enumerate(self.encoder_blocks):

@@ -160,11 +160,14 @@ extern "C" int ws_pyramid_build(ws_neighbors_ws* nws, ws_subsample_ws* sws, ws_p
     float last_r = -1.0f;
     for (int l = 0; l < L; ++l) {
         const int64_t n = d->n[l];
-        for (int k = 0; k < 3; ++k) { d->max_count[3 * l + k] = -1; d->width[3 * l + k] = 0; }
+        for (int k = 0; k < 3; ++k) { d->max_count[3 * l + k] = -1; d->width[3 * l + k] = 0; d->cap[3 * l + k] = 0; }
         if (d->conv_on[l]) {
             if (last_s == pts[l] && last_r == d->r_conv[l]) { if ((rc = ws_radius_neighbors_reuse_grid(nws, 1))) return rc; }
             if (d->want_grids)
                 if ((rc = ws_radius_neighbors_set_key_last(nws, (uint64_t*)(A.base + d->off_key_last[l])))) return rc;
+            // the slab of each search is recorded when it is issued (read BEFORE the launch: a widening in between can only
+            // make the check below stricter); ws_nb_wide_caps is process-global and another builder may widen it meanwhile
+            d->cap[3 * l] = ws_radius_neighbors_async_cap(d->limit[l]);
             if ((rc = ws_radius_neighbors_search_async(nws, pts[l], n, pts[l], n, d->lens[l], d->lens[l], nb, d->r_conv[l], d->limit[l],
                                                        nullptr, (int64_t*)(A.base + d->off_neighbors[l]), slots + 3 * l, st)))
                 return rc;
@@ -181,12 +184,14 @@ extern "C" int ws_pyramid_build(ws_neighbors_ws* nws, ws_subsample_ws* sws, ws_p
         if (d->pool_on[l]) {
             const int64_t m = d->n[l + 1];
             if (last_s == pts[l] && last_r == d->r_pool[l]) { if ((rc = ws_radius_neighbors_reuse_grid(nws, 1))) return rc; }
+            d->cap[3 * l + 1] = ws_radius_neighbors_async_cap(d->limit[l]);
             if ((rc = ws_radius_neighbors_search_async(nws, pts[l + 1], m, pts[l], n, d->lens[l + 1], d->lens[l], nb, d->r_pool[l],
                                                        d->limit[l], nullptr, (int64_t*)(A.base + d->off_pools[l]), slots + 3 * l + 1, st)))
                 return rc;
             last_s = pts[l]; last_r = d->r_pool[l];
             d->width[3 * l + 1] = d->limit[l];
             const float r_up = d->r_up[l];
+            d->cap[3 * l + 2] = ws_radius_neighbors_async_cap(d->nearest_up ? 1 : d->limit[l + 1]);
             if (d->nearest_up) {
                 // opt-in: only the nearest support of every point (what closest_pool reads of an upsampling matrix)
                 if ((rc = ws_radius_neighbors_nearest_async(nws, pts[l], n, pts[l + 1], m, d->lens[l], d->lens[l + 1], nb, r_up, nullptr,
@@ -215,8 +220,8 @@ extern "C" int ws_pyramid_build(ws_neighbors_ws* nws, ws_subsample_ws* sws, ws_p
         for (int k = 0; k < 3; ++k) {
             const int w = d->width[3 * l + k], mc = d->max_count[3 * l + k];
             if (w <= 0) continue;
-            const int cap = ws_radius_neighbors_async_cap(w);
-            if (mc <= 0 || mc > cap) continue;                       // empty result / slab overflow: the caller's business
+            // the slab the search was LAUNCHED with, not the current one
+            if (mc <= 0 || mc > d->cap[3 * l + k]) continue;         // empty result / slab overflow: the caller's business
             d->final_width[3 * l + k] = w;
             if (mc < w) {
                 const int64_t rows = k == 1 ? d->n[l + 1] : d->n[l];

@@ -7,6 +7,7 @@ torch's current stream.  CPU tensors are rejected -- there is no CPU path in the
 """
 import collections
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -102,18 +103,36 @@ def clear_table_cache():
     _col0_tables.clear()
 
 
-_col0_tables = {}     # (inds.data_ptr(), shape, ns) -> table of the first column (closest_pool backward)
+# ------------------------------------------------------------------------------------------------
+# index hints: what a registry knows about ONE index tensor (its table, its search grid, that its rows are sorted).  The
+# dictionaries are keyed by (data_ptr, shape) for an O(1) lookup, but an entry only answers for the tensor object it was
+# registered with, at the `_version` it had then: a matrix built later at a recycled address, or the same matrix changed in
+# place, gets nothing (a stale hint makes the kernels do the wrong thing without any error).
+# ------------------------------------------------------------------------------------------------
+def _hint_entry(t, payload):
+    return (weakref.ref(t), t._version, payload)
+
+
+def _hint(registry, key, t):
+    """payload of `registry[key]` if it was registered for `t` itself at its current version, else None"""
+    hit = registry.get(key)
+    if hit is None or hit[0]() is not t or hit[1] != t._version:
+        return None
+    return hit[2]
+
+
+_col0_tables = {}     # (inds.data_ptr(), shape, ns) -> hint entry: table of the first column (closest_pool backward)
 
 
 def col0_table(inds, ns):
     """transposed table of the FIRST column of `inds` (closest_pool / nearest upsampling backward), cached per index
     tensor like the full tables"""
     key = (inds.data_ptr(), tuple(inds.shape), ns)
-    hit = _col0_tables.get(key)
-    if hit is not None:
-        return hit[1]
+    table = _hint(_col0_tables, key, inds)
+    if table is not None:
+        return table
     table = TransposedTable(inds[:, :1].contiguous(), ns)
-    _col0_tables[key] = (inds, table)
+    _col0_tables[key] = _hint_entry(inds, table)
     return table
 
 
@@ -123,7 +142,7 @@ def install_tables(full, col0):
     for inds, ns, table in full:
         _tables[(inds.data_ptr(), tuple(inds.shape), ns, inds._version)] = (inds, table)
     for inds, ns, table in col0:
-        _col0_tables[(inds.data_ptr(), tuple(inds.shape), ns)] = (inds, table)
+        _col0_tables[(inds.data_ptr(), tuple(inds.shape), ns)] = _hint_entry(inds, table)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -172,14 +191,18 @@ def set_pool_orders(triples):
     _pool_orders.clear()
     for inds, oq, osup in triples:
         if isinstance(inds, torch.Tensor) and inds.dim() == 2 and inds.shape[0] > 0:
-            _pool_orders[(inds.data_ptr(), tuple(inds.shape))] = (oq, osup)
+            _pool_orders[(inds.data_ptr(), tuple(inds.shape))] = _hint_entry(inds, (oq, osup))
+
+
+def _pool_orders_for(inds):
+    return _hint(_pool_orders, (inds.data_ptr(), tuple(inds.shape)), inds) or (None, None)
 
 
 def set_search_grids(pairs):
     """install the (index matrix, SearchGrid) pairs of the batch about to be trained on (PyramidBatch.activate)"""
     _grids.clear()
     for inds, grid in pairs:
-        _grids[(inds.data_ptr(), tuple(inds.shape))] = (inds, grid)
+        _grids[(inds.data_ptr(), tuple(inds.shape))] = _hint_entry(inds, grid)
 
 
 _sorted_rows = {}
@@ -193,12 +216,21 @@ def set_sorted_rows(pairs):
     _sorted_rows.clear()
     for m, radius in pairs:
         if isinstance(m, torch.Tensor) and m.dim() == 2 and m.shape[0] > 0:
-            _sorted_rows[(m.data_ptr(), tuple(m.shape))] = float(radius)
+            _sorted_rows[(m.data_ptr(), tuple(m.shape))] = _hint_entry(m, float(radius))
+
+
+def clear_batch_hints():
+    """forget every hint a batch installed (sorted rows, search grids, pooling orders, transposed tables): for a forward on a
+    batch that brings none (no PyramidBatch.activate), so that nothing of the previous batch applies to it"""
+    _sorted_rows.clear()
+    _grids.clear()
+    _pool_orders.clear()
+    clear_table_cache()
 
 
 def sorted_rows_radius(inds):
     """search radius of a registered distance-sorted matrix, None for anything else"""
-    return _sorted_rows.get((inds.data_ptr(), tuple(inds.shape))) if SORTED_ROW_CUTOFF else None
+    return _hint(_sorted_rows, (inds.data_ptr(), tuple(inds.shape)), inds) if SORTED_ROW_CUTOFF else None
 
 
 def rows_cutoff_pays(inds, conv_radius):
@@ -213,8 +245,7 @@ GRID_NARROW_MAX = 128      # rows up to this length: the slab form of the grid b
 
 
 def _grid_for(inds):
-    hit = _grids.get((inds.data_ptr(), tuple(inds.shape))) if GRID_BACKWARD else None
-    return hit[1] if hit is not None else None
+    return _hint(_grids, (inds.data_ptr(), tuple(inds.shape)), inds) if GRID_BACKWARD else None
 
 
 def _order_for(points):
@@ -812,7 +843,7 @@ class _MaxPool(torch.autograd.Function):
         nq, h = inds.shape
         out = torch.empty((nq, c), dtype=x.dtype, device=x.device)
         arg = torch.empty((nq, c), dtype=torch.int32, device=x.device)
-        oq, osup = _pool_orders.get((inds.data_ptr(), tuple(inds.shape)), (None, None))      # scheduling hints (PyramidBatch.activate)
+        oq, osup = _pool_orders_for(inds)      # scheduling hints (PyramidBatch.activate)
         if oq is not None and oq.numel() != nq:
             oq = None
         if osup is not None and osup.numel() != ns:
@@ -1031,6 +1062,8 @@ class DeferredSearches:
             raise RuntimeError("DeferredSearches capacity exceeded")
         ws = _ws.neighbors(q.device)
         width = max(1, int(limit))
+        # sort slab of this launch, read before it (ws_nb_wide_caps may change before finish(): another search widens it)
+        cap = int(lib.ws_radius_neighbors_async_cap(width))
         out = torch.empty((q.shape[0], width), dtype=torch.int64, device=q.device)
         slot = len(self.calls)
         grid = None
@@ -1040,7 +1073,7 @@ class DeferredSearches:
             if want_grid:
                 grid = SearchGrid()
                 grid.max_count = 0            # true maximum row length of the search: set by the caller after finish()
-                grid.cap = int(lib.ws_radius_neighbors_async_cap(width))      # sort slab of the asynchronous pass: key_last is valid up to it
+                grid.cap = cap                # sort slab of the asynchronous pass: key_last is valid up to it
                 grid.key_last = torch.empty((q.shape[0],), dtype=torch.int64, device=q.device)
                 grid.radius = float(np.float32(radius))
                 grid.overflow = torch.zeros((1,), dtype=torch.int32, device=q.device)
@@ -1059,7 +1092,7 @@ class DeferredSearches:
                 grid.blob = torch.empty((nbytes.value,), dtype=torch.uint8, device=q.device)
                 grid.nb, grid.cells, grid.ns = nb.value, cells.value, ns_.value
                 check(lib.ws_radius_neighbors_grid_export(ws, ptr(grid.blob), current_stream()))
-        self.calls.append((out, (q, s, ql, sl, radius, width)))
+        self.calls.append((out, (q, s, ql, sl, radius, width, cap)))
         if want_grid:
             return out, order, grid
         return (out, order) if want_order else out
@@ -1069,10 +1102,10 @@ class DeferredSearches:
         self.last_counts = [int(c) for c in counts]      # true maximum row length of every call, in order
         final = []
         for (out, args), mc in zip(self.calls, counts):
-            q, s, ql, sl, radius, width = args
+            q, s, ql, sl, radius, width, cap = args
             if mc == 0:
                 raise _lib.WeasalHipError("libweasal_hip status 4: Error")
-            if mc > int(_lib.lib().ws_radius_neighbors_async_cap(int(width))):      # beyond the sort slab the asynchronous pass used
+            if mc > cap:                  # beyond the sort slab the asynchronous pass used
                 widen_async_slabs(mc)
                 out = radius_neighbors(q, s, ql, sl, radius, limit=width, dtype=torch.int64)
             elif mc < width:

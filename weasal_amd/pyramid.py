@@ -181,7 +181,7 @@ class PyramidDesc(_C.Structure):
                                                           "off_key_last", "off_blob", "blob_bytes", "grid_cells")]
                 + [("off_lens", _C.c_int64), ("off_slots", _C.c_int64),
                    ("max_count", _C.c_int32 * (3 * _ML)), ("width", _C.c_int32 * (3 * _ML)),
-                   ("final_width", _C.c_int32 * (3 * _ML)), ("reserved2", _C.c_int32 * (3 * _ML)),
+                   ("final_width", _C.c_int32 * (3 * _ML)), ("cap", _C.c_int32 * (3 * _ML)),
                    ("off_toffsets", _C.c_int64 * (3 * _ML)), ("off_tpairs", _C.c_int64 * (3 * _ML))])
 
 
@@ -310,7 +310,6 @@ def segmentation_inputs_native(config, stacked_points, stacked_features, labels,
     lens_host = [np.array(d.lens[l][:B], dtype=np.int32) for l in range(L)]
     slots = view(d.off_slots, 4 * L * 4, torch.int32, (4 * L,))
     empty_i = lambda: torch.zeros((0, 1), dtype=torch.int64, device=dev)
-    cap_of = lambda width: int(lib.ws_radius_neighbors_async_cap(int(width)))
 
     def finish(l, kind, off, rows, q, s, ql, sl, radius):
         """the matrix of search (l, kind) as the reference's crop leaves it: trimmed to the true width when that is smaller
@@ -341,7 +340,7 @@ def segmentation_inputs_native(config, stacked_points, stacked_features, labels,
                 grid.key_last = view(d.off_key_last[l], n[l] * 8, torch.int64, (n[l],))
                 grid.radius = float(np.float32(lv["r_conv"]))
                 grid.overflow = slots[3 * L + l:3 * L + l + 1]
-                grid.max_count, grid.cap = mc, cap_of(int(d.width[3 * l]))
+                grid.max_count, grid.cap = mc, int(d.cap[3 * l])      # the slab of the launch, not the process's current one
                 search_grids.append((mat, grid))
         else:
             neighbors.append(empty_i())

@@ -162,6 +162,11 @@ def test_deformable_kpconv_bf16_vs_oracle(gpu, modulated, influence):
     mk = lambda c: types.SimpleNamespace(modules=lambda: [c], l1=torch.nn.L1Loss(), K=15, repulse_extent=1.2,
                                          deform_fitting_power=1.0)
     reg = p2p_fitting_regularizer(mk(conv))
+    got = {}
+    if influence == "linear":          # the fast path: also compared with the rounding replay below
+        conv.offset_features.register_hook(lambda g_: got.__setitem__("d_off", g_.detach()))
+        conv.min_d2.register_hook(lambda g_: got.__setitem__("g_min_d2", g_.detach()))
+        conv.deformed_KP.register_hook(lambda g_: got.__setitem__("g_dkp", g_.detach()))
     ((out.float() * dy.float()).sum() + reg).backward()
     xc = x.float().cpu().requires_grad_(True)
     with kpconv_ref.cpu_reference_mode():
@@ -181,6 +186,15 @@ def test_deformable_kpconv_bf16_vs_oracle(gpu, modulated, influence):
     tol = 0.12 if influence == "linear" else 3e-2
     assert errs["dx_l2"] < tol and errs["dx_max"] < 2.5 * tol, errs
     assert errs["dW"] < 3e-2 and errs["dW_off"] < tol and errs["db_off"] < tol, errs
+    if influence == "linear":
+        # against the rounding replay (oracle/kpconv_bf16_ref.py), with this run's regulariser gradients: the bounds of
+        # tests/test_bf16_deform_chain_gpu.py, per row on d offset_features
+        from test_bf16_deform_chain_gpu import COMPOSED, assert_chain, compare_module, replay_module
+        rep = replay_module(conv, x, P, P, inds, dy, got["g_min_d2"], got["g_dkp"])
+        er = {}
+        bad, near, _, _ = compare_module(conv, rep, out, xg.grad, got["d_off"], P, P, inds, er)
+        print("bf16 deformable vs replay:", er)
+        assert_chain(er, bad, near, P.shape[0], "replay", COMPOSED)
 
 
 def test_pools_bf16_bit_exact(gpu):

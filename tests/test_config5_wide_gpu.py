@@ -13,7 +13,8 @@ oracle/kpconv_ref.py = the reference's op sequence in plain torch, oracle/pyrami
   * deformable + modulated KPConv forward / backward at H = 422 / 519 / 472, self-query (table-free backward) and
     strided (transposed table) layers, Ci = 32 / 64 / 128:
         f32 rows   out 1e-4, dx / dW 1e-4, gradients through the learned offsets 5e-4   
-        bf16 rows  against the fp32 oracle on bf16-rounded operands, bounds of tests/test_bf16_gpu.py
+        bf16 rows  against the fp32 oracle on bf16-rounded operands, bounds of tests/test_bf16_gpu.py, and against the
+                   rounding replay oracle/kpconv_bf16_ref.py, bounds of tests/test_bf16_deform_chain_gpu.py
   * the full-size workload (8 x 50 000 points): adjointness / linearity of the deformed gather on every level.
 Reference units: models/blocks.py:244-325, 366-367; datasets/common.py:500-502; models/architectures.py:24-57.
 """
@@ -224,6 +225,8 @@ def test_deformable_kpconv_real_width_vs_oracle(gpu, kind, lvl, ci, rows):
                                          deform_fitting_power=1.0)
     got = {}
     conv.offset_features.register_hook(lambda g_: got.__setitem__("d_off", g_.detach().float().cpu()))
+    conv.min_d2.register_hook(lambda g_: got.__setitem__("g_min_d2", g_.detach()))
+    conv.deformed_KP.register_hook(lambda g_: got.__setitem__("g_dkp", g_.detach()))
     reg = p2p_fitting_regularizer(mk(conv))
     ((out.float() * dy.float()).sum() + reg).backward()
     torch.cuda.synchronize()
@@ -288,6 +291,15 @@ def test_deformable_kpconv_real_width_vs_oracle(gpu, kind, lvl, ci, rows):
         assert errs["dx_l2"] < 0.12 and errs["dx_max"] < 0.30, errs
         assert errs["dW"] < 3e-2 and errs["dW_off_l2"] < 0.12 and errs["db_off_l2"] < 0.12, errs
         assert errs["dW_off"] < 0.30 and errs["db_off"] < 0.30, errs
+        # against the rounding replay (oracle/kpconv_bf16_ref.py: the twin that also rounds where the bf16 path rounds), with
+        # the regulariser's gradients of min_d2 / deformed_KP taken from this run: per-row bounds on d offset_features and
+        # the bounds of tests/test_bf16_deform_chain_gpu.py on everything else
+        from test_bf16_deform_chain_gpu import COMPOSED, assert_chain, compare_module, replay_module
+        rep = replay_module(conv, x, q_pts, s_pts, inds, dy, got["g_min_d2"], got["g_dkp"])
+        er = {}
+        bad_r, near_r, _, _ = compare_module(conv, rep, out, xg.grad, got["d_off"], q_pts, s_pts, inds, er)
+        _report("%s_l%d_c%d_%s_replay" % (kind, lvl, ci, rows), er)
+        assert_chain(er, bad_r, near_r, q_pts.shape[0], "replay", COMPOSED)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -70,6 +70,64 @@ def test_fast_path_equals_generic_kernels(gpu, ci, co, radius, strided, modulate
         assert rel(a[key], b[key]) < tol, (key, rel(a[key], b[key]))
 
 
+FAST_CASES = [(16, 16, 0.9, False, False), (32, 64, 1.3, False, True), (48, 32, 1.1, True, True), (64, 64, 1.6, False, True),
+              (128, 32, 1.2, True, True), (256, 64, 1.0, False, True)]
+
+
+@pytest.mark.parametrize("ci,co,radius,strided,modulated", [c for c in FAST_CASES if c[0] % 16 == 0])
+def test_fast_path_equals_generic_kernels_bf16(gpu, ci, co, radius, strided, modulated):
+    """the same A/B on bf16 rows: both paths round wf_off, wf, out, dwf, the offsets' dz and dx, so what may differ is the
+    offset bias (the fast path adds it in the epilogue, the generic one afterwards: one fp32 ulp of the offsets), the fp32
+    accumulation order and the ties it decides -- bf16 outputs within their own ulp plus what a tie upstream moves them
+    by (2 x 2^-7 |r| + floor max|r|, floors out 4e-4, dx 2e-3), weight gradients 1e-3 (5.5e-4 measured).  The
+    offset bias gradient differs by rounding: the fast path sums the bf16-rounded d offset_features in the epilogue's
+    backward, the generic path's autograd sums them in fp32 (2.5e-3 measured, u = 2^-9): held at 1e-2, the bound
+    test_sorted_row_cutoff_changes_nothing uses for bf16"""
+    from weasal_amd import blocks
+    from weasal_amd.architectures import p2p_fitting_regularizer
+    from weasal_amd.blocks import KPConv
+    import weasal_amd.architectures as arch
+    q, s, inds = _geometry(gpu, 5000, radius, ci, strided)
+    np.random.seed(1)
+    torch.manual_seed(1)
+    conv = KPConv(15, 3, ci, co, 0.4 * radius, radius, deformable=True, modulated=modulated).to(gpu)
+    with torch.no_grad():
+        conv.offset_conv.weights.mul_(4.0 * (32.0 / ci) ** 0.5)
+        conv.offset_bias.normal_(0.0, 0.05)
+    x = torch.randn(s.shape[0], ci, device=gpu).to(torch.bfloat16)
+    dy = torch.randn(q.shape[0], co, device=gpu).to(torch.bfloat16)
+    mk = lambda c: types.SimpleNamespace(modules=lambda: [c], l1=torch.nn.L1Loss(), K=15, repulse_extent=1.2, deform_fitting_power=1.0)
+    res = {}
+    for fast in (True, False):
+        blocks.DEFORM_FAST_PATH = fast
+        arch.REGULARIZER_KERNEL = fast
+        try:
+            conv.zero_grad()
+            xg = x.clone().requires_grad_(True)
+            out = conv(q, s, inds, xg)
+            assert out.dtype == torch.bfloat16
+            reg = p2p_fitting_regularizer(mk(conv))
+            ((out.float() * dy.float()).sum() + reg).backward()
+            res[fast] = dict(out=out.detach(), reg=reg.detach(), min_d2=conv.min_d2.detach(), dkp=conv.deformed_KP.detach(),
+                             dx=xg.grad, dW=conv.weights.grad.clone(), dWo=conv.offset_conv.weights.grad.clone(),
+                             dbo=conv.offset_bias.grad.clone())
+        finally:
+            blocks.DEFORM_FAST_PATH = True
+            arch.REGULARIZER_KERNEL = True
+    a, b = res[True], res[False]
+    errs = {k: rel(a[k], b[k]) for k in a}
+    for key, floor in (("out", 4e-4), ("dx", 2e-3)):
+        d = (a[key].double() - b[key].double()).abs()
+        m = b[key].double().abs().max()
+        errs[key + "_ulp"] = float((d / (2 * 2.0 ** -7 * b[key].double().abs() + floor * m)).max())
+        errs[key + "_frac"] = float((d > 1e-6 * m).double().mean())
+    print("bf16 fast vs generic:", errs)
+    assert errs["dkp"] < 1e-6 and errs["min_d2"] < 1e-5 and errs["reg"] < 1e-5, errs
+    for key in ("out", "dx"):
+        assert errs[key + "_ulp"] <= 1.0 and errs[key + "_frac"] <= 5e-3, (key, errs)
+    assert errs["dW"] < 1e-3 and errs["dWo"] < 1e-3 and errs["dbo"] < 1e-2, errs
+
+
 def test_regularizer_kernel_vs_torch_ops(gpu):
     """ws_p2p_regularizer_fwd / _bwd against the torch-op restatement of models/architectures.py:36-51"""
     import weasal_amd.architectures as arch

@@ -205,3 +205,97 @@ def test_kpfcnn_mprm_vs_golden_cpu():
     assert sorted(grads) == [str(n) for n in g["grad_names"]]
     for n, ref_norm in zip(g["grad_names"], g["grad_norms"]):
         assert abs(float(grads[str(n)].double().norm()) - float(ref_norm)) <= 1e-3 * max(float(ref_norm), 1e-8), n
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the bf16 rounding replay (oracle/kpconv_bf16_ref.py) of one deformable bf16 layer
+# ---------------------------------------------------------------------------------------------------------------------
+def _deform_case(name, modulated):
+    """the g5 inputs, one KPConv module holding them (float64), fixed upstream gradients of out / min_d2 / deformed_KP"""
+    from weasal_amd.blocks import KPConv
+    g = golden(name)
+    ci, co = g["x"].shape[1], g["out"].shape[1]
+    np.random.seed(0)
+    conv = KPConv(15, 3, ci, co, float(g["KP_extent"]), float(g["radius"]), deformable=True, modulated=modulated)
+    with torch.no_grad():
+        conv.weights.copy_(t(g["weights"]))
+        conv.kernel_points.copy_(t(g["kernel_points"]))
+        conv.offset_conv.weights.copy_(t(g["offset_weights"]))
+        conv.offset_conv.kernel_points.copy_(t(g["offset_kernel_points"]))
+        conv.offset_bias.copy_(t(g["offset_bias"]))
+    conv = conv.double()
+    gen = torch.Generator().manual_seed(7)
+    nq = g["q_pts"].shape[0]
+    g1 = torch.randn(nq, 15, generator=gen, dtype=torch.float64)
+    g2 = torch.randn(nq, 15, 3, generator=gen, dtype=torch.float64)
+    return g, conv, g1, g2
+
+
+def _replay(g, conv, g1, g2, x, dy, rounding, trace=None):
+    from oracle import kpconv_bf16_ref
+    return kpconv_bf16_ref.replay_deformable(
+        x, t(g["q_pts"]), t(g["s_pts"]), t(g["inds"]), conv.kernel_points, conv.KP_extent, conv.weights, dy,
+        offset_weights=conv.offset_conv.weights, offset_bias=conv.offset_bias,
+        offset_kernel_points=conv.offset_conv.kernel_points, modulated=conv.modulated, g_min_d2=g1, g_dkp=g2,
+        rounding=rounding, trace=trace)
+
+
+G5_DEFORM = [("g5_kpconv_deform_16_16.npz", False), ("g5_kpconv_deform_mod_16_32.npz", True),
+             ("g5_kpconv_deform_strided_16_16.npz", False)]
+
+
+@pytest.mark.parametrize("name,modulated", G5_DEFORM)
+def test_bf16_replay_without_rounding_is_the_module_path(name, modulated):
+    """rounding=False: the replay is the module under cpu_reference_mode (the path goldens g4 / g5 pin), in float64"""
+    g, conv, g1, g2 = _deform_case(name, modulated)
+    x = t(g["x"]).double().requires_grad_(True)
+    dy = t(g["dy"]).double()
+    with kpconv_ref.cpu_reference_mode():
+        out = conv(t(g["q_pts"]).double(), t(g["s_pts"]).double(), t(g["inds"]), x)
+    got = {}
+    conv.offset_features.register_hook(lambda g_: got.__setitem__("d_off", g_.detach()))
+    ((out * dy).sum() + (conv.min_d2 * g1).sum() + (conv.deformed_KP * g2).sum()).backward()
+    r = _replay(g, conv, g1, g2, x.detach(), dy, rounding=False)
+    K, ci = conv.K, conv.in_channels
+    pairs = [(r["out"], out), (r["offsets"], conv.offset_features), (r["deformed_KP"], conv.deformed_KP),
+             (r["min_d2"], conv.min_d2), (r["dx"], x.grad), (r["dW"], conv.weights.grad.reshape(K * ci, -1)),
+             (r["d_off"], got["d_off"]), (r["dW_off"], conv.offset_conv.weights.grad.reshape(K * ci, -1)),
+             (r["db_off"], conv.offset_bias.grad)]
+    for i, (a, b) in enumerate(pairs):
+        assert a.dtype == torch.float64 and a.shape == b.shape, i
+        assert rel(a.numpy(), b.detach().numpy()) <= 1e-10, (i, rel(a.numpy(), b.detach().numpy()))
+
+
+def _bf16_valued(v):
+    return bool(torch.equal(v, v.float().to(torch.bfloat16).double()))
+
+
+@pytest.mark.parametrize("name,modulated", G5_DEFORM[:2])
+def test_bf16_replay_rounds_at_its_points(name, modulated):
+    """rounding=True on bf16 operands: every value at a listed rounding point is a bf16 value; the f32 points are not
+    rounded; the rounded result moves by a few units of bf16 roundoff u = 2^-9 -- and not by zero"""
+    g, conv, g1, g2 = _deform_case(name, modulated)
+    x = t(g["x"]).to(torch.bfloat16).double()
+    dy = t(g["dy"]).to(torch.bfloat16).double()
+    trace = {}
+    r = _replay(g, conv, g1, g2, x, dy, rounding=True, trace=trace)
+    n_off = conv.offset_dim
+    for key in ("wf", "out", "dx_main", "dx_off", "dx"):
+        assert _bf16_valued(r[key]), key
+    for key in ("wf_off", "dwf%d" % n_off, "dwf%d" % conv.out_channels, "dz%d" % n_off):
+        assert key in trace and all(_bf16_valued(v) for v in trace[key]), key
+    if n_off % 4 == 0:
+        # the bias gradient is the column sum of the rounded d offset_features (act_bwd_colsum_bf16_kernel)
+        dz = torch.cat(trace["dz%d" % n_off])
+        assert torch.allclose(dz.sum(0), r["db_off"], rtol=1e-12, atol=0)
+        assert not torch.equal(dz, r["d_off"])
+    for key in ("offsets", "min_d2", "deformed_KP", "d_off", "dW", "dW_off", "db_off"):
+        assert not _bf16_valued(r[key]), key                      # f32 points stay unrounded
+    exact = _replay(g, conv, g1, g2, x, dy, rounding=False)
+    u = 2.0 ** -9
+    # smooth in the rounded values: a few u; through the offsets the rounding moves the kernel points, and d w / d kp jumps at
+    # the influence extent (models/blocks.py:337), so those gradients are only required to move
+    for key, hi in (("wf", 4.0), ("out", 4.0), ("offsets", 4.0), ("dx", 8.0), ("dW", 4.0), ("d_off", None),
+                    ("dW_off", None), ("db_off", None)):
+        e = rel(r[key].numpy(), exact[key].numpy()) / u
+        assert e > 0.1 and (hi is None or e < hi), (key, e)

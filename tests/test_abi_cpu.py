@@ -29,6 +29,14 @@ def test_library_exports_every_declared_symbol():
     assert isinstance(lib.ws_device_count(), int)
 
 
+def test_env_switches_resolve():
+    """every WEASAL_* variable that _lib.lib() maps onto a library switch names an integer global the library exports"""
+    from weasal_amd import _lib
+    lib = _lib.lib()
+    for env, sym in _lib.ENV_SWITCHES:
+        C.c_int.in_dll(lib, sym)     # ValueError if the symbol is gone
+
+
 def test_argument_validation_needs_no_device():
     from weasal_amd import _lib
     lib = _lib.lib()

@@ -316,41 +316,24 @@ def test_gated_gather_backward_is_the_plain_one_times_the_activation_derivative(
 
 @pytest.mark.parametrize("m,k,n", [(100000, 128, 128), (10257, 1920, 128), (380, 7680, 512), (5000, 64, 32)])
 def test_split_bf16_products_are_fp32_accurate(gpu, m, k, n):
-    """the opt-in gemm_xb3 path (ws_gemm_split = 1: fp32 products as six bf16 MFMA partial products of exact three-way
-    splits) against float64, next to the default f32-input MFMA kernels on the same operands: its error is not larger"""
-    import ctypes
+    """the products the library runs (the f32-input MFMA kernels: y = x b, with split K on the short deep shape, and
+    dW = x^T dy) against float64 on rows of very different scale.  (Once the comparison of an opt-in bf16 three-way split
+    path with them; that path is gone, the bounds on the default path stay.)"""
     from weasal_amd import _lib, ops
-    try:
-        sw = ctypes.c_int.in_dll(_lib.lib(), "ws_gemm_split")
-    except ValueError:
-        pytest.skip("lab-only kernels (make CXXFLAGS+=-DWS_LAB_SPLIT_GEMM): not compiled into the product library")
     torch.manual_seed(m + k)
     x = torch.randn(m, k, device=gpu) * torch.exp(torch.randn(m, 1, device=gpu))       # rows of very different scale
     b = torch.randn(k, n, device=gpu) / k ** 0.5
     ref = x.double() @ b.double()
-    err = {}
-    try:
-        for mode in (0, 1):
-            sw.value = mode
-            y = ops._gemm_xb(x, b)
-            err[mode] = ((y.double() - ref).abs().max() / ref.abs().max()).item()
-    finally:
-        sw.value = 0
-    assert err[0] < 5e-6 and err[1] < 5e-6
-    assert err[1] <= 1.5 * err[0] + 1e-7
-    # dW = x^T dy on the same path
+    y = ops._gemm_xb(x, b)
+    err = ((y.double() - ref).abs().max() / ref.abs().max()).item()
+    assert err < 5e-6
+    # dW = x^T dy
     dy = torch.randn(m, n, device=gpu) * torch.exp(torch.randn(m, 1, device=gpu))
     xs = torch.randn(m, min(k, 512), device=gpu)
     ref_w = xs.double().t() @ dy.double()
-    errw = {}
-    try:
-        for mode in (0, 1):
-            sw.value = mode
-            o = ops._gemm_xty(_lib.lib(), xs, dy)
-            errw[mode] = ((o.double() - ref_w).abs().max() / ref_w.abs().max()).item()
-    finally:
-        sw.value = 0
-    assert errw[0] < 5e-6 and errw[1] < 5e-6 and errw[1] <= 1.5 * errw[0] + 2e-7
+    o = ops._gemm_xty(_lib.lib(), xs, dy)
+    errw = ((o.double() - ref_w).abs().max() / ref_w.abs().max()).item()
+    assert errw < 5e-6
 
 
 @pytest.mark.gpu

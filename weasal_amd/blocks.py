@@ -275,7 +275,7 @@ class UnaryBlock(nn.Module):
         links = None
         linked = batch is not None and residual is None and (getattr(batch, "gate_link_in", None) is not None
                                                              or getattr(batch, "gate_link_out", None) is not None)
-        if linked and ops.matmul_epilogue is _MATMUL_EPILOGUE and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and ops.FUSED_EPILOGUE and x.shape[0] >= ops.GEMM_MIN_ROWS:
+        if linked and ops.matmul_epilogue is _MATMUL_EPILOGUE and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32:
             from . import fused
             links = fused.linear_links(batch, x, True)
         if links is None:

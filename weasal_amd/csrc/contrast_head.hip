@@ -1,5 +1,5 @@
 // weasal_amd/csrc/contrast_head.hip -- everything of KPFCNN.contrast_loss (models/architectures.py:405-504) AROUND the
-// [N, slc_con] part (contrast.hip / contrast_mfma.hip): a handful of kernels instead of ~75 framework launches per step.
+// [N, slc_con] part (contrast_mfma.hip): a handful of kernels instead of ~75 framework launches per step.
 //
 //   head, forward  (:425-454, :475-476)   softmax -> pseudo_logits = max prob, pseudo label = argmax (given labels < 10 win),
 //                                         certain = (pseudo_logits > threshold) | labelled, L2-normalised rows `on`;

@@ -1,14 +1,28 @@
-// weasal_amd/csrc/contrast_mfma.hip -- the [N, slc_con] part of KPFCNN.contrast_loss (models/architectures.py:455-497) on the
-// matrix core (round 3; contrast.hip holds the VALU form and the description of the arithmetic, which is unchanged).
+// weasal_amd/csrc/contrast_mfma.hip -- the per-point part of the supervised contrastive loss of the pseudo-label trainer,
+// KPFCNN.contrast_loss (models/architectures.py:455-497), fused, on the matrix core.
+//
+// The reference materialises six [N, 1000] float matrices (three masks, the logits, exp_logits, log_prob) and their autograd
+// copies; N = 400 000 makes that ~1.6 GB each.  Here the slice table (1000 normalised logit rows + their index / certainty /
+// pseudo label) lives in LDS, and the row statistics
+//   m_i = max_j mul_ij,  E_i = sum_j use_ij exp(mul_ij - m_i),  P_i = sum_j pos_ij,  S_i = sum_j pos_ij (mul_ij - m_i)
+//   mul_ij = <o_i, s_j> / T,   use_ij = (slc_idx_j != i) & (certain_slc_j == certain_i),   pos_ij = use_ij & (lbl_slc_j == lbl_i)
+//   loss_i = -T * (S_i - P_i log(E_i + eps)) / (P_i + 1e-12)                          (:478-497)
+// come from ONE pass over the slice: nothing of size [N, 1000] exists.  The rows are unit vectors, so every logit lies in
+// [-1/T, 1/T]: the sums are taken against that bound,
+//   E' = sum_j use_ij exp(mul_ij - 1/T),   S' = sum_j pos_ij mul_ij,   m = max_j mul_ij   (over ALL columns, :484-486),
+// and rebased on the true maximum afterwards: E = E' exp(1/T - m), S = S' - P m.  exp(mul - 1/T) >= exp(-2/T) = 2e-9
+// at T = 0.1: no underflow, the same relative rounding as a two-pass form.  (The maximum cannot be dropped altogether: eps
+// enters log(E + eps) after the subtraction, :490.)  Backward: d mul_ij = g_i * (-T / (P_i + 1e-12))
+// * (pos_ij - P_i use_ij exp(mul_ij - m_i) / (E_i + eps)), with the max detached as in the reference (:486).
 //
 // The similarities  mul = O (N x C) . S^T (C x 1000) / T  are a dense product; so are both gradients,
 //     d O = W (N x 1000) . S (1000 x C) / T        d S = W^T (1000 x N) . O (N x C) / T,
-// with W = d loss / d mul evaluated element-wise from the similarities and the row statistics.  The VALU form spends
-// 12 + 12 fused multiply-adds and ~12 other instructions per (point, slice column) in each of three kernels; here a
+// with W = d loss / d mul evaluated element-wise from the similarities and the row statistics.  A thread-per-point VALU form
+// spends 12 + 12 fused multiply-adds and ~12 other instructions per (point, slice column) in each of three kernels; here a
 // 16 x 16 tile of similarities costs 3-4 v_mfma_f32_16x16x4_f32 (C <= 16 padded to a multiple of 4), the element-wise part
 // runs on the 4 values a lane holds of it, and the two gradient products take the tile of W back in as an MFMA operand
 // (through a 1 KB LDS scratch per wave: the D layout of one product is not the A / B layout of the next).
-//   forward    point tiles outer, slice tiles inner; the slice table (rows + index / tag) in LDS; one pass (see contrast.hip)
+//   forward    point tiles outer, slice tiles inner; the slice table (rows + index / tag) in LDS; one pass (see above)
 //   backward   ONE kernel for both gradients: slice tiles outer, the wave's 8 point tiles (128 points, staged in LDS)
 //              inner; d O accumulates in registers across the outer loop, d S per slice tile is summed over the four
 //              waves through LDS and written as the workgroup's partial (fixed-order reduction afterwards: deterministic).
@@ -102,7 +116,7 @@ __global__ __launch_bounds__(512) void contrast_fwd_mfma_kernel(const float* __r
             }
             const int64_t p = p0 + 4 * kk + r;
             if (i == 0 && p < n) {
-                const float Er = E[r] * __expf(inv_t - m[r]);         // rebased on the true maximum (contrast.hip)
+                const float Er = E[r] * __expf(inv_t - m[r]);         // rebased on the true maximum (see the top of the file)
                 const float dd = Er + eps;
                 loss[p] = -temperature * (((S[r] - P[r] * m[r]) - P[r] * logf(dd)) / (P[r] + 1e-12f));
                 rowmax[p] = m[r];
@@ -242,13 +256,17 @@ __global__ __launch_bounds__(1024) void contrast_reduce2_kernel(const float* __r
 
 }  // namespace
 
-// 2 = matrix-core kernels (this file), 1 = the VALU form of contrast.hip (A/B switch: WEASAL_CONTRAST_VARIANT)
-extern "C" int ws_contrast_variant = 2;
+extern "C" {
 
-extern "C" int ws_contrast_mfma_fwd(const float* on, int64_t n, int32_t c, const float* xs, int32_t s, const int64_t* slc_idx,
-                                    const uint8_t* certain, const int64_t* lbl, float temperature, float eps, float* loss,
-                                    float* rowmax, float* den, float* npos, void* stream)
+int ws_contrast_rows_fwd(const float* on, int64_t n, int32_t c, const float* xs, int32_t s, const int64_t* slc_idx,
+                         const uint8_t* certain, const int64_t* lbl, float temperature, float eps, float* loss,
+                         float* rowmax, float* den, float* npos, void* stream)
 {
+    WS_REQUIRE(n >= 0 && c >= 1 && s >= 1, "bad sizes n=%lld c=%d s=%d", (long long)n, c, s);
+    if (c > 16 || s > CM_SMAX) return ws_fail(WS_ERR_UNSUPPORTED, "contrast rows: c=%d (<= 16) s=%d (<= %d)", c, s, CM_SMAX);
+    WS_REQUIRE(n < (1ll << 31), "n exceeds int32");
+    if (n == 0) return WS_OK;
+    WS_REQUIRE(on && xs && slc_idx && certain && lbl && loss && rowmax && den && npos, "NULL argument");
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)ws_ceil_div(n, CF_WAVES * CF_TILES * 16);
     if (c <= 4) contrast_fwd_mfma_kernel<1><<<grid, 64 * CF_WAVES, 0, st>>>(on, n, c, xs, s, slc_idx, certain, lbl, temperature, eps, loss, rowmax, den, npos);
@@ -259,17 +277,25 @@ extern "C" int ws_contrast_mfma_fwd(const float* on, int64_t n, int32_t c, const
     return WS_OK;
 }
 
-extern "C" int64_t ws_contrast_mfma_bwd_scratch_bytes(int64_t n, int32_t c, int32_t s)
+int64_t ws_contrast_rows_bwd_scratch_bytes(int64_t n, int32_t c, int32_t s)
 {
     return ws_ceil_div(n > 0 ? n : 1, 4 * CB_TILES * 16) * (int64_t)s * c * (int64_t)sizeof(float);
 }
 
-extern "C" int ws_contrast_mfma_bwd(const float* on, int64_t n, int32_t c, const float* xs, int32_t s, const int64_t* slc_idx,
-                                    const uint8_t* certain, const int64_t* lbl, float temperature, const float* rowmax,
-                                    const float* den, const float* npos, const float* g, float* d_on, float* d_xs, void* scratch,
-                                    void* stream)
+int ws_contrast_rows_bwd(const float* on, int64_t n, int32_t c, const float* xs, int32_t s, const int64_t* slc_idx,
+                         const uint8_t* certain, const int64_t* lbl, float temperature, const float* rowmax,
+                         const float* den, const float* npos, const float* g, float* d_on, float* d_xs, void* scratch,
+                         void* stream)
 {
+    WS_REQUIRE(n >= 0 && c >= 1 && s >= 1, "bad sizes n=%lld c=%d s=%d", (long long)n, c, s);
+    if (c > 16 || s > CM_SMAX) return ws_fail(WS_ERR_UNSUPPORTED, "contrast rows: c=%d (<= 16) s=%d (<= %d)", c, s, CM_SMAX);
+    WS_REQUIRE(d_xs, "NULL argument");
     hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        WS_HIP(hipMemsetAsync(d_xs, 0, sizeof(float) * (size_t)s * c, st));
+        return WS_OK;
+    }
+    WS_REQUIRE(on && xs && slc_idx && certain && lbl && rowmax && den && npos && g && d_on && scratch, "NULL argument");
     const int chunks = (int)ws_ceil_div(n, 4 * CB_TILES * 16);
     float* partial = chunks == 1 ? d_xs : (float*)scratch;
 #define WS_CBM(NSV) contrast_bwd_mfma_kernel<NSV><<<chunks, 256, 0, st>>>(on, n, c, xs, s, slc_idx, certain, lbl, temperature, rowmax, den, npos, g, d_on, partial)
@@ -286,3 +312,5 @@ extern "C" int ws_contrast_mfma_bwd(const float* on, int64_t n, int32_t c, const
     }
     return WS_OK;
 }
+
+}  // extern "C"

@@ -14,10 +14,6 @@
 #include "ws_grid.h"
 #include "ws_bf16.h"
 
-extern "C" int ws_kpconv_table_interleave;
-extern "C" int ws_kpconv_gridw_interleave;
-extern "C" int ws_kpconv_k6_interleave;
-extern "C" int ws_kpconv_grid_interleave;
 namespace {
 
 constexpr float WS_SHADOW = 1e6f;
@@ -27,8 +23,6 @@ struct GeomParams {
     int influence;
     int aggregation;
     int deformable;   // 1: apply the in-range filter of blocks.py:301-325
-    int ablate;       // diagnostics only (tools/kpconv_lab.py): 1 = no wf store, 2 = every row gather reads row 0,
-                      // 4 = coordinates of point `lane` instead of the neighbour's, 8 = no index load
     const void* gate; // K4 / K4G only: rows [ns, ci] of the activated output y of the layer that produced x; the stored
     float gate_slope; // gradient is dx * LeakyReLU'(y) (1 where y > 0, gate_slope elsewhere) -- the activation backward
                       // of the preceding unary block folded into the store.  NULL: plain dx.
@@ -727,14 +721,10 @@ __global__ __launch_bounds__(256) void kpconv_gather_fwd_mfma_kernel(
         return order ? order[qi + vz] : (int)qi + vz;
     };
     const int col0 = lane < h ? lane : 0;
-    auto raw_idx = [&](int qv) -> int64_t {
-        if (g.ablate & 8) return ((int64_t)qv + 37 * col0) % ns;
-        return inds[(int64_t)qv * h + col0];
-    };
+    auto raw_idx = [&](int qv) -> int64_t { return inds[(int64_t)qv * h + col0]; };
     auto chk = [&](int64_t raw) -> int { return (lane < h && raw >= 0 && raw < ns) ? (int)raw : -1; };
     auto pt_raw = [&](int idx, float& px, float& py, float& pz) {
-        int ii = idx >= 0 ? idx : 0;
-        if (g.ablate & 4) ii = lane;
+        const int ii = idx >= 0 ? idx : 0;
         px = s_pts[3 * (int64_t)ii]; py = s_pts[3 * (int64_t)ii + 1]; pz = s_pts[3 * (int64_t)ii + 2];
     };
     auto q_xyz = [&](int qv, float& x_, float& y_, float& z_) {
@@ -830,7 +820,7 @@ __global__ __launch_bounds__(256) void kpconv_gather_fwd_mfma_kernel(
                             const bool incol = h0 + lane < h;
                             sx = incol ? px - qx : 3.0e18f; sy = incol ? py - qy : 3.0e18f; sz = incol ? pz - qz : 3.0e18f;
                         }
-                        const unsigned off = real && !(g.ablate & 2) ? (unsigned)idx * (unsigned)ci : 0u;
+                        const unsigned off = real ? (unsigned)idx * (unsigned)ci : 0u;
                         const int sstep = lane >> 2, skk = lane & 3;  // this lane's neighbour is column 4 sstep + skk
                         float* dst = nbf + (((sstep >> 1) * 4 + skk) * 8) + (sstep & 1);
                         dst[0] = sx; dst[2] = sy; dst[4] = sz; dst[6] = __uint_as_float(off);
@@ -929,7 +919,7 @@ __global__ __launch_bounds__(256) void kpconv_gather_fwd_mfma_kernel(
                         const int s = gi * GS + u;
                         const int nidx = __float_as_int(nv[u].w);     // >= 0 real, -2 shadow column, -1 past the row
                         const bool live = nidx >= 0 && s < steps;
-                        const unsigned row = (live && !(g.ablate & 2)) ? (unsigned)nidx : 0u;
+                        const unsigned row = live ? (unsigned)nidx : 0u;
                         const T* src = x + (size_t)(row * (unsigned)ci) + (chok ? ch : 0);
                         RowLoad<NT, T>::ld(src, xb[slot][u]);
                     }
@@ -1045,7 +1035,7 @@ __global__ __launch_bounds__(256) void kpconv_gather_fwd_mfma_kernel(
 #pragma unroll
                             for (int t = 0; t < NT; ++t) v[t] *= md;
                         }
-                        if (!(g.ablate & 1) || v[0] == 1.2345e30f) RowLoad<NT, T>::st(wf + (q * K + k) * ci + ch, v);
+                        RowLoad<NT, T>::st(wf + (q * K + k) * ci + ch, v);
                     }
                 }
             }
@@ -1363,7 +1353,7 @@ __global__ __launch_bounds__(256) void kpconv_gather_bwd_geom_def_kernel(
     const float* __restrict__ q_pts, int64_t nq, const float* __restrict__ s_pts, int64_t ns,
     const int64_t* __restrict__ inds, int h, const T* __restrict__ x, int ci, const T* __restrict__ dwf,
     const float4* __restrict__ kp4, const float* __restrict__ d_min_d2, float extent, float4* __restrict__ d_kp4,
-    const int32_t* __restrict__ order, int ilv)
+    const int32_t* __restrict__ order)
 {
     constexpr int K = 15;
     constexpr int CB = 4 * CK;                                   // channels per pass of the product
@@ -1374,7 +1364,7 @@ __global__ __launch_bounds__(256) void kpconv_gather_bwd_geom_def_kernel(
     float4* nb = nb_all[wave];
     const float inv_extent = 1.0f / extent;
     int64_t item0, istep, iend;
-    ws_wave_items(nq, order ? ilv : 0, wave, item0, istep, iend);
+    ws_wave_items(nq, 0, wave, item0, istep, iend);
     for (int64_t item = item0; item < iend; item += istep) {
         const int64_t q = order ? (int64_t)order[item] : item;
         float4 kq[4];
@@ -2121,26 +2111,14 @@ __global__ __launch_bounds__(256) void kpconv_gather_bwd_x_gridw_kernel(
 
 }  // namespace
 
-// 1 = entry pool + VALU accumulate (kpconv_gather_fwd_kernel), 2 = matrix core (kpconv_gather_fwd_mfma_kernel);
-// diagnostic switch (tools / A-B tests), not part of the drop-in surface
-extern "C" int ws_kpconv_variant;
-int ws_kpconv_variant = 2;
-extern "C" int ws_kpconv_ablate;          // diagnostics (GeomParams::ablate); 0 in every product path
-int ws_kpconv_ablate = 0;
-extern "C" int ws_kpconv_gs;              // diagnostics: > 0 forces the group size of the Ci = 32 matrix-core kernel
-int ws_kpconv_gs = 0;
-extern "C" int ws_kpconv_grid_rows;       // diagnostics: 0 = K4G always walks the cell grid (WEASAL_K4G_ROWS=0)
-int ws_kpconv_grid_rows = 1;
-extern "C" int ws_kpconv_split_nt = 4;        // ... with at most this many channels per lane (blocks of 16 x this many channels)
-extern "C" int ws_kpconv_split_rows = 4096;   // matrix-core K3 on fewer queries than this: one item per (query, channel block) (0 = never; WEASAL_K3_SPLIT_ROWS)
 extern "C" int ws_kpconv_grid_sorted;     // 1: ws_kpconv_gather_bwd_x_grid sums the incoming pairs in index order (the pair order of
-extern "C" int ws_kpconv_k6_interleave = 0;       // the same for the geometry backward on the matrix core (WEASAL_K6_INTERLEAVE)
-extern "C" int ws_kpconv_gridw_interleave = 512;    // the same for the wide-row K4G of config 5 (WEASAL_K4GW_INTERLEAVE)
-extern "C" int ws_kpconv_table_interleave = 0;    // the same for the transposed-table K4 (WEASAL_K4_INTERLEAVE)
-extern "C" int ws_kpconv_grid_interleave = 512;   // lab: workgroups per XCD of the interleaved assignment (WEASAL_K4G_INTERLEAVE)
 int ws_kpconv_grid_sorted = 0;            //    the transposed table: bit-identical to ws_kpconv_gather_bwd_x); 0: in grid-walk order
 
 namespace {
+
+constexpr int SPLIT_ROWS = 4096;   // matrix-core K3 on fewer queries than this: one item per (query, channel block)
+constexpr int SPLIT_NT = 4;        // ... with at most this many channels per lane (blocks of 16 x this many channels)
+constexpr int GRID_INTERLEAVE = 512;   // K4G and the wide-row K4G of config 5: workgroups per XCD of the interleaved assignment
 
 template <typename T>
 int gather_fwd_impl(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
@@ -2154,14 +2132,14 @@ int gather_fwd_impl(const float* q_pts, int64_t nq, const float* s_pts, int64_t 
     if (rc) return rc;
     if (nq == 0) return WS_OK;
     WS_REQUIRE(inds && x && wf && (kernel_points || deformed_kp), "NULL argument");
-    GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, ws_kpconv_ablate, nullptr, 0.0f, nullptr, 0, nullptr, nullptr,
+    GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, nullptr, 0.0f, nullptr, 0, nullptr, nullptr,
                  rows_sorted ? 1 : 0};
     hipStream_t st = (hipStream_t)stream;
     int grid = ws_grid(nq, 4);
     WS_REQUIRE(ns * (int64_t)ci < (1ll << 31), "ns*ci exceeds the 32-bit row offsets of the gather");
     const int vec4 = (ci % 4 == 0) && ws_row_aligned<T>(x) && ws_row_aligned<T>(wf);
     WS_REQUIRE(F32 || vec4, "bf16 feature rows need ci %% 4 == 0 and 8-byte aligned rows (ci=%d)", ci);
-    if (ws_kpconv_variant == 2 && ci > 4) {      // (the 3..4-channel input layer: the narrow-row pool form is 10 % faster)
+    if (ci > 4) {      // (the 3..4-channel input layer: the narrow-row pool form is 10 % faster)
         // matrix-core form (kpconv_gather_fwd_mfma_kernel): NT consecutive channels per lane, 16 NT channels per block
         const bool fastm = !deformed_kp && !modulations && influence == WS_INFLUENCE_LINEAR && aggregation == WS_AGGREGATION_SUM;
         int nt = ci <= 16 ? 1 : (ci <= 32 ? 2 : (ci <= 64 ? 4 : (ci <= 128 ? 8 : 16)));
@@ -2169,28 +2147,15 @@ int gather_fwd_impl(const float* q_pts, int64_t nq, const float* s_pts, int64_t 
         bool vecrow = (ci % nt == 0) && (nt == 1 || al16);
         if (!vecrow) nt = 1;
         if (nt == 1) vecrow = true;       // one channel per lane: any ci, any alignment (lanes past ci are masked)
-        if (fastm && !rows_sorted && ws_kpconv_split_rows > 0 && nq < ws_kpconv_split_rows && vecrow && nt > ws_kpconv_split_nt && ws_kpconv_split_nt > 0 &&
-            ci % ws_kpconv_split_nt == 0)
-            nt = ws_kpconv_split_nt;                              // narrower blocks: more items per query
-        if (fastm && !rows_sorted && ws_kpconv_split_rows > 0 && nq < ws_kpconv_split_rows && ci > 16 * nt) {
+        if (fastm && !rows_sorted && nq < SPLIT_ROWS && vecrow && nt > SPLIT_NT && ci % SPLIT_NT == 0)
+            nt = SPLIT_NT;                                        // narrower blocks: more items per query
+        if (fastm && !rows_sorted && nq < SPLIT_ROWS && ci > 16 * nt) {
             g.csplit = (ci + 16 * nt - 1) / (16 * nt);           // one channel block per item
             grid = ws_grid(nq * g.csplit, 4);
         }
 #define WS_FWDM2(NTV, MODEV, DEFV)                                                                                  \
     kpconv_gather_fwd_mfma_kernel<NTV, MODEV, DEFV, true, T><<<grid, 256, 0, st>>>(q_pts, nq, s_pts, ns, inds, h, x, ci, \
                                                                                    kernel_points, deformed_kp, modulations, g, wf, min_d2, order)
-        if (F32 && nt == 2 && fastm && ws_kpconv_gs > 0) {      // diagnostics: group-size sweep on the dominant shape
-            if constexpr (F32) {
-#define WS_FWDG(GSX) kpconv_gather_fwd_mfma_kernel<2, 0, false, true, T, GSX><<<grid, 256, 0, st>>>(q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, deformed_kp, modulations, g, wf, min_d2, order)
-                if (ws_kpconv_gs == 1) WS_FWDG(1);
-                else if (ws_kpconv_gs == 2) WS_FWDG(2);
-                else if (ws_kpconv_gs == 4) WS_FWDG(4);
-                else WS_FWDG(8);
-#undef WS_FWDG
-            }
-            WS_LAUNCH_CHECK();
-            return WS_OK;
-        }
 #define WS_FWDM(NTV)                                    \
     do {                                                \
         if (deformed_kp) WS_FWDM2(NTV, 1, true);        \
@@ -2210,39 +2175,22 @@ int gather_fwd_impl(const float* q_pts, int64_t nq, const float* s_pts, int64_t 
         WS_LAUNCH_CHECK();
         return WS_OK;
     }
-#define WS_FWD2(G, MODEV, DEFV, VECV)                                                                              \
-    do {                                                                                                           \
-        if constexpr (F32 || VECV)                                                                                 \
-            kpconv_gather_fwd_kernel<15, G, MODEV, DEFV, VECV, 4, T><<<grid, 256, 0, st>>>(                        \
-                q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, deformed_kp, modulations, g, wf, min_d2, order); \
-    } while (0)
-#define WS_FWD(G)                                                                                   \
-    do {                                                                                            \
-        if (deformed_kp) { if (vec4) WS_FWD2(G, 1, true, true); else WS_FWD2(G, 1, true, false); }  \
-        else if (fast) { if (vec4) WS_FWD2(G, 0, false, true); else WS_FWD2(G, 0, false, false); }  \
-        else { if (vec4) WS_FWD2(G, 1, false, true); else WS_FWD2(G, 1, false, false); }            \
-    } while (0)
+    // the 3..4-channel input layer: entry pool + VALU accumulate (kpconv_gather_fwd_kernel)
+#define WS_FWDV(G, MODEV, DEFV, VECV, PW)                                                                             \
+    kpconv_gather_fwd_kernel<15, G, MODEV, DEFV, VECV, PW, T><<<grid, 256, 0, st>>>(                                  \
+        q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, deformed_kp, modulations, g, wf, min_d2, order)
     const bool fast = influence == WS_INFLUENCE_LINEAR && aggregation == WS_AGGREGATION_SUM;
-    if (ci <= 4 && !vec4) {
+    if (vec4) {
+        if (deformed_kp) WS_FWDV(1, 1, true, true, 4);
+        else if (fast) WS_FWDV(1, 0, false, true, 4);
+        else WS_FWDV(1, 1, false, true, 4);
+    } else if constexpr (F32) {
         // narrow rows that are not float4 (the 3-channel input layer): 4-byte pieces, 16 slots of 4 lanes
-#define WS_FWDN(MODEV, DEFV)                                                                                          \
-    do {                                                                                                              \
-        if constexpr (F32)                                                                                            \
-            kpconv_gather_fwd_kernel<15, 4, MODEV, DEFV, false, 1, T><<<grid, 256, 0, st>>>(                          \
-                q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, deformed_kp, modulations, g, wf, min_d2, order);  \
-    } while (0)
-        if (deformed_kp) WS_FWDN(1, true);
-        else if (fast) WS_FWDN(0, false);
-        else WS_FWDN(1, false);
-#undef WS_FWDN
+        if (deformed_kp) WS_FWDV(4, 1, true, false, 1);
+        else if (fast) WS_FWDV(4, 0, false, false, 1);
+        else WS_FWDV(4, 1, false, false, 1);
     }
-    else if (ci <= 4) WS_FWD(1);
-    else if (ci <= 8) WS_FWD(2);
-    else if (ci <= 16) WS_FWD(4);
-    else if (ci <= 32) WS_FWD(8);
-    else WS_FWD(16);
-#undef WS_FWD2
-#undef WS_FWD
+#undef WS_FWDV
     WS_LAUNCH_CHECK();
     return WS_OK;
 }
@@ -2263,10 +2211,9 @@ int gather_bwd_x_impl(const float* q_pts, int64_t nq, const float* s_pts, int64_
     WS_REQUIRE(t_offsets && t_pairs && dwf && dx && (kernel_points || deformed_kp), "NULL argument");
     WS_REQUIRE(nq * (int64_t)h < (1ll << 31), "nq*h exceeds int32");
     WS_REQUIRE(nq * (int64_t)k * ci < (1ll << 31), "nq*k*ci exceeds the 32-bit row offsets of the gather");
-    GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, ws_kpconv_ablate, gate, gate_slope, nullptr, 0};
+    GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, gate, gate_slope, nullptr, 0};
     hipStream_t st = (hipStream_t)stream;
-    g.ilv = order ? ws_kpconv_table_interleave : 0;
-    const int grid = g.ilv > 0 ? 8 * (int)std::max<int64_t>(1, std::min<int64_t>(g.ilv, ws_ceil_div(ns, 32))) : ws_grid(ns, 4);
+    const int grid = ws_grid(ns, 4);
     const int vec4 = (ci % 4 == 0) && ws_row_aligned<T>(dwf) && ws_row_aligned<T>(dx);
     WS_REQUIRE(F32 || vec4, "bf16 feature rows need ci %% 4 == 0 and 8-byte aligned rows (ci=%d)", ci);
 #define WS_BWD2(G, MODEV, VECV)                                                                                       \
@@ -2305,7 +2252,7 @@ int gather_bwd_geom_impl(const float* q_pts, int64_t nq, const float* s_pts, int
     if (rc) return rc;
     if (nq == 0) return WS_OK;
     WS_REQUIRE(inds && x && dwf && deformed_kp && d_deformed_kp, "NULL argument");
-    GeomParams g{extent, influence, aggregation, 1, 0, nullptr, 0.0f, nullptr, 0};
+    GeomParams g{extent, influence, aggregation, 1, nullptr, 0.0f, nullptr, 0};
     hipStream_t st = (hipStream_t)stream;
     kpconv_gather_bwd_geom_kernel<15, T><<<ws_grid(nq, 4), 256, 0, st>>>(q_pts, nq, s_pts, ns, inds, h, x, ci, dwf,
                                                                           deformed_kp, modulations, d_min_d2, g,
@@ -2331,8 +2278,7 @@ int gather_bwd_x_grid_impl(const float* s_pts, int64_t ns, const void* grid_blob
     WS_REQUIRE(nb >= 1 && cells >= 1, "bad grid nb=%d cells=%lld", nb, (long long)cells);
     WS_REQUIRE(ns * (int64_t)k * ci < (1ll << 31), "ns*k*ci exceeds the 32-bit row offsets of the gather");
     WS_REQUIRE(!rows || rows_h >= 1, "index rows given without their width");
-    GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, ws_kpconv_ablate, gate, gate_slope,
-                 ws_kpconv_grid_rows ? rows : nullptr, rows_h};
+    GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, gate, gate_slope, rows, rows_h};
     hipStream_t st = (hipStream_t)stream;
     const char* base = (const char*)grid_blob;
     const CloudGrid* grids = (const CloudGrid*)base;
@@ -2340,7 +2286,7 @@ int gather_bwd_x_grid_impl(const float* s_pts, int64_t ns, const void* grid_blob
     const float4* sorted = (const float4*)(base + ws_grid_blob_sorted_off(nb, cells));
     const float r2 = radius * radius;                       // neighbors.cpp:226, as in the search
     const unsigned long long* kl = reinterpret_cast<const unsigned long long*>(key_last);
-    g.ilv = order ? ws_kpconv_grid_interleave : 0;
+    g.ilv = order ? GRID_INTERLEAVE : 0;
     const int grid = g.ilv > 0 ? 8 * (int)std::max<int64_t>(1, std::min<int64_t>(g.ilv, ws_ceil_div(ns, 32))) : ws_grid(ns, 4);
     const int vec4 = (ci % 4 == 0) && ws_row_aligned<T>(dwf) && ws_row_aligned<T>(dx);
     WS_REQUIRE(F32 || vec4, "bf16 feature rows need ci %% 4 == 0 and 8-byte aligned rows (ci=%d)", ci);
@@ -2384,7 +2330,7 @@ int gather_fwd_def_impl(const float* q_pts, int64_t nq, const float* s_pts, int6
     WS_REQUIRE(inds && x && wf && kp4, "NULL argument");
     WS_REQUIRE(aligned16(kp4), "kp4 must be 16-byte aligned");
     WS_REQUIRE(ns * (int64_t)ci < (1ll << 31), "ns*ci exceeds the 32-bit row offsets of the gather");
-    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 1, 0, nullptr, 0.0f, nullptr, 0, kp4};
+    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 1, nullptr, 0.0f, nullptr, 0, kp4};
     hipStream_t st = (hipStream_t)stream;
     const int grid = ws_grid(nq, 4);
     int nt = ci <= 16 ? 1 : (ci <= 32 ? 2 : (ci <= 64 ? 4 : (ci <= 128 ? 8 : 16)));
@@ -2421,7 +2367,7 @@ int gather_bwd_x_def_impl(const float* q_pts, int64_t nq, const float* s_pts, in
     WS_REQUIRE(t_offsets && t_pairs && dwf && dx && kp4 && aligned16(kp4), "NULL / unaligned argument");
     WS_REQUIRE(nq * (int64_t)h < (1ll << 31), "nq*h exceeds int32");
     WS_REQUIRE(nq * (int64_t)k * ci < (1ll << 31), "nq*k*ci exceeds the 32-bit row offsets of the gather");
-    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 1, 0, nullptr, 0.0f, nullptr, 0, kp4};
+    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 1, nullptr, 0.0f, nullptr, 0, kp4};
     hipStream_t st = (hipStream_t)stream;
     const int grid = ws_grid(ns, 4);
     const int vec4 = (ci % 4 == 0) && ws_row_aligned<T>(dwf) && ws_row_aligned<T>(dx);
@@ -2459,8 +2405,8 @@ int gather_bwd_x_gridw_impl(const float* s_pts, int64_t ns, const void* grid_blo
     WS_REQUIRE(nb >= 1 && cells >= 1, "bad grid nb=%d cells=%lld", nb, (long long)cells);
     WS_REQUIRE(ns * (int64_t)k * ci < (1ll << 31), "ns*k*ci exceeds the 32-bit row offsets of the gather");
     WS_REQUIRE(!rows || rows_h >= 1, "index rows given without their width");
-    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, kp4 ? 1 : 0, 0, nullptr, 0.0f,
-                 ws_kpconv_grid_rows ? rows : nullptr, rows_h, kp4, kp4 ? rmax : nullptr, 0};
+    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, kp4 ? 1 : 0, nullptr, 0.0f, rows, rows_h, kp4,
+                 kp4 ? rmax : nullptr, 0};
     hipStream_t st = (hipStream_t)stream;
     const char* base = (const char*)grid_blob;
     const CloudGrid* grids = (const CloudGrid*)base;
@@ -2468,7 +2414,7 @@ int gather_bwd_x_gridw_impl(const float* s_pts, int64_t ns, const void* grid_blo
     const float4* sorted = (const float4*)(base + ws_grid_blob_sorted_off(nb, cells));
     const float r2 = radius * radius;
     const unsigned long long* kl = reinterpret_cast<const unsigned long long*>(key_last);
-    g.ilv = order ? ws_kpconv_gridw_interleave : 0;
+    g.ilv = order ? GRID_INTERLEAVE : 0;
     const int grid = g.ilv > 0 ? 8 * (int)std::max<int64_t>(1, std::min<int64_t>(g.ilv, ws_ceil_div(ns, 32))) : ws_grid(ns, 4);
     const int vec4 = (ci % 4 == 0) && ws_row_aligned<T>(dwf) && ws_row_aligned<T>(dx);
     WS_REQUIRE(F32 || vec4, "bf16 feature rows need ci %% 4 == 0 and 8-byte aligned rows (ci=%d)", ci);
@@ -2515,16 +2461,15 @@ int gather_bwd_geom_def_impl(const float* q_pts, int64_t nq, const float* s_pts,
     if (ci % 16 != 0 || !aligned16(x) || !aligned16(dwf))
         return ws_fail(WS_ERR_UNSUPPORTED, "geometry backward on the matrix core needs ci %% 16 == 0 and 16-byte aligned rows (ci=%d)", ci);
     hipStream_t st = (hipStream_t)stream;
-    const int ilv = order ? ws_kpconv_k6_interleave : 0;
-    const int grid = ilv > 0 ? 8 * (int)std::max<int64_t>(1, std::min<int64_t>(ilv, ws_ceil_div(nq, 32))) : ws_grid(nq, 4);
+    const int grid = ws_grid(nq, 4);
 #define WS_K6(CKV, AREGV)                                                                                                 \
     do {                                                                                                                  \
         if (rows_sorted)                                                                                                  \
             kpconv_gather_bwd_geom_def_kernel<CKV, AREGV, T, true><<<grid, 256, 0, st>>>(q_pts, nq, s_pts, ns, inds, h, x, ci, dwf, kp4, \
-                                                                                         d_min_d2, extent, d_kp4, order, ilv); \
+                                                                                         d_min_d2, extent, d_kp4, order); \
         else                                                                                                              \
             kpconv_gather_bwd_geom_def_kernel<CKV, AREGV, T, false><<<grid, 256, 0, st>>>(q_pts, nq, s_pts, ns, inds, h, x, ci, dwf, kp4, \
-                                                                                          d_min_d2, extent, d_kp4, order, ilv); \
+                                                                                          d_min_d2, extent, d_kp4, order); \
     } while (0)
     if (ci == 16) WS_K6(4, true);
     else if (ci == 32) WS_K6(8, true);
@@ -2628,7 +2573,7 @@ int ws_kpconv_layer_fwd_fused(const float* q_pts, int64_t nq, const float* s_pts
     if (nq == 0) return WS_OK;
     WS_REQUIRE(inds && x && kernel_points && weights && out, "NULL argument");
     WS_REQUIRE(ns * (int64_t)ci < (1ll << 31), "ns*ci exceeds the 32-bit row offsets of the gather");
-    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 0, 0, nullptr, 0.0f, nullptr, 0, nullptr, nullptr, 0};
+    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 0, nullptr, 0.0f, nullptr, 0, nullptr, nullptr, 0};
     FuseArgs fz{weights, bias, slope, act, out};
     kpconv_gather_fwd_mfma_kernel<2, 0, false, true, float, WS_FUSE_GS, false, true><<<ws_grid(nq, 4), 256, 0, (hipStream_t)stream>>>(
         q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, nullptr, nullptr, g, nullptr, nullptr, order, fz);
@@ -2645,7 +2590,7 @@ int ws_kpconv_gather_fwd_variant(int32_t ci, int32_t mode, int32_t influence, in
     WS_REQUIRE(out && cap > 0 && ci >= 1, "bad argument");
     const char* t = rows_bf16 ? "bf16" : "float";
     const bool fast = influence == WS_INFLUENCE_LINEAR && aggregation == WS_AGGREGATION_SUM;
-    if (mode == 2 || (ws_kpconv_variant == 2 && ci > 4)) {
+    if (mode == 2 || ci > 4) {
         int nt = ci <= 16 ? 1 : (ci <= 32 ? 2 : (ci <= 64 ? 4 : (ci <= 128 ? 8 : 16)));
         if (ci % nt) nt = 1;
         const int m = mode == 2 ? 2 : (mode == 1 ? 1 : (fast ? 0 : 1));
@@ -2655,9 +2600,8 @@ int ws_kpconv_gather_fwd_variant(int32_t ci, int32_t mode, int32_t influence, in
         return WS_OK;
     }
     const int vec4 = ci % 4 == 0;
-    const int g = (ci <= 4) ? (vec4 ? 1 : 4) : (ci <= 8 ? 2 : (ci <= 16 ? 4 : (ci <= 32 ? 8 : 16)));
-    snprintf(out, (size_t)cap, "kpconv_gather_fwd_kernel<K=15, G=%d, MODE=%d, DEF=%s, VEC=%s, PW=%d, %s>%s", g, (mode || !fast) ? 1 : 0,
-             mode ? "true" : "false", vec4 ? "true" : "false", (ci <= 4 && !vec4) ? 1 : 4, t,
+    snprintf(out, (size_t)cap, "kpconv_gather_fwd_kernel<K=15, G=%d, MODE=%d, DEF=%s, VEC=%s, PW=%d, %s>%s", vec4 ? 1 : 4,
+             (mode || !fast) ? 1 : 0, mode ? "true" : "false", vec4 ? "true" : "false", vec4 ? 4 : 1, t,
              (rows_sorted && !mode && fast) ? " (sorted-row cutoff on)" : "");
     return WS_OK;
 }

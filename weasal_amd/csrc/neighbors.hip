@@ -275,8 +275,8 @@ __global__ __launch_bounds__(256) void nb_fill_kernel(const float* __restrict__ 
 //    their first 64 candidates fetched together, so nine independent gathers are in flight instead
 //    of nine dependent round trips;
 //  * hits are compacted through the wave's LDS slab, then each lane takes two keys (i and i+64) and
-//    finds their sorted positions by counting the smaller keys (LDS broadcast reads).
-template <typename OutT, bool BUCKET = false>
+//    finds their sorted positions by counting the smaller keys of the lower distance buckets and of its own.
+template <typename OutT>
 __global__ __launch_bounds__(256) void nb_fill128_kernel(const float* __restrict__ queries, int64_t nq,
                                                           const CloudGrid* __restrict__ grids, int nb,
                                                           const int32_t* __restrict__ cell_start,
@@ -353,72 +353,56 @@ __global__ __launch_bounds__(256) void nb_fill128_kernel(const float* __restrict
         cnt = min(cnt, CAP);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        // rank by counting: the keys are distinct (the index is part of the key), so the number of smaller
-        // keys IS the sorted position.  Every lane compares its (up to) two keys with key i, read as an LDS
-        // broadcast -- independent iterations, no cross-lane shuffle and no dependent latency chain (the
-        // 128-key bitonic network this replaces was 28 serially dependent shuffle stages).
         const unsigned long long a = lane < cnt ? slab[lane] : ~0ull;
         const unsigned long long bkey = lane + 64 < cnt ? slab[lane + 64] : ~0ull;
-        int ra = 0, rb = 0;
-        if constexpr (BUCKET) {
-            // round 3: one level of buckets in front of the counting (as in nb_fill_wide_kernel): 64 buckets over [0, r^2),
-            // bucket = (int)(d2 * 64 / r^2) is monotone in d2, so rank = keys in smaller buckets + smaller keys of the own
-            // bucket -- ~1 key per bucket: a 64-wide scan and a two- or three-step count instead of cnt (60 .. 90) steps
-            __shared__ int hist_all[4][64];
-            __shared__ unsigned char member_all[4][128];
-            int* hist = hist_all[wave];
-            unsigned char* member = member_all[wave];
-            hist[lane] = 0;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const float bscale = 64.0f / r2;
-            const int ba = min(63, (int)(__uint_as_float((unsigned)(a >> 32)) * bscale));
-            const int bb = min(63, (int)(__uint_as_float((unsigned)(bkey >> 32)) * bscale));
-            int pa = 0, pb = 0;
-            if (lane < cnt) pa = atomicAdd(&hist[ba], 1);
-            if (lane + 64 < cnt) pb = atomicAdd(&hist[bb], 1);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int own = hist[lane];
-            int incl = own;
+        // rank: the keys are distinct (the index is part of the key), so the number of smaller keys IS the sorted position.
+        // One level of buckets in front of the counting (as in nb_fill_wide_kernel): 64 buckets over [0, r^2),
+        // bucket = (int)(d2 * 64 / r^2) is monotone in d2, so rank = keys in smaller buckets + smaller keys of the own
+        // bucket -- ~1 key per bucket: a 64-wide scan and a two- or three-step count instead of cnt (60 .. 90) steps
+        __shared__ int hist_all[4][64];
+        __shared__ unsigned char member_all[4][128];
+        int* hist = hist_all[wave];
+        unsigned char* member = member_all[wave];
+        hist[lane] = 0;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const float bscale = 64.0f / r2;
+        const int ba = min(63, (int)(__uint_as_float((unsigned)(a >> 32)) * bscale));
+        const int bb = min(63, (int)(__uint_as_float((unsigned)(bkey >> 32)) * bscale));
+        int pa = 0, pb = 0;
+        if (lane < cnt) pa = atomicAdd(&hist[ba], 1);
+        if (lane + 64 < cnt) pb = atomicAdd(&hist[bb], 1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const int own = hist[lane];
+        int incl = own;
 #pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(incl, o, 64);
-                incl += lane >= o ? t : 0;
-            }
-            int maxb = own;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(incl, o, 64);
+            incl += lane >= o ? t : 0;
+        }
+        int maxb = own;
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) maxb = max(maxb, __shfl_xor(maxb, o, 64));
-            maxb = __builtin_amdgcn_readfirstlane(maxb);
-            __shared__ int start_all[4][64];
-            int* start = start_all[wave];
-            start[lane] = incl - own;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int sa = start[ba], sb = start[bb];
-            const int na = lane < cnt ? hist[ba] : 0, nbk = lane + 64 < cnt ? hist[bb] : 0;
-            if (lane < cnt) member[sa + pa] = (unsigned char)lane;
-            if (lane + 64 < cnt) member[sb + pb] = (unsigned char)(lane + 64);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            ra = sa; rb = sb;
-            for (int t = 0; t < maxb; ++t) {
-                const bool oka = t < na, okb = t < nbk;
-                const unsigned long long ka = slab[member[oka ? sa + t : 0]];
-                const unsigned long long kb = slab[member[okb ? sb + t : 0]];
-                ra += (oka && ka < a) ? 1 : 0;
-                rb += (okb && kb < bkey) ? 1 : 0;
-            }
-        } else if (cnt <= 64) {
-#pragma unroll 8
-            for (int i = 0; i < cnt; ++i) ra += slab[i] < a ? 1 : 0;
-        } else {
-#pragma unroll 8
-            for (int i = 0; i < cnt; ++i) {
-                const unsigned long long kk = slab[i];
-                ra += kk < a ? 1 : 0;
-                rb += kk < bkey ? 1 : 0;
-            }
+        for (int o = 32; o > 0; o >>= 1) maxb = max(maxb, __shfl_xor(maxb, o, 64));
+        maxb = __builtin_amdgcn_readfirstlane(maxb);
+        __shared__ int start_all[4][64];
+        int* start = start_all[wave];
+        start[lane] = incl - own;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const int sa = start[ba], sb = start[bb];
+        const int na = lane < cnt ? hist[ba] : 0, nbk = lane + 64 < cnt ? hist[bb] : 0;
+        if (lane < cnt) member[sa + pa] = (unsigned char)lane;
+        if (lane + 64 < cnt) member[sb + pb] = (unsigned char)(lane + 64);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        int ra = sa, rb = sb;
+        for (int t = 0; t < maxb; ++t) {
+            const bool oka = t < na, okb = t < nbk;
+            const unsigned long long ka = slab[member[oka ? sa + t : 0]];
+            const unsigned long long kb = slab[member[okb ? sb + t : 0]];
+            ra += (oka && ka < a) ? 1 : 0;
+            rb += (okb && kb < bkey) ? 1 : 0;
         }
         OutT* orow = out + q * width;
         if (lane < cnt && ra < width) orow[ra] = (OutT)(unsigned)(a & 0xffffffffull);
@@ -723,9 +707,6 @@ struct DevBuf {
 
 }  // namespace
 
-// A/B switch (WEASAL_NB_BUCKET=0/1): bucketed rank in the <= 128-neighbour search
-extern "C" int ws_nb_bucket128 = 1;
-
 struct ws_neighbors_ws {
     DevBuf<CloudGrid> grids;
     DevBuf<float> bbox;
@@ -895,21 +876,18 @@ struct KeyLastGuard {
     ~KeyLastGuard() { if (ws) ws->key_last = nullptr; }
 };
 
-// lab switches (tools/k1_lab.py): grid cap and queries per workgroup of the fill launch
 extern "C" int ws_nb_wide_caps = 1;       // 1: slab of the wide asynchronous search sized to the width (576 / 704 / 1024), 0: always 1024 (A/B: WEASAL_NB_WIDE_CAPS)
 // grid cap of the fill launch on the ASYNCHRONOUS entries (the pyramid builders; the synchronous drop-in entries keep 4 096).  1 024 workgroups (4 per CU: the fill's queries are walked in cell order either way) instead of
-// 4 096: alone the 13 searches of a pyramid take 1.29 instead of 1.08 ms (tools/k1_lab2.py), but they run under the training
-// stream, which gets wave slots back -- DALES step 13.53 -> 13.42 ms, inference 5.20 -> 5.09 ms, config 5 38.7 -> 38.4 ms (A/B: WEASAL_NB_MAX_BLOCKS, 0 = 4 096)
-extern "C" int ws_nb_max_blocks = 1024;
-extern "C" int ws_nb_queries_per_block = 0;
+// 4 096: alone the 13 searches of a pyramid take 1.29 instead of 1.08 ms, but they run under the training
+// stream, which gets wave slots back -- DALES step 13.53 -> 13.42 ms, inference 5.20 -> 5.09 ms, config 5 38.7 -> 38.4 ms
+constexpr int NB_MAX_BLOCKS = 1024;
 
 // beside: the call comes through the asynchronous entries, i.e. from a pyramid builder working beside a training stream: the
 // grid cap above applies; the synchronous entries (the drop-in `batch_query` and plan / fill) have the GPU to themselves: 4 096
 static int nb_launch_fill(ws_neighbors_ws* ws, int cap, int32_t width, int32_t* out_i32, int64_t* out_i64,
                           bool with_counts, hipStream_t st, bool beside = false)
 {
-    const int grid = ws_grid(ws->nq, ws_nb_queries_per_block > 0 ? ws_nb_queries_per_block : 4,
-                             (beside && ws_nb_max_blocks > 0) ? ws_nb_max_blocks : 256 * 16);
+    const int grid = ws_grid(ws->nq, 4, beside ? NB_MAX_BLOCKS : 256 * 16);
     const int32_t* qo = ws->self_query ? ws->order.p : nullptr;
     int32_t* cn = with_counts ? ws->counts.p : nullptr;
     int32_t* mx = with_counts ? ws->max_count_word : nullptr;
@@ -924,11 +902,11 @@ static int nb_launch_fill(ws_neighbors_ws* ws, int cap, int32_t width, int32_t* 
                                                                ws->sorted.p, ws->r2, ws->ns, width, qo, out_i64, cn, mx, kl);  \
     } while (0)
     if (cap <= 128) {
-#define WS_NB128(OT, BK, OUT)                                                                                                \
-    nb_fill128_kernel<OT, BK><<<grid, 256, 0, st>>>(ws->queries, ws->nq, ws->grids.p, ws->nb, ws->cell_start.p, ws->sorted.p, \
-                                                    ws->r2, ws->ns, width, qo, OUT, cn, mx, kl)
-        if (ws_nb_bucket128) { if (out_i32) WS_NB128(int32_t, true, out_i32); else WS_NB128(int64_t, true, out_i64); }
-        else { if (out_i32) WS_NB128(int32_t, false, out_i32); else WS_NB128(int64_t, false, out_i64); }
+#define WS_NB128(OT, OUT)                                                                                                    \
+    nb_fill128_kernel<OT><<<grid, 256, 0, st>>>(ws->queries, ws->nq, ws->grids.p, ws->nb, ws->cell_start.p, ws->sorted.p,     \
+                                                ws->r2, ws->ns, width, qo, OUT, cn, mx, kl)
+        if (out_i32) WS_NB128(int32_t, out_i32);
+        else WS_NB128(int64_t, out_i64);
 #undef WS_NB128
     }
     else if (cap <= 1024) {

@@ -309,14 +309,13 @@ __global__ __launch_bounds__(256) void closest_pool_bwd_vec_kernel(const float* 
     }
 }
 
-// workgroups per XCD of the interleaved assignment (0 = contiguous chunks; A/B switch WEASAL_POOL_INTERLEAVE).  Level-0 max-pool
-// of the DALES step (71 000 x 59 rows of 512 bytes): forward 245 -> 195 us in the step, 136 -> 97 us alone (tools/pool_lab.py)
-extern "C" int ws_pool_interleave = 256;
-extern "C" int ws_pool_unroll = 8;          // neighbour rows in flight per lane of the 128-channel max-pool forward: 8 (level 0 of the DALES step: 184 -> 172 us alone) or 4
-extern "C" int ws_pool_split_rows = 8192;   // max-pools over fewer rows than this give every 256-channel chunk of a row a wave of its own (0 = never)
+// workgroups per XCD of the interleaved assignment (with a spatial order; without one: contiguous chunks).  Level-0 max-pool
+// of the DALES step (71 000 x 59 rows of 512 bytes): forward 245 -> 195 us in the step, 136 -> 97 us alone
+constexpr int POOL_INTERLEAVE = 256;
+constexpr int POOL_SPLIT_ROWS = 8192;   // max-pools over fewer rows than this give every 256-channel chunk of a row a wave of its own
 static int pool_split(int64_t rows, int c)
 {
-    return (ws_pool_split_rows > 0 && rows < ws_pool_split_rows && c > 256) ? (int)ws_ceil_div(c, 256) : 1;
+    return (rows < POOL_SPLIT_ROWS && c > 256) ? (int)ws_ceil_div(c, 256) : 1;
 }
 extern "C" int ws_closest_bwd_vec = 1;      // nearest-upsampling backward: 1 = float4 lanes, several incoming rows side by side (A/B: WEASAL_CLOSEST_BWD_VEC)
 static inline int pool_grid(int64_t groups, int ilv)
@@ -335,7 +334,7 @@ int max_pool_fwd_impl(const T* x, int64_t ns, int32_t c, const int64_t* inds, in
     WS_REQUIRE(inds && out && (ns == 0 || x), "NULL argument");
     hipStream_t st = (hipStream_t)stream;
     const bool vec = (c % 4 == 0) && ws_row_aligned<T>(x) && ws_row_aligned<T>(out) && (!arg || al16p(arg));
-    const int ilv = order ? ws_pool_interleave : 0;
+    const int ilv = order ? POOL_INTERLEAVE : 0;
     if (vec && c <= 16) max_pool_fwd_vec_kernel<4, T><<<pool_grid(ws_ceil_div(nq, 16), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
     else if (vec && c <= 32) max_pool_fwd_vec_kernel<8, T><<<pool_grid(ws_ceil_div(nq, 8), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
     else if (vec && c <= 64) max_pool_fwd_vec_kernel<16, T><<<pool_grid(ws_ceil_div(nq, 4), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
@@ -359,7 +358,7 @@ int max_pool_bwd_impl(const T* dy, const int32_t* arg, int64_t nq, int32_t h, in
     WS_REQUIRE(t_offsets && dx && (nq == 0 || (dy && arg && t_pairs)), "NULL argument");
     hipStream_t st = (hipStream_t)stream;
     const bool vec = (c % 4 == 0) && ws_row_aligned<T>(dy) && ws_row_aligned<T>(dx) && al16p(arg);
-    const int ilv = order ? ws_pool_interleave : 0;
+    const int ilv = order ? POOL_INTERLEAVE : 0;
     if (vec && c <= 32) max_pool_bwd_vec_kernel<8, T><<<pool_grid(ws_ceil_div(ns, 8), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv);
     else if (vec && c <= 64) max_pool_bwd_vec_kernel<16, T><<<pool_grid(ws_ceil_div(ns, 4), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv);
     else if (vec && c <= 128) max_pool_bwd_vec_kernel<32, T><<<pool_grid(ws_ceil_div(ns, 2), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv);
@@ -377,12 +376,12 @@ int max_pool_fwd_u8_impl(const float* x, int64_t ns, int32_t c, const int64_t* i
                          const int32_t* order, hipStream_t st)
 {
     if (nq == 0) return WS_OK;
-    const int ilv = order ? ws_pool_interleave : 0;       // (only with a spatial order is a neighbouring group a neighbouring place)
+    const int ilv = order ? POOL_INTERLEAVE : 0;       // (only with a spatial order is a neighbouring group a neighbouring place)
     if (c <= 16) max_pool_fwd_vec_kernel<4, float, uint8_t><<<pool_grid(ws_ceil_div(nq, 16), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
     else if (c <= 32) max_pool_fwd_vec_kernel<8, float, uint8_t><<<pool_grid(ws_ceil_div(nq, 8), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
     else if (c <= 64) max_pool_fwd_vec_kernel<16, float, uint8_t><<<pool_grid(ws_ceil_div(nq, 4), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
-    else if (c <= 128 && ws_pool_unroll == 8) max_pool_fwd_vec_kernel<32, float, uint8_t, 8><<<pool_grid(ws_ceil_div(nq, 2), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
-    else if (c <= 128) max_pool_fwd_vec_kernel<32, float, uint8_t><<<pool_grid(ws_ceil_div(nq, 2), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
+    // 128 channels: 8 neighbour rows in flight per lane (level 0 of the DALES step: 184 -> 172 us alone, against 4)
+    else if (c <= 128) max_pool_fwd_vec_kernel<32, float, uint8_t, 8><<<pool_grid(ws_ceil_div(nq, 2), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
     else {
         const int sp = pool_split(nq, c);
         max_pool_fwd_vec_kernel<64, float, uint8_t><<<pool_grid(nq * sp, ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv, sp);
@@ -396,7 +395,7 @@ int max_pool_bwd_u8_impl(const float* dy, const uint8_t* arg, int64_t nq, int32_
 {
     (void)nq;
     if (ns == 0) return WS_OK;
-    const int ilv = order ? ws_pool_interleave : 0;       // (only with a spatial order is a neighbouring group a neighbouring place)
+    const int ilv = order ? POOL_INTERLEAVE : 0;       // (only with a spatial order is a neighbouring group a neighbouring place)
     if (c <= 32) max_pool_bwd_vec_kernel<8, float, uint8_t><<<pool_grid(ws_ceil_div(ns, 8), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv, add);
     else if (c <= 64) max_pool_bwd_vec_kernel<16, float, uint8_t><<<pool_grid(ws_ceil_div(ns, 4), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv, add);
     else if (c <= 128) max_pool_bwd_vec_kernel<32, float, uint8_t><<<pool_grid(ws_ceil_div(ns, 2), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv, add);

@@ -522,10 +522,6 @@ def p2p_regularizer(deformed_kp, min_d2, extent, repulse_extent):
 # ------------------------------------------------------------------------------------------------
 # tall-skinny GEMMs (unary MLPs and the kernel contraction) on the f32 MFMA
 # ------------------------------------------------------------------------------------------------
-FUSED_EPILOGUE = os.environ.get("WEASAL_FUSED_EPILOGUE", "1") != "0"   # A/B switch (diagnostics)
-GEMM_MIN_ROWS = int(os.environ.get("WEASAL_GEMM_MIN_ROWS", "0"))        # A/B switch (diagnostics): fewer rows -> torch.matmul (library GEMM); default: never
-XTY_MIN_ROWS = 0         # A/B switch: rows below which dW = x^T dy goes to the library GEMM (in the training step the MFMA
-                         # reduction is ahead at every level that reaches it: 0.42 ms vs 0.54 ms per step at M = 10 257)
 
 
 def _gemm_xb(x, b):
@@ -552,12 +548,10 @@ def _xb_launch(lib, x, m, k, b, n, bias, residual, slope, y):
 
 
 def _gemm_xty(lib, x, dy):
-    """x^T @ dy: the LDS-free MFMA reduction (rows split per workgroup: gemm.hip xty_chunk); XTY_MIN_ROWS > 0 is a
-    diagnostics switch to the library GEMM for shorter operands"""
+    """x^T @ dy: the LDS-free MFMA reduction (rows split per workgroup: gemm.hip xty_chunk; in the training step it is ahead of
+    the library GEMM at every level that reaches it: 0.42 ms vs 0.54 ms per step at M = 10 257)"""
     m, k = x.shape
     n = dy.shape[1]
-    if m < XTY_MIN_ROWS:
-        return torch.matmul(x.t(), dy)
     db = torch.empty((k, n), dtype=torch.float32, device=x.device)
     scratch = torch.empty(max(lib.ws_gemm_xty_scratch_bytes(m, k, n), 16), dtype=torch.uint8, device=x.device)
     check(lib.ws_gemm_xty(ptr(x), m, k, x.stride(0), ptr(dy), n, dy.stride(0), ptr(db), ptr(scratch), current_stream()))
@@ -782,22 +776,15 @@ class _MatmulEpilogue(torch.autograd.Function):
 
 def matmul_epilogue(x, b, bias=None, residual=None, slope=None, out_f32=False, links=None):
     """act(x @ b + bias + residual): one MFMA kernel (b is [K,N]; short, deep products of the deep layers split K).
-    GEMM_MIN_ROWS > 0 (diagnostics) hands operands with fewer rows to the library GEMM through torch.
-    bf16 rows (x.dtype bfloat16) always take the bf16 MFMA kernel; out_f32 keeps its output in f32."""
+    bf16 rows (x.dtype bfloat16) always take the bf16 MFMA kernel; out_f32 keeps its output in f32.  Operands the kernels
+    do not take (not 2-D, not float32 / bf16) go through torch.matmul."""
     _need_cuda(x, b)
     if x.dtype == torch.bfloat16 and x.dim() == 2:
         return _MatmulEpilogueBF16.apply(x, b, bias, residual, slope, bool(out_f32))
-    if FUSED_EPILOGUE and x.dim() == 2 and x.shape[0] >= GEMM_MIN_ROWS and x.dtype == torch.float32:
+    if x.dim() == 2 and x.dtype == torch.float32:
         return _MatmulEpilogue.apply(x, b, bias, residual, slope, links)
     if links is not None and (links[0] is not None or links[1] is not None):
         raise _lib.WeasalHipError("matmul_epilogue: gate links need the float32 kernel path")
-    if not FUSED_EPILOGUE:
-        y = matmul(x, b)
-        if bias is not None:
-            y = y + bias
-        if residual is not None:
-            y = y + residual
-        return y if slope is None else torch.nn.functional.leaky_relu(y, slope)
     y = torch.matmul(x, b)
     if bias is not None:
         y = y + bias
@@ -807,11 +794,11 @@ def matmul_epilogue(x, b, bias=None, residual=None, slope=None, out_f32=False, l
 
 
 def matmul(x, b):
-    """x [M,K] @ b [K,N] on the MFMA kernels of this library (GEMM_MIN_ROWS > 0: diagnostics switch to the library GEMM)"""
+    """x [M,K] @ b [K,N] on the MFMA kernels of this library (other operands: torch.matmul)"""
     _need_cuda(x, b)
     if x.dtype == torch.bfloat16 and x.dim() == 2 and b.dim() == 2:
         return _MatmulEpilogueBF16.apply(x, b, None, None, None, False)
-    if x.dim() == 2 and b.dim() == 2 and x.shape[0] >= GEMM_MIN_ROWS and x.dtype == torch.float32:
+    if x.dim() == 2 and b.dim() == 2 and x.dtype == torch.float32:
         return _MatmulXB.apply(x, b)
     return torch.matmul(x, b)
 

@@ -346,6 +346,13 @@ __global__ __launch_bounds__(256) void kpconv_gather_fwd_kernel(
         }
     }
 
+    // bf16 rows: the running sum of a row that takes several flushes (H > 64, pool overflow) stays in f32 registers and is
+    // rounded once per store -- read back from wf it would be rounded to bf16 at every flush.  One channel chunk per lane
+    // (the launcher sends ci <= 4 = CC here), so one float4 per kernel point of the slot.
+    constexpr bool CARRY = sizeof(T) == 2;
+    float4 carry[CARRY ? KPS : 1];
+#pragma unroll
+    for (int t = 0; t < (CARRY ? KPS : 1); ++t) carry[t] = make_float4(0.f, 0.f, 0.f, 0.f);
     // flush the pool: every slot walks the segments of its kernel points for all channel chunks.
     // maxlen = longest segment (wave-uniform): every round runs that many steps.
     auto flush = [&](int64_t q, bool accumulate, int maxlen) {
@@ -429,7 +436,11 @@ __global__ __launch_bounds__(256) void kpconv_gather_fwd_kernel(
                     if (modulations) { const float md = modulations[q * K + k]; a.x *= md; a.y *= md; a.z *= md; a.w *= md; }
                     T* dst = wf + (q * K + k) * ci + ch;
                     if (VEC) {
-                        if (accumulate) { const float4 o = ld4(dst); a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w; }
+                        if (accumulate) {
+                            const float4 o = CARRY ? carry[CARRY ? kk : 0] : ld4(dst);
+                            a.x += o.x; a.y += o.y; a.z += o.z; a.w += o.w;
+                        }
+                        if (CARRY) carry[CARRY ? kk : 0] = a;
                         st4(dst, a);
                     } else {
                         if (ch + 0 < ci) st1(dst + 0, (accumulate ? ld1(dst + 0) : 0.f) + a.x);

@@ -746,6 +746,22 @@ int ws_kpconv_layer_fwd_fused(const float* q_pts, int64_t nq, const float* s_pts
  * generic entries, 2 deformable fast path): for reports, no device work */
 int ws_kpconv_gather_fwd_variant(int32_t ci, int32_t mode, int32_t influence, int32_t aggregation, int32_t rows_bf16,
                                  int32_t rows_sorted, char* out, int32_t cap);
+/* the launches the dense products make for these arguments (the dispatchers' own plan functions; pointers are only tested
+ * for alignment, nothing is read or launched): "kernel<template arguments> key=value ..." into out[cap].
+ * ws_gemm_xb_variant: any ws_gemm_xb* entry (b_row_stride < 0 = row-major [K, N]; gate_y / mask NULL when absent);
+ * ws_gemm_xty_variant: ws_gemm_xty (ldo = 0), the pitched dW (ldo >= n), ws_gemm_xty_bf16 (rows_bf16 = 1);
+ * ws_act_bwd_colsum_variant: ws_act_bwd_colsum[_dropout]; the bf16 forms: ws_gemm_xbt_bf16, ws_act_bwd_colsum_bf16 */
+int ws_gemm_xb_variant(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int64_t b_row_stride, int64_t b_col_stride,
+                       int32_t n, const float* bias, const float* residual, int64_t ldr, const float* gate_y, int64_t ldg,
+                       const uint8_t* mask, int64_t ldm, const float* y, int64_t ldy, const void* scratch, int64_t scratch_bytes,
+                       char* out, int32_t cap);
+int ws_gemm_xty_variant(const void* x, int64_t m, int32_t k, int64_t ldx, const void* y, int32_t n, int64_t ldy, float* out_m,
+                        int64_t ldo, void* scratch, int32_t rows_bf16, char* out, int32_t cap);
+int ws_act_bwd_colsum_variant(const float* dy, int64_t m, int32_t n, int64_t lddy, const float* y, int64_t ldy, const float* dz,
+                              int64_t lddz, float* colsum, void* scratch, char* out, int32_t cap);
+int ws_gemm_xbt_bf16_variant(int64_t m, int32_t k, int32_t n, const float* bias, const uint16_t* residual, int64_t ldr, const void* y,
+                             int64_t ldy, int32_t out_f32, char* out, int32_t cap);
+int ws_act_bwd_colsum_bf16_variant(int32_t dy_f32, int64_t m, int32_t n, float* colsum, void* scratch, char* out, int32_t cap);
 int64_t ws_p2p_regularizer_scratch_bytes(int64_t n);
 int ws_p2p_regularizer_fwd(const float* deformed_kp, const float* kp4, const float* min_d2, int64_t n, int32_t k, float extent,
                            float repulse_extent, float* out2, void* scratch, void* stream);

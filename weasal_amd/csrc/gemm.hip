@@ -1024,9 +1024,13 @@ int64_t colsum_chunk(int64_t m)
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // chunk sums -> out: the wide form for large outputs of few chunks, the grouped form otherwise
+bool reduce_partials_wide(const void* partial, int64_t elems, int chunks, const void* out, int n, int64_t ldo)
+{
+    return elems >= 65536 && chunks <= 64 && elems % 4 == 0 && al16(partial) && al16(out) && (ldo <= n || (n % 4 == 0 && ldo % 4 == 0));
+}
 void launch_reduce_partials(const float* partial, int64_t elems, int chunks, float* out, hipStream_t st, int n = 0, int64_t ldo = 0)
 {
-    if (elems >= 65536 && chunks <= 64 && elems % 4 == 0 && al16(partial) && al16(out) && (ldo <= n || (n % 4 == 0 && ldo % 4 == 0)))
+    if (reduce_partials_wide(partial, elems, chunks, out, n, ldo))
         reduce_partials_wide_kernel<<<(unsigned)ws_ceil_div(elems, 1024), 256, 0, st>>>(partial, elems, chunks, out, n, ldo);
     else
         reduce_partials_kernel<<<(unsigned)ws_ceil_div(elems, 32), 256, 0, st>>>(partial, elems, chunks, out, n, ldo);
@@ -1073,6 +1077,77 @@ int64_t ws_gemm_xb_scratch_bytes(int64_t m, int32_t k, int32_t n)
     return 16 * m * (int64_t)n * (int64_t)sizeof(float);
 }
 
+// The launch a product takes: every selection rule of gemm_xb_impl, shared with the reporter ws_gemm_xb_variant (which
+// only reads the pointers' alignment).
+enum { XB_NONE = 0, XB_XB2 = 1, XB_SHALLOW = 2, XB_GENERIC = 3 };
+struct XbPlan {
+    int kind;
+    int nt, wn;             // XB_XB2: gemm_xb2_kernel<nt, wn>; XB_GENERIC: gemm_xb_kernel<nt, 32>
+    dim3 grid;
+    int splits, csplit;     // XB_XB2: split-K layers (splits > 1: sums in scratch, then splitk_epilogue_kernel), chunks per layer
+    int staged;             // XB_XB2: ws_gemm_staged
+    int vecx, vecb;         // XB_GENERIC: float4 loads of x / b
+    int rows;               // XB_SHALLOW: rows per workgroup
+    size_t lds;             // XB_SHALLOW: dynamic LDS bytes
+};
+
+static int xb_plan(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n, const float* bias,
+                   const float* residual, int64_t ldr, const float* y, int64_t ldy, const void* scratch, int64_t scratch_bytes,
+                   int64_t brs, int64_t bcs, const XbGate& gate, XbPlan& p)
+{
+    p = XbPlan{};
+    if (m == 0) return WS_OK;
+    const int vecx = al16(x) && (ldx % 4 == 0);
+    const int vecb = al16(b) && (n % 4 == 0);
+    const int64_t gx = ws_ceil_div(m, BM);
+    WS_REQUIRE(gx < (1ll << 31), "m too large");
+    if (vecx && k % 32 == 0 && n % 4 == 0 && al16(y) && ldy % 4 == 0 &&
+        (!residual || (al16(residual) && ldr % 4 == 0)) && (!bias || al16(bias)) &&
+        (int64_t)(k - 1) * brs + (int64_t)(n - 1) * bcs < (1ll << 29) && 128 * ldx < (1ll << 29) && al16(b) &&
+        (bcs == 1 ? true : (brs == 1 && bcs % 4 == 0)) &&
+        (!gate.y || (al16(gate.y) && gate.ld % 4 == 0)) && (!gate.mask || ((reinterpret_cast<uintptr_t>(gate.mask) & 3u) == 0 && gate.ldm % 4 == 0))) {
+        const int64_t tiles = ws_ceil_div(m, 32);
+        int wn = tiles >= 2048 ? 1 : 2;
+        if (n <= 32) wn = 1;
+        const int nt = wn == 1 ? (n <= 32 ? 1 : (n <= 64 || k <= THIN_K) ? 2 : 4) : (n <= 64 ? 1 : 2);
+        const unsigned gx2 = (unsigned)ws_ceil_div(m, 32 * (4 / wn)), gy2 = (unsigned)ws_ceil_div(n, 32 * nt * wn);
+        const int nch = k / 32;
+        int splits = 1;
+        if (scratch && (int64_t)gx2 * gy2 < 256 && nch >= 16) {
+            splits = (int)ws_ceil_div(768, (int64_t)gx2 * gy2);
+            if (splits > nch / 8) splits = nch / 8;
+            if (splits > 16) splits = 16;
+            if ((int64_t)splits * m * n * 4 > scratch_bytes) splits = (int)(scratch_bytes / (m * n * 4));
+            if (splits < 2) splits = 1;
+        }
+        const int csplit = (int)ws_ceil_div(nch, splits);
+        splits = (int)ws_ceil_div(nch, csplit);
+        p.kind = XB_XB2; p.nt = nt; p.wn = wn; p.grid = dim3(gx2, gy2, (unsigned)splits);
+        p.splits = splits; p.csplit = csplit; p.staged = ws_gemm_staged;
+        return WS_OK;
+    }
+    WS_REQUIRE(bcs == 1 && brs == n, "a strided small matrix needs k %% 32 == 0, n %% 4 == 0 and 16-byte aligned rows "
+                                     "(k=%d n=%d): pass a row-major [K,N] copy for this shape", k, n);
+    if (ws_gemm_shallow && k <= 64 && n % 4 == 0 && n <= 1024 && (int64_t)k * n <= 8192 && m >= 4096 && al16(b) && al16(y) && ldy % 4 == 0 &&
+        (!residual || (al16(residual) && ldr % 4 == 0)) && (!bias || al16(bias)) && (!gate.y || (al16(gate.y) && gate.ld % 4 == 0)) &&
+        (!gate.mask || ((reinterpret_cast<uintptr_t>(gate.mask) & 3u) == 0 && gate.ldm % 4 == 0))) {
+        // shallow, ragged contraction over many rows: the streaming VALU form (gemm_xb_shallow_kernel)
+        const int per = 256 / (n / 4);
+        const int kp = (k + 3) & ~3;
+        p.kind = XB_SHALLOW;
+        p.rows = per * 8;                                               // 8 row passes per workgroup
+        p.grid = dim3((unsigned)ws_ceil_div(m, p.rows));
+        p.lds = sizeof(float) * ((size_t)kp * n + (size_t)p.rows * kp);
+        return WS_OK;
+    }
+    p.kind = XB_GENERIC; p.vecx = vecx; p.vecb = vecb;
+    // measured (tools/gemm_bench.py, M = 400k): for n > 64, shallow K is latency bound and prefers the 64-column
+    // tile (more waves per SIMD, L2 serves the X re-read); deep K prefers the 128-column tile (X reuse)
+    p.nt = n <= 32 ? 1 : (n <= 64 || k < 128) ? 2 : 4;
+    p.grid = dim3((unsigned)gx, n <= 64 ? 1u : (unsigned)ws_ceil_div(n, 32 * p.nt));
+    return WS_OK;
+}
+
 static int gemm_xb_impl(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n,
                         const float* bias, const float* residual, int64_t ldr, int32_t act, float slope,
                         float* y, int64_t ldy, void* scratch, int64_t scratch_bytes, void* stream,
@@ -1085,80 +1160,35 @@ static int gemm_xb_impl(const float* x, int64_t m, int32_t k, int64_t ldx, const
     if (m == 0) return WS_OK;
     WS_REQUIRE(x && b && y, "NULL argument");
     hipStream_t st = (hipStream_t)stream;
-    const int vecx = al16(x) && (ldx % 4 == 0);
-    const int vecb = al16(b) && (n % 4 == 0);
-    const int64_t gx = ws_ceil_div(m, BM);
-    WS_REQUIRE(gx < (1ll << 31), "m too large");
-    if (vecx && k % 32 == 0 && n % 4 == 0 && al16(y) && ldy % 4 == 0 &&
-        (!residual || (al16(residual) && ldr % 4 == 0)) && (!bias || al16(bias)) &&
-        (int64_t)(k - 1) * brs + (int64_t)(n - 1) * bcs < (1ll << 29) && 128 * ldx < (1ll << 29) && al16(b) &&
-        (bcs == 1 ? true : (brs == 1 && bcs % 4 == 0)) &&
-        (!gate.y || (al16(gate.y) && gate.ld % 4 == 0)) && (!gate.mask || ((reinterpret_cast<uintptr_t>(gate.mask) & 3u) == 0 && gate.ldm % 4 == 0))) {
-#define WS_XB2(NTV, WNV)                                                                                        \
-    do {                                                                                                        \
-        const unsigned gx2 = (unsigned)ws_ceil_div(m, 32 * (4 / WNV)), gy2 = (unsigned)ws_ceil_div(n, 32 * NTV * WNV); \
-        const int nch = k / 32;                                                                                 \
-        int splits = 1;                                                                                         \
-        if (scratch && (int64_t)gx2 * gy2 < 256 && nch >= 16) {                                                 \
-            splits = (int)ws_ceil_div(768, (int64_t)gx2 * gy2);                                                 \
-            if (splits > nch / 8) splits = nch / 8;                                                             \
-            if (splits > 16) splits = 16;                                                                       \
-            if ((int64_t)splits * m * n * 4 > scratch_bytes) splits = (int)(scratch_bytes / (m * n * 4));       \
-            if (splits < 2) splits = 1;                                                                         \
-        }                                                                                                       \
-        const int csplit = (int)ws_ceil_div(nch, splits);                                                       \
-        splits = (int)ws_ceil_div(nch, csplit);                                                                 \
-        float* part = splits > 1 ? (float*)scratch : nullptr;                                                   \
-        gemm_xb2_kernel<NTV, WNV><<<dim3(gx2, gy2, (unsigned)splits), 256, 0, st>>>(x, m, k, ldx, b, n, (int)brs, (int)bcs, y, ldy, bias, residual, \
-                                                                                    ldr, act, slope, csplit, part, gate, ws_gemm_staged);   \
-        if (splits > 1)                                                                                         \
-            splitk_epilogue_kernel<<<ws_grid(m * (n / 4), 256), 256, 0, st>>>(part, splits, m, n, y, ldy, bias, residual, ldr, \
-                                                                              act, slope, gate);                \
-    } while (0)
-        const int64_t tiles = ws_ceil_div(m, 32);
-        int wn = tiles >= 2048 ? 1 : 2;
-        if (n <= 32) wn = 1;
-        if (wn == 1) {
-            if (n <= 32) WS_XB2(1, 1);
-            else if (n <= 64 || k <= THIN_K) WS_XB2(2, 1);
+    XbPlan p;
+    const int rc = xb_plan(x, m, k, ldx, b, n, bias, residual, ldr, y, ldy, scratch, scratch_bytes, brs, bcs, gate, p);
+    if (rc != WS_OK) return rc;
+    if (p.kind == XB_XB2) {
+        float* part = p.splits > 1 ? (float*)scratch : nullptr;
+#define WS_XB2(NTV, WNV)                                                                                                   \
+    gemm_xb2_kernel<NTV, WNV><<<p.grid, 256, 0, st>>>(x, m, k, ldx, b, n, (int)brs, (int)bcs, y, ldy, bias, residual, ldr, act, \
+                                                      slope, p.csplit, part, gate, p.staged)
+        if (p.wn == 1) {
+            if (p.nt == 1) WS_XB2(1, 1);
+            else if (p.nt == 2) WS_XB2(2, 1);
             else WS_XB2(4, 1);
         } else {
-            if (n <= 64) WS_XB2(1, 2);
+            if (p.nt == 1) WS_XB2(1, 2);
             else WS_XB2(2, 2);
         }
 #undef WS_XB2
-        WS_LAUNCH_CHECK();
-        return WS_OK;
-    }
-    WS_REQUIRE(bcs == 1 && brs == n, "a strided small matrix needs k %% 32 == 0, n %% 4 == 0 and 16-byte aligned rows "
-                                     "(k=%d n=%d): pass a row-major [K,N] copy for this shape", k, n);
-    if (ws_gemm_shallow && k <= 64 && n % 4 == 0 && n <= 1024 && (int64_t)k * n <= 8192 && m >= 4096 && al16(b) && al16(y) && ldy % 4 == 0 &&
-        (!residual || (al16(residual) && ldr % 4 == 0)) && (!bias || al16(bias)) && (!gate.y || (al16(gate.y) && gate.ld % 4 == 0)) &&
-        (!gate.mask || ((reinterpret_cast<uintptr_t>(gate.mask) & 3u) == 0 && gate.ldm % 4 == 0))) {
-        // shallow, ragged contraction over many rows: the streaming VALU form (gemm_xb_shallow_kernel)
-        const int per = 256 / (n / 4);
-        const int kp = (k + 3) & ~3;
-        int rows = per * 8;                                             // 8 row passes per workgroup
-        gemm_xb_shallow_kernel<<<(unsigned)ws_ceil_div(m, rows), 256, sizeof(float) * ((size_t)kp * n + (size_t)rows * kp), st>>>(
-            x, m, k, ldx, b, n, y, ldy, bias, residual, ldr, act, slope, gate, rows);
-        WS_LAUNCH_CHECK();
-        return WS_OK;
-    }
-    if (n <= 32) {
-        gemm_xb_kernel<1, 32><<<dim3((unsigned)gx, 1), 256, 0, st>>>(x, m, k, ldx, b, n, n, y, ldy, vecx, vecb, bias, residual, ldr,
-                                                                 act, slope, gate);
-    } else if (n <= 64) {
-        gemm_xb_kernel<2, 32><<<dim3((unsigned)gx, 1), 256, 0, st>>>(x, m, k, ldx, b, n, n, y, ldy, vecx, vecb, bias, residual, ldr,
-                                                                 act, slope, gate);
+        if (p.splits > 1)
+            splitk_epilogue_kernel<<<ws_grid(m * (n / 4), 256), 256, 0, st>>>(part, p.splits, m, n, y, ldy, bias, residual, ldr,
+                                                                              act, slope, gate);
+    } else if (p.kind == XB_SHALLOW) {
+        gemm_xb_shallow_kernel<<<p.grid, 256, p.lds, st>>>(x, m, k, ldx, b, n, y, ldy, bias, residual, ldr, act, slope, gate, p.rows);
     } else {
-        // measured (tools/gemm_bench.py, M = 400k): shallow K is latency bound and prefers the 64-column
-        // tile (more waves per SIMD, L2 serves the X re-read); deep K prefers the 128-column tile (X reuse)
-        if (k < 128)
-            gemm_xb_kernel<2, 32><<<dim3((unsigned)gx, (unsigned)ws_ceil_div(n, 64)), 256, 0, st>>>(
-                x, m, k, ldx, b, n, n, y, ldy, vecx, vecb, bias, residual, ldr, act, slope, gate);
-        else
-            gemm_xb_kernel<4, 32><<<dim3((unsigned)gx, (unsigned)ws_ceil_div(n, 128)), 256, 0, st>>>(
-                x, m, k, ldx, b, n, n, y, ldy, vecx, vecb, bias, residual, ldr, act, slope, gate);
+#define WS_XB(NTV)                                                                                                         \
+    gemm_xb_kernel<NTV, 32><<<p.grid, 256, 0, st>>>(x, m, k, ldx, b, n, n, y, ldy, p.vecx, p.vecb, bias, residual, ldr, act, slope, gate)
+        if (p.nt == 1) WS_XB(1);
+        else if (p.nt == 2) WS_XB(2);
+        else WS_XB(4);
+#undef WS_XB
     }
     WS_LAUNCH_CHECK();
     return WS_OK;
@@ -1167,6 +1197,30 @@ static int gemm_xb_impl(const float* x, int64_t m, int32_t k, int64_t ldx, const
 int64_t ws_act_bwd_colsum_scratch_bytes(int64_t m, int32_t n)
 {
     return ws_ceil_div(m > 0 ? m : 1, colsum_chunk(m)) * (int64_t)n * (int64_t)sizeof(float);
+}
+
+// The launches of act_bwd_colsum_impl (m > 0), shared with the reporter ws_act_bwd_colsum_variant
+struct ColsumPlan {
+    int v;                  // act_bwd_colsum_kernel<v>: 4 = float4 columns, 1 = any n
+    int64_t chunk;
+    int chunks;
+    float* partial;         // NULL (no column sums), colsum itself (one chunk) or the scratch
+    int reduce;             // 1: reduce_partials_kernel adds the chunks
+    dim3 grid;
+};
+
+static ColsumPlan colsum_plan(const void* dy, int64_t m, int32_t n, int64_t lddy, const void* y, int64_t ldy, const void* dz,
+                              int64_t lddz, float* colsum, void* scratch)
+{
+    ColsumPlan p{};
+    p.chunk = colsum_chunk(m);
+    p.chunks = (int)ws_ceil_div(m, p.chunk);
+    p.partial = colsum ? (p.chunks == 1 ? colsum : (float*)scratch) : nullptr;
+    p.reduce = colsum && p.chunks > 1;
+    const bool vec = n % 4 == 0 && al16(dy) && lddy % 4 == 0 && (!y || (al16(y) && ldy % 4 == 0 && al16(dz) && lddz % 4 == 0));
+    p.v = vec ? 4 : 1;
+    p.grid = dim3(p.chunks, (unsigned)ws_ceil_div(ws_ceil_div(n, p.v), 256));
+    return p;
 }
 
 static int act_bwd_colsum_impl(const float* dy, int64_t m, int32_t n, int64_t lddy, const float* y, int64_t ldy, float slope,
@@ -1198,19 +1252,14 @@ static int act_bwd_colsum_impl(const float* dy, int64_t m, int32_t n, int64_t ld
         return WS_OK;
     }
     WS_REQUIRE(dy && (y || colsum), "NULL argument");
-    const int64_t chunk = colsum_chunk(m);
-    const int chunks = (int)ws_ceil_div(m, chunk);
-    float* partial = colsum ? (chunks == 1 ? colsum : (float*)scratch) : nullptr;
-    const bool vec = n % 4 == 0 && al16(dy) && lddy % 4 == 0 && (!y || (al16(y) && ldy % 4 == 0 && al16(dz) && lddz % 4 == 0));
-    if (vec)
-        act_bwd_colsum_kernel<4><<<dim3(chunks, (unsigned)ws_ceil_div(ws_ceil_div(n, 4), 256)), 256, 0, st>>>(
-            dy, y, m, n, lddy, ldy, slope, dz, lddz, partial, chunk, drop);
+    const ColsumPlan p = colsum_plan(dy, m, n, lddy, y, ldy, dz, lddz, colsum, scratch);
+    if (p.v == 4)
+        act_bwd_colsum_kernel<4><<<p.grid, 256, 0, st>>>(dy, y, m, n, lddy, ldy, slope, dz, lddz, p.partial, p.chunk, drop);
     else
-        act_bwd_colsum_kernel<1><<<dim3(chunks, (unsigned)ws_ceil_div(n, 256)), 256, 0, st>>>(dy, y, m, n, lddy, ldy, slope, dz, lddz,
-                                                                                              partial, chunk, drop);
+        act_bwd_colsum_kernel<1><<<p.grid, 256, 0, st>>>(dy, y, m, n, lddy, ldy, slope, dz, lddz, p.partial, p.chunk, drop);
     WS_LAUNCH_CHECK();
-    if (colsum && chunks > 1) {
-        reduce_partials_kernel<<<(unsigned)ws_ceil_div(n, 32), 256, 0, st>>>(partial, n, chunks, colsum);
+    if (p.reduce) {
+        reduce_partials_kernel<<<(unsigned)ws_ceil_div(n, 32), 256, 0, st>>>(p.partial, n, p.chunks, colsum);
         WS_LAUNCH_CHECK();
     }
     return WS_OK;
@@ -1302,8 +1351,9 @@ int ws_gemm_xb(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b
 
 int64_t ws_gemm_xty_scratch_bytes(int64_t m, int32_t k, int32_t n)
 {
-    const int64_t chunk = xty_chunk(m, k, n);
-    return ws_ceil_div(m > 0 ? m : 1, chunk) * (int64_t)k * n * (int64_t)sizeof(float);
+    // (xty_chunk(0, ..) is 0: size an empty operand as one row, like ws_act_bwd_colsum_scratch_bytes)
+    const int64_t rows = m > 0 ? m : 1;
+    return ws_ceil_div(rows, xty_chunk(rows, k, n)) * (int64_t)k * n * (int64_t)sizeof(float);
 }
 
 static int gemm_xty_core(const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy,
@@ -1313,6 +1363,55 @@ int ws_gemm_xty(const float* x, int64_t m, int32_t k, int64_t ldx, const float* 
                 float* out, void* scratch, void* stream)
 {
     return gemm_xty_core(x, m, k, ldx, y, n, ldy, out, scratch, stream);
+}
+
+// The launches of a dW reduction: every selection rule of gemm_xty_core / ws_gemm_xty_bf16, shared with the reporter
+// ws_gemm_xty_variant (which only reads the pointers' alignment).  bf16: 2-byte operands (no gemm_xty_kernel fallback).
+struct XtyPlan {
+    int lds;                // 0: gemm_xty2_kernel<kt, nt, wk, wn>; 1: gemm_xty_kernel<nt, kt> (32-bit buffer offsets overflow)
+    int kt, nt, wk, wn;
+    int vecx, vecy;         // gemm_xty_kernel: float4 loads
+    int64_t chunk;
+    int chunks;
+    float* partial;         // out itself (one chunk, flat) or the scratch
+    int reduce;             // 0: none, 1: reduce_partials_kernel, 2: reduce_partials_wide_kernel
+    bool pitched;
+    dim3 grid;
+};
+
+static int xty_plan(const void* x, int64_t m, int32_t k, int64_t ldx, const void* y, int32_t n, int64_t ldy, float* out, void* scratch,
+                    int64_t ldo, bool bf16, XtyPlan& p)
+{
+    p = XtyPlan{};
+    p.pitched = ldo > n;
+    if (m == 0) return WS_OK;
+    p.chunk = xty_chunk(m, k, n);
+    p.chunks = (int)ws_ceil_div(m, p.chunk);
+    const int64_t span = p.chunk * (ldx > ldy ? ldx : ldy);
+    if (bf16) WS_REQUIRE(span * 2 < (1ll << 31), "operand exceeds the 32-bit buffer offsets");
+    p.partial = (p.chunks == 1 && !p.pitched) ? out : (float*)scratch;
+    p.lds = !bf16 && span * 4 >= (1ll << 31);
+    if (!p.lds) {
+        // per-wave tile (32 KT) x (32 NT); waves WK x WN over the output, the rest split the rows
+        const bool a2x = bf16 ? (reinterpret_cast<uintptr_t>(x) & 3u) == 0 && ldx % 2 == 0 && k % 2 == 0
+                              : (reinterpret_cast<uintptr_t>(x) & 7u) == 0 && ldx % 2 == 0;
+        const bool a2y = bf16 ? (reinterpret_cast<uintptr_t>(y) & 3u) == 0 && ldy % 2 == 0 && n % 2 == 0
+                              : (reinterpret_cast<uintptr_t>(y) & 7u) == 0 && ldy % 2 == 0;
+        p.kt = (k > 32 && a2x) ? 2 : 1;
+        p.nt = (n > 32 && a2y) ? 2 : 1;
+        p.wk = k > 32 * p.kt ? 2 : 1;
+        p.wn = (n > 32 * p.nt && p.wk == 1) || (n > 32 * p.nt && k > 32 * p.kt) ? 2 : 1;
+        p.grid = dim3(p.chunks, (unsigned)ws_ceil_div(k, 32 * p.kt * p.wk), (unsigned)ws_ceil_div(n, 32 * p.nt * p.wn));
+    } else {
+        p.vecx = al16(x) && (ldx % 4 == 0);
+        p.vecy = al16(y) && (ldy % 4 == 0);
+        p.kt = k <= 32 ? 1 : (k <= 64 ? 2 : 4);
+        p.nt = n <= 32 ? 1 : (n <= 64 ? 2 : 4);
+        p.grid = dim3(p.chunks, (unsigned)ws_ceil_div(k, 32 * p.kt), (unsigned)ws_ceil_div(n, 32 * p.nt));
+    }
+    if (p.chunks > 1 || p.pitched)
+        p.reduce = reduce_partials_wide(p.partial, (int64_t)k * n, p.chunks, out, n, p.pitched ? ldo : 0) ? 2 : 1;
+    return WS_OK;
 }
 
 static int gemm_xty_core(const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy,
@@ -1330,56 +1429,42 @@ static int gemm_xty_core(const float* x, int64_t m, int32_t k, int64_t ldx, cons
         return WS_OK;
     }
     WS_REQUIRE(x && y && scratch, "NULL argument");
-    const int64_t chunk = xty_chunk(m, k, n);
-    const int chunks = (int)ws_ceil_div(m, chunk);
-    const int vecx = al16(x) && (ldx % 4 == 0);
-    const int vecy = al16(y) && (ldy % 4 == 0);
-    float* partial = (chunks == 1 && !pitched) ? out : (float*)scratch;
-    const bool al8x = (reinterpret_cast<uintptr_t>(x) & 7u) == 0 && ldx % 2 == 0;
-    const bool al8y = (reinterpret_cast<uintptr_t>(y) & 7u) == 0 && ldy % 2 == 0;
-    if (chunk * (ldx > ldy ? ldx : ldy) * 4 < (1ll << 31)) {
-        // per-wave tile (32 KT) x (32 NT); waves WK x WN over the output, the rest split the rows
-        const int kt = (k > 32 && al8x) ? 2 : 1, nt = (n > 32 && al8y) ? 2 : 1;
-        const int wk = k > 32 * kt ? 2 : 1;
-        const int wn = (n > 32 * nt && wk == 1) || (n > 32 * nt && k > 32 * kt) ? 2 : 1;
-#define WS_XTY2(KTV, NTV, WKV, WNV)                                                                                   \
-    do {                                                                                                              \
-        const dim3 g3(chunks, (unsigned)ws_ceil_div(k, 32 * KTV * WKV), (unsigned)ws_ceil_div(n, 32 * NTV * WNV));    \
-        gemm_xty2_kernel<KTV, NTV, WKV, WNV><<<g3, 256, 0, st>>>(x, m, k, ldx, y, n, ldy, partial, chunk);            \
-    } while (0)
+    XtyPlan p;
+    const int rc = xty_plan(x, m, k, ldx, y, n, ldy, out, scratch, ldo, false, p);
+    if (rc != WS_OK) return rc;
+    if (!p.lds) {
+#define WS_XTY2(KTV, NTV, WKV, WNV) gemm_xty2_kernel<KTV, NTV, WKV, WNV><<<p.grid, 256, 0, st>>>(x, m, k, ldx, y, n, ldy, p.partial, p.chunk)
 #define WS_XTY2_W(KTV, NTV)                          \
     do {                                             \
-        if (wk == 2 && wn == 2) WS_XTY2(KTV, NTV, 2, 2); \
-        else if (wk == 2) WS_XTY2(KTV, NTV, 2, 1);   \
-        else if (wn == 2) WS_XTY2(KTV, NTV, 1, 2);   \
+        if (p.wk == 2 && p.wn == 2) WS_XTY2(KTV, NTV, 2, 2); \
+        else if (p.wk == 2) WS_XTY2(KTV, NTV, 2, 1);   \
+        else if (p.wn == 2) WS_XTY2(KTV, NTV, 1, 2);   \
         else WS_XTY2(KTV, NTV, 1, 1);                \
     } while (0)
-        if (kt == 2 && nt == 2) WS_XTY2_W(2, 2);
-        else if (kt == 2) WS_XTY2_W(2, 1);
-        else if (nt == 2) WS_XTY2_W(1, 2);
+        if (p.kt == 2 && p.nt == 2) WS_XTY2_W(2, 2);
+        else if (p.kt == 2) WS_XTY2_W(2, 1);
+        else if (p.nt == 2) WS_XTY2_W(1, 2);
         else WS_XTY2_W(1, 1);
 #undef WS_XTY2_W
 #undef WS_XTY2
     } else {
-#define WS_XTY(NTV, KTV)                                                                                              \
-    gemm_xty_kernel<NTV, KTV><<<dim3(chunks, (unsigned)ws_ceil_div(k, 32 * KTV), (unsigned)ws_ceil_div(n, 32 * NTV)), 256, 0, \
-                                st>>>(x, m, k, ldx, y, n, ldy, partial, chunk, vecx, vecy)
+#define WS_XTY(NTV, KTV) gemm_xty_kernel<NTV, KTV><<<p.grid, 256, 0, st>>>(x, m, k, ldx, y, n, ldy, p.partial, p.chunk, p.vecx, p.vecy)
 #define WS_XTY_K(NTV)                    \
     do {                                 \
-        if (k <= 32) WS_XTY(NTV, 1);     \
-        else if (k <= 64) WS_XTY(NTV, 2); \
+        if (p.kt == 1) WS_XTY(NTV, 1);     \
+        else if (p.kt == 2) WS_XTY(NTV, 2); \
         else WS_XTY(NTV, 4);             \
     } while (0)
-        if (n <= 32) WS_XTY_K(1);
-        else if (n <= 64) WS_XTY_K(2);
+        if (p.nt == 1) WS_XTY_K(1);
+        else if (p.nt == 2) WS_XTY_K(2);
         else WS_XTY_K(4);
 #undef WS_XTY_K
 #undef WS_XTY
     }
     WS_LAUNCH_CHECK();
-    if (chunks > 1 || pitched) {
+    if (p.reduce) {
         const int64_t elems = (int64_t)k * n;
-        launch_reduce_partials(partial, elems, chunks, out, st, n, pitched ? ldo : 0);
+        launch_reduce_partials(p.partial, elems, p.chunks, out, st, n, pitched ? ldo : 0);
         WS_LAUNCH_CHECK();
     }
     return WS_OK;
@@ -1407,41 +1492,108 @@ int ws_gemm_xty_bf16(const uint16_t* x, int64_t m, int32_t k, int64_t ldx, const
         return WS_OK;
     }
     WS_REQUIRE(x && y && scratch, "NULL argument");
-    const int64_t chunk = xty_chunk(m, k, n);
-    const int chunks = (int)ws_ceil_div(m, chunk);
-    WS_REQUIRE(chunk * (ldx > ldy ? ldx : ldy) * 2 < (1ll << 31), "operand exceeds the 32-bit buffer offsets");
-    float* partial = chunks == 1 ? out : (float*)scratch;
+    XtyPlan p;
+    const int rc = xty_plan(x, m, k, ldx, y, n, ldy, out, scratch, 0, true, p);
+    if (rc != WS_OK) return rc;
     const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
     const bf16_t* yb = reinterpret_cast<const bf16_t*>(y);
-    const bool al4x = (reinterpret_cast<uintptr_t>(x) & 3u) == 0 && ldx % 2 == 0 && k % 2 == 0;
-    const bool al4y = (reinterpret_cast<uintptr_t>(y) & 3u) == 0 && ldy % 2 == 0 && n % 2 == 0;
-    const int kt = (k > 32 && al4x) ? 2 : 1, nt = (n > 32 && al4y) ? 2 : 1;
-    const int wk = k > 32 * kt ? 2 : 1;
-    const int wn = (n > 32 * nt && wk == 1) || (n > 32 * nt && k > 32 * kt) ? 2 : 1;
-#define WS_XTY2B(KTV, NTV, WKV, WNV)                                                                                  \
-    gemm_xty2_kernel<KTV, NTV, WKV, WNV, bf16_t><<<dim3(chunks, (unsigned)ws_ceil_div(k, 32 * KTV * WKV),             \
-                                                        (unsigned)ws_ceil_div(n, 32 * NTV * WNV)), 256, 0, st>>>(     \
-        xb, m, k, ldx, yb, n, ldy, partial, chunk)
+#define WS_XTY2B(KTV, NTV, WKV, WNV) gemm_xty2_kernel<KTV, NTV, WKV, WNV, bf16_t><<<p.grid, 256, 0, st>>>(xb, m, k, ldx, yb, n, ldy, p.partial, p.chunk)
 #define WS_XTY2B_W(KTV, NTV)                          \
     do {                                              \
-        if (wk == 2 && wn == 2) WS_XTY2B(KTV, NTV, 2, 2); \
-        else if (wk == 2) WS_XTY2B(KTV, NTV, 2, 1);   \
-        else if (wn == 2) WS_XTY2B(KTV, NTV, 1, 2);   \
+        if (p.wk == 2 && p.wn == 2) WS_XTY2B(KTV, NTV, 2, 2); \
+        else if (p.wk == 2) WS_XTY2B(KTV, NTV, 2, 1);   \
+        else if (p.wn == 2) WS_XTY2B(KTV, NTV, 1, 2);   \
         else WS_XTY2B(KTV, NTV, 1, 1);                \
     } while (0)
-    if (kt == 2 && nt == 2) WS_XTY2B_W(2, 2);
-    else if (kt == 2) WS_XTY2B_W(2, 1);
-    else if (nt == 2) WS_XTY2B_W(1, 2);
+    if (p.kt == 2 && p.nt == 2) WS_XTY2B_W(2, 2);
+    else if (p.kt == 2) WS_XTY2B_W(2, 1);
+    else if (p.nt == 2) WS_XTY2B_W(1, 2);
     else WS_XTY2B_W(1, 1);
 #undef WS_XTY2B_W
 #undef WS_XTY2B
     WS_LAUNCH_CHECK();
-    if (chunks > 1) {
+    if (p.reduce) {
         const int64_t elems = (int64_t)k * n;
-        launch_reduce_partials(partial, elems, chunks, out, st);
+        launch_reduce_partials(p.partial, elems, p.chunks, out, st);
         WS_LAUNCH_CHECK();
     }
     return WS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Reporters: the launches the entries above make for these arguments (the same plan functions; pointers are only
+// tested for alignment, nothing is read or launched).  Form: "kernel<template arguments> key=value ...".
+// ---------------------------------------------------------------------------------------------
+static const char* reduce_name(int r)
+{
+    return r == 2 ? "reduce_partials_wide_kernel" : (r == 1 ? "reduce_partials_kernel" : "none");
+}
+
+// ws_gemm_xb* / ws_priv_gemm_xb_ex: b_row_stride < 0 = row-major [K, N] (the non-strided entries); gate_y / mask as in
+// ws_gemm_xb_gated_strided (dropout and the gathered residual do not change the launch)
+int ws_gemm_xb_variant(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int64_t b_row_stride, int64_t b_col_stride,
+                       int32_t n, const float* bias, const float* residual, int64_t ldr, const float* gate_y, int64_t ldg,
+                       const uint8_t* mask, int64_t ldm, const float* y, int64_t ldy, const void* scratch, int64_t scratch_bytes,
+                       char* out, int32_t cap)
+{
+    WS_REQUIRE(out && cap > 0, "bad argument");
+    WS_REQUIRE(m >= 0 && k >= 1 && n >= 1 && ldx >= k && ldy >= n, "bad sizes m=%lld k=%d n=%d", (long long)m, k, n);
+    const int64_t brs = b_row_stride < 0 ? n : b_row_stride;
+    XbGate gate{};
+    gate.y = gate_y; gate.ld = ldg; gate.mask = mask; gate.ldm = ldm;
+    XbPlan p;
+    const int rc = xb_plan(x, m, k, ldx, b, n, bias, residual, ldr, y, ldy, scratch, scratch_bytes, brs, b_col_stride, gate, p);
+    if (rc != WS_OK) return rc;
+    if (p.kind == XB_NONE)
+        snprintf(out, (size_t)cap, "none (m == 0)");
+    else if (p.kind == XB_XB2)
+        snprintf(out, (size_t)cap, "gemm_xb2_kernel<NT=%d, WN=%d> b=%s epilogue=%s splits=%d csplit=%d%s", p.nt, p.wn,
+                 brs == 1 ? "transposed" : "rows", p.staged ? "staged" : "lanes", p.splits, p.csplit,
+                 p.splits > 1 ? " + splitk_epilogue_kernel" : "");
+    else if (p.kind == XB_SHALLOW)
+        snprintf(out, (size_t)cap, "gemm_xb_shallow_kernel rows=%d", p.rows);
+    else
+        snprintf(out, (size_t)cap, "gemm_xb_kernel<NT=%d, BKX=32> vecx=%d vecb=%d", p.nt, p.vecx, p.vecb);
+    return WS_OK;
+}
+
+// ws_gemm_xty (ldo = 0), ws_priv_gemm_xty_pitched (ldo >= n) and, rows_bf16 = 1, ws_gemm_xty_bf16 (uint16_t rows, ldo = 0)
+int ws_gemm_xty_variant(const void* x, int64_t m, int32_t k, int64_t ldx, const void* y, int32_t n, int64_t ldy, float* out_m,
+                        int64_t ldo, void* scratch, int32_t rows_bf16, char* out, int32_t cap)
+{
+    WS_REQUIRE(out && cap > 0, "bad argument");
+    WS_REQUIRE(m >= 0 && k >= 1 && n >= 1 && ldx >= k && ldy >= n, "bad sizes m=%lld k=%d n=%d", (long long)m, k, n);
+    WS_REQUIRE(!rows_bf16 || ldo == 0, "the bf16 reduction has no pitched form");
+    XtyPlan p;
+    const int rc = xty_plan(x, m, k, ldx, y, n, ldy, out_m, scratch, ldo, rows_bf16 != 0, p);
+    if (rc != WS_OK) return rc;
+    const char* form = p.pitched ? "pitched" : "flat";
+    if (m == 0)
+        snprintf(out, (size_t)cap, "memset (m == 0) out=%s", form);
+    else if (!p.lds)
+        snprintf(out, (size_t)cap, "gemm_xty2_kernel<KT=%d, NT=%d, WK=%d, WN=%d, TI=%s> chunk=%lld chunks=%d reduce=%s out=%s", p.kt, p.nt,
+                 p.wk, p.wn, rows_bf16 ? "bf16" : "float", (long long)p.chunk, p.chunks, reduce_name(p.reduce), form);
+    else
+        snprintf(out, (size_t)cap, "gemm_xty_kernel<NT=%d, KT=%d> vecx=%d vecy=%d chunk=%lld chunks=%d reduce=%s out=%s", p.nt, p.kt,
+                 p.vecx, p.vecy, (long long)p.chunk, p.chunks, reduce_name(p.reduce), form);
+    return WS_OK;
+}
+
+// ws_act_bwd_colsum / ws_act_bwd_colsum_dropout (the dropout form launches the same kernels)
+int ws_act_bwd_colsum_variant(const float* dy, int64_t m, int32_t n, int64_t lddy, const float* y, int64_t ldy, const float* dz,
+                              int64_t lddz, float* colsum, void* scratch, char* out, int32_t cap)
+{
+    WS_REQUIRE(out && cap > 0, "bad argument");
+    WS_REQUIRE(m >= 0 && n >= 1 && lddy >= n, "bad sizes m=%lld n=%d", (long long)m, n);
+    if (m == 0) {
+        snprintf(out, (size_t)cap, "%s (m == 0)", colsum ? "memset" : "none");
+        return WS_OK;
+    }
+    const ColsumPlan p = colsum_plan(dy, m, n, lddy, y, ldy, dz, lddz, colsum, scratch);
+    snprintf(out, (size_t)cap, "act_bwd_colsum_kernel<V=%d> chunk=%lld chunks=%d reduce=%s", p.v, (long long)p.chunk, p.chunks,
+             reduce_name(p.reduce));
+    return WS_OK;
+}
+
 }  // extern "C"
+

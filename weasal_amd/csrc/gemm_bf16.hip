@@ -264,6 +264,31 @@ int64_t colsum_chunk_bf(int64_t m)
 bool al16b(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 bool al8b(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
+// the launch of ws_gemm_xbt_bf16 (m > 0), shared with the reporter ws_gemm_xbt_bf16_variant
+struct XbtPlan {
+    int nt;                 // gemm_xbt_bf16_kernel<nt, out_f32>
+    int vecout;             // quads of columns stored at once
+    int staged;             // ws_gemm_staged (the kernel turns the tile through LDS only with vecout)
+    dim3 grid;
+};
+XbtPlan xbt_plan(int64_t m, int32_t n, int64_t ldy, const float* bias, const uint16_t* residual, int64_t ldr, const void* y,
+                 int32_t out_f32)
+{
+    XbtPlan p;
+    p.vecout = (n % 4 == 0) && (ldy % 4 == 0) && (out_f32 ? al16b(y) : al8b(y)) && (!bias || al16b(bias)) &&
+               (!residual || (al8b(residual) && ldr % 4 == 0));
+    p.staged = ws_gemm_staged;
+    p.nt = n <= 32 ? 1 : (n <= 64 ? 2 : 4);
+    p.grid = dim3((unsigned)ws_ceil_div(m, 128), (unsigned)ws_ceil_div(n, 32 * p.nt));
+    return p;
+}
+
+// where the bf16 column sums go first: NULL (none), colsum itself (one chunk) or the scratch (reduce_partials_bf_kernel after)
+float* colsum_bf_partial(int64_t m, float* colsum, void* scratch)
+{
+    return colsum ? (ws_ceil_div(m, colsum_chunk_bf(m)) == 1 ? colsum : (float*)scratch) : nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -282,21 +307,18 @@ int ws_gemm_xbt_bf16(const uint16_t* x, int64_t m, int32_t k, int64_t ldx, const
     WS_REQUIRE(al16b(x) && al16b(bt), "x and bt must be 16-byte aligned");
     WS_REQUIRE(128 * ldx * 2 + (int64_t)k * 2 < (1ll << 31) && ((int64_t)n * ldbt) * 2 < (1ll << 31), "operand exceeds the 32-bit buffer offsets");
     hipStream_t st = (hipStream_t)stream;
-    const int64_t gx = ws_ceil_div(m, 128);
-    WS_REQUIRE(gx < (1ll << 31), "m too large");
-    const int vecout = (n % 4 == 0) && (ldy % 4 == 0) && (out_f32 ? al16b(y) : al8b(y)) && (!bias || al16b(bias)) &&
-                       (!residual || (al8b(residual) && ldr % 4 == 0));
+    WS_REQUIRE(ws_ceil_div(m, 128) < (1ll << 31), "m too large");
+    const XbtPlan p = xbt_plan(m, n, ldy, bias, residual, ldr, y, out_f32);
     const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
     const bf16_t* bb = reinterpret_cast<const bf16_t*>(bt);
     const bf16_t* rb = reinterpret_cast<const bf16_t*>(residual);
 #define WS_XBT(NTV)                                                                                                        \
     do {                                                                                                                   \
-        const dim3 grid((unsigned)gx, (unsigned)ws_ceil_div(n, 32 * NTV));                                                 \
-        if (out_f32) gemm_xbt_bf16_kernel<NTV, true><<<grid, 256, 0, st>>>(xb, m, k, ldx, bb, n, ldbt, y, ldy, bias, rb, ldr, act, slope, vecout, ws_gemm_staged); \
-        else gemm_xbt_bf16_kernel<NTV, false><<<grid, 256, 0, st>>>(xb, m, k, ldx, bb, n, ldbt, y, ldy, bias, rb, ldr, act, slope, vecout, ws_gemm_staged);       \
+        if (out_f32) gemm_xbt_bf16_kernel<NTV, true><<<p.grid, 256, 0, st>>>(xb, m, k, ldx, bb, n, ldbt, y, ldy, bias, rb, ldr, act, slope, p.vecout, p.staged); \
+        else gemm_xbt_bf16_kernel<NTV, false><<<p.grid, 256, 0, st>>>(xb, m, k, ldx, bb, n, ldbt, y, ldy, bias, rb, ldr, act, slope, p.vecout, p.staged);       \
     } while (0)
-    if (n <= 32) WS_XBT(1);
-    else if (n <= 64) WS_XBT(2);
+    if (p.nt == 1) WS_XBT(1);
+    else if (p.nt == 2) WS_XBT(2);
     else WS_XBT(4);
 #undef WS_XBT
     WS_LAUNCH_CHECK();
@@ -325,7 +347,7 @@ int ws_act_bwd_colsum_bf16(const void* dy, int32_t dy_f32, int64_t m, int32_t n,
     WS_REQUIRE(al8b(dy) && (!y || al8b(y)) && (!dz || al8b(dz)), "rows must be 8-byte aligned");
     const int64_t chunk = colsum_chunk_bf(m);
     const int chunks = (int)ws_ceil_div(m, chunk);
-    float* partial = colsum ? (chunks == 1 ? colsum : (float*)scratch) : nullptr;
+    float* partial = colsum_bf_partial(m, colsum, scratch);
     const bf16_t* yb = reinterpret_cast<const bf16_t*>(y);
     bf16_t* dzb = reinterpret_cast<bf16_t*>(dz);
     if (dy_f32) {
@@ -342,4 +364,35 @@ int ws_act_bwd_colsum_bf16(const void* dy, int32_t dy_f32, int64_t m, int32_t n,
     return WS_OK;
 }
 
+// reporters (see gemm.hip): the launches of ws_gemm_xbt_bf16 / ws_act_bwd_colsum_bf16 for these arguments
+int ws_gemm_xbt_bf16_variant(int64_t m, int32_t k, int32_t n, const float* bias, const uint16_t* residual, int64_t ldr, const void* y,
+                             int64_t ldy, int32_t out_f32, char* out, int32_t cap)
+{
+    WS_REQUIRE(out && cap > 0 && m >= 0 && k >= 32 && n >= 1, "bad argument");
+    if (m == 0) {
+        snprintf(out, (size_t)cap, "none (m == 0)");
+        return WS_OK;
+    }
+    const XbtPlan p = xbt_plan(m, n, ldy, bias, residual, ldr, y, out_f32);
+    snprintf(out, (size_t)cap, "gemm_xbt_bf16_kernel<NT=%d, OUT_F32=%s> vecout=%d epilogue=%s", p.nt, out_f32 ? "true" : "false",
+             p.vecout, p.vecout && (n & 3) == 0 && p.staged ? "staged" : "lanes");
+    return WS_OK;
+}
+
+int ws_act_bwd_colsum_bf16_variant(int32_t dy_f32, int64_t m, int32_t n, float* colsum, void* scratch, char* out, int32_t cap)
+{
+    WS_REQUIRE(out && cap > 0 && m >= 0 && n >= 4, "bad argument");
+    if (m == 0) {
+        snprintf(out, (size_t)cap, "%s (m == 0)", colsum ? "memset" : "none");
+        return WS_OK;
+    }
+    const int64_t chunk = colsum_chunk_bf(m);
+    const int chunks = (int)ws_ceil_div(m, chunk);
+    const bool red = colsum_bf_partial(m, colsum, scratch) && chunks > 1;
+    snprintf(out, (size_t)cap, "act_bwd_colsum_bf16_kernel<TG=%s> chunk=%lld chunks=%d reduce=%s", dy_f32 ? "float" : "bf16",
+             (long long)chunk, chunks, red ? "reduce_partials_bf_kernel" : "none");
+    return WS_OK;
+}
+
 }  // extern "C"
+

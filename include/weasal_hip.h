@@ -651,6 +651,53 @@ int64_t ws_potentials_scratch_bytes(int64_t n);
 int ws_potentials_update(const float* pot_points, int64_t n, const double* h_center, double radius, double* potentials,
                          double* out_min, int64_t* out_argmin, void* scratch, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The sphere sampler on tiles resident in device memory: datasets/DALES_PseudoLabel.py:265-518 (`potential_item`) with
+ * datasets/common.py:252-334 (`augmentation_transform`), a whole batch per call and no host round trip per sphere.
+ *
+ * ws_sampler_create / _destroy: the table of clouds (at most 4096) and the chain's scratch.
+ * ws_sampler_add_cloud: one tile -- sub_points [n,3] f32, sub_labels [n] i32 (NULL when every batch is cut with
+ *   labels_zero), pot_points [p,3] f32 (DALES_PseudoLabel.py:826-845), potentials [p] f64 (initialised by the caller,
+ *   :211; updated in place by ws_sampler_batch).  Computes the cloud's (min, first arg-min) pair (:212-214); synchronises.
+ *   The pointers must stay valid for the life of the sampler.
+ * ws_sampler_batch: queues the chain for max_spheres (<= 64) sphere slots on `stream` and returns; nothing synchronises.
+ *   Per slot k (:321-408), skipped once `done` is set:
+ *     cloud = first arg-min of the per-cloud minima, point = its arg-min (:322-323);
+ *     centre = f64(pot_points[point]) + h_draws[k].noise (:329-333; pot_points itself is NOT modified);
+ *     members = { i : (dx*dx + dy*dy) + dz*dz <= in_radius^2 }, d = f64(sub_points[i]) - centre, float64, no FMA, in
+ *       ASCENDING index order (the KD-tree's :358 set, index-ordered);
+ *     n < 2: dropped, n_fail += 1 (:367-373); row_off + n > capacity_rows: `overflow` and `done` are set and the slot is
+ *       left undone (nothing written, potentials untouched) -- call again with resume = 1, larger buffers holding the rows
+ *       written so far, the same draws: the chain goes on with this slot;
+ *     otherwise the potentials take their Tukey update (:340-350, float64: dist = sqrt(rd), d2 = dist^2,
+ *       (1 - d2 / r^2)^2; update_potentials = 0 skips it: set 'ERF', :344) and the rows row_off .. row_off + n receive
+ *       points = (((p0 R[0,j] + p1 R[1,j]) + p2 R[2,j]) * scale[j]) + augment_noise * N(0,1), p = f32(f64(sub_points[i])
+ *       - centre) (:376, common.py:316; float32, no FMA; the normal deviate is a pure function of (seed, seq0 + k, row
+ *       in the sphere, j): counter hash of ws_dropout_apply + Box-Muller; augment_noise = 0 adds nothing),
+ *       features = [1] (fd = 1) or [1, f32(f64(z') + centre_z), z'] (fd = 3) (:389, :430-434; any other fd:
+ *       WS_ERR_UNSUPPORTED with the reference's message), labels = label_lut[sub_labels[i]] (:381; -1 outside
+ *       [0, lut_n); NULL lut: the raw label; labels_zero: 0, :377-378), input_inds = i; the slot's lengths / scales /
+ *       rots / cloud_inds / point_inds entries are written at the sphere's ordinal (:419-427, :456);
+ *       `done` once row_off > batch_limit (:404-408) or the last slot is used.
+ *   h_draws: max_spheres records of ws_sampler_draw_bytes() = 72 bytes { double noise[3]; float rot[9]; float scale[3]; }
+ *   (host; pinned memory makes the upload asynchronous).  d_state: ws_sampler_state_bytes() bytes of device memory, int64
+ *   words { done, overflow, n_spheres, n_fail, row_off, attempts, cur_slot, cur_flags } followed by 64 slot records of 8
+ *   words { n, cloud, point, row, ord (-1: not kept), centre x, y, z as float64 }: the one thing the host reads back.
+ *   Launches: 1 + 3 * max_spheres, whatever the data.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ws_sampler ws_sampler;
+int ws_sampler_create(ws_sampler** ws);
+void ws_sampler_destroy(ws_sampler* ws);
+int ws_sampler_add_cloud(ws_sampler* ws, const float* sub_points, const int32_t* sub_labels, int64_t n, const float* pot_points,
+                         double* potentials, int64_t p, void* stream);
+int64_t ws_sampler_state_bytes(void);
+int64_t ws_sampler_draw_bytes(void);
+int ws_sampler_batch(ws_sampler* ws, const void* h_draws, int32_t max_spheres, int32_t resume, int64_t batch_limit, double in_radius,
+                     float augment_noise, uint64_t seed, uint64_t seq0, int32_t fd, const int32_t* label_lut, int32_t lut_n,
+                     int32_t labels_zero, int32_t update_potentials, float* out_points, float* out_features, int64_t* out_labels,
+                     int64_t* out_input_inds, int32_t* out_lengths, float* out_scales, float* out_rots, int32_t* out_cloud_inds,
+                     int32_t* out_point_inds, int64_t capacity_rows, void* d_state, void* stream);
+
 /* nn.Dropout on the decoder output in front of the head, training mode (models/architectures.py:345-346): out[i] = keep(i) ? in[i] / (1 - p) : 0,
  * keep(i) a pure function of (seed, i) (counter-based; Bernoulli(1 - p)): the backward is the same call on the incoming
  * gradient with the same seed, no mask is stored.  in / out float32 [n], 16-byte aligned; in == out allowed. */

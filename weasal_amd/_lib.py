@@ -129,6 +129,13 @@ SIGNATURES = {
     "ws_project_confusion": (C.c_int, [_vp, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
     "ws_potentials_scratch_bytes": (_i64, [_i64]),
     "ws_potentials_update": (C.c_int, [_vp, _i64, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "ws_sampler_create": (C.c_int, [C.POINTER(_vp)]),
+    "ws_sampler_destroy": (None, [_vp]),
+    "ws_sampler_add_cloud": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "ws_sampler_state_bytes": (_i64, []),
+    "ws_sampler_draw_bytes": (_i64, []),
+    "ws_sampler_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i64, C.c_double, _f32, C.c_uint64, C.c_uint64, _i32, _vp, _i32, _i32, _i32,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "ws_softmax_ce_scratch_bytes": (_i64, [_i64]),
     "ws_softmax_ce_fwd": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ws_softmax_ce_bwd": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -9,29 +9,6 @@ char* ws_errbuf()
 
 namespace {
 
-__device__ __forceinline__ int block_exclusive_scan(int v, int* lds /*[WS_SCAN_BLOCK/64 + 1]*/, int& block_total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    int wave_off = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < WS_SCAN_BLOCK / 64; ++w) {
-        const int s = lds[w];
-        if (w < wave) wave_off += s;
-        total += s;
-    }
-    __syncthreads();
-    block_total = total;
-    return wave_off + inc - v;
-}
-
 __global__ __launch_bounds__(WS_SCAN_BLOCK) void scan_tile_sums(const int32_t* __restrict__ in, int64_t n,
                                                                  int32_t* __restrict__ sums)
 {
@@ -44,7 +21,7 @@ __global__ __launch_bounds__(WS_SCAN_BLOCK) void scan_tile_sums(const int32_t* _
         if (j < n) s += in[j];
     }
     int total;
-    block_exclusive_scan(s, lds, total);
+    ws_block_exclusive_scan(s, lds, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -63,7 +40,7 @@ __global__ __launch_bounds__(WS_SCAN_BLOCK) void scan_tile_apply(const int32_t* 
         s += v[i];
     }
     int total;
-    int run = block_exclusive_scan(s, lds, total) + (offs ? offs[blockIdx.x] : 0);
+    int run = ws_block_exclusive_scan(s, lds, total) + (offs ? offs[blockIdx.x] : 0);
 #pragma unroll
     for (int i = 0; i < WS_SCAN_IPT; ++i) {
         const int64_t j = base + i;

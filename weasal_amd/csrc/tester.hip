@@ -12,6 +12,7 @@
 // The nearest-neighbour projection itself (DALES_PseudoLabel.py:888-892, KDTree.query(k = 1)) is the K1 radius search with
 // one column (rows are sorted by distance): weasal_amd/tester.py.
 #include "ws_common.h"
+#include "ws_argmin.h"
 
 namespace {
 
@@ -94,20 +95,7 @@ __global__ __launch_bounds__(256) void argmin_partial_kernel(const double* __res
         const double x = v[i];
         if (x < best || (x == best && (bi < 0 || i < bi))) { best = x; bi = i; }
     }
-    sv[threadIdx.x] = best;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const double ov = sv[threadIdx.x + o];
-            const long long oi = si[threadIdx.x + o];
-            if (oi >= 0 && (ov < sv[threadIdx.x] || (ov == sv[threadIdx.x] && (si[threadIdx.x] < 0 || oi < si[threadIdx.x])))) {
-                sv[threadIdx.x] = ov;
-                si[threadIdx.x] = oi;
-            }
-        }
-        __syncthreads();
-    }
+    ws_argmin_block(best, bi, sv, si);       // ws_argmin.h (shared with sampler.hip)
     if (threadIdx.x == 0) { pv[blockIdx.x] = sv[0]; pi[blockIdx.x] = si[0]; }
 }
 
@@ -124,20 +112,7 @@ __global__ __launch_bounds__(256) void argmin_final_kernel(const double* __restr
         const long long xi = pi[e];
         if (xi >= 0 && (x < best || (x == best && (bi < 0 || xi < bi)))) { best = x; bi = xi; }
     }
-    sv[threadIdx.x] = best;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const double ov = sv[threadIdx.x + o];
-            const long long oi = si[threadIdx.x + o];
-            if (oi >= 0 && (ov < sv[threadIdx.x] || (ov == sv[threadIdx.x] && (si[threadIdx.x] < 0 || oi < si[threadIdx.x])))) {
-                sv[threadIdx.x] = ov;
-                si[threadIdx.x] = oi;
-            }
-        }
-        __syncthreads();
-    }
+    ws_argmin_block(best, bi, sv, si);       // ws_argmin.h (shared with sampler.hip)
     if (threadIdx.x == 0) { *out_min = sv[0]; *out_argmin = si[0]; }
 }
 

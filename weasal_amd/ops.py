@@ -1362,3 +1362,53 @@ def contrast_rows(on, xs, slc_idx, certain, lbl, temperature, eps):
     xs [S,C] = on[slc_idx], certain [N] bool, lbl [N] pseudo labels"""
     _need_cuda(on, xs)
     return _ContrastRows.apply(on, xs, slc_idx, certain, lbl, temperature, eps)
+
+
+# ------------------------------------------------------------------------------------------------
+# sphere sampler (datasets/DALES_PseudoLabel.py:265-518): thin binding of ws_sampler_*; the policy lives in sampler.py
+# ------------------------------------------------------------------------------------------------
+class SamplerHandle:
+    """the library's table of resident tiles (ws_sampler).  Keeps the tensors it was given alive."""
+
+    def __init__(self):
+        import ctypes as C
+        self.h = C.c_void_p()
+        check(_lib.lib().ws_sampler_create(C.byref(self.h)))
+        self.keep = []
+
+    def add_cloud(self, sub_points, sub_labels, pot_points, potentials):
+        _need_cuda(sub_points, pot_points, potentials)
+        if sub_points.dtype != torch.float32 or pot_points.dtype != torch.float32 or not sub_points.is_contiguous() \
+                or not pot_points.is_contiguous():
+            raise ValueError("sub_points / pot_points must be contiguous float32 tensors")
+        if potentials.dtype != torch.float64 or not potentials.is_contiguous() or potentials.shape[0] != pot_points.shape[0]:
+            raise ValueError("potentials must be a contiguous float64 tensor, one value per potential point")
+        if sub_labels is not None and (sub_labels.dtype != torch.int32 or not sub_labels.is_contiguous()
+                                       or sub_labels.shape[0] != sub_points.shape[0]):
+            raise ValueError("sub_labels must be a contiguous int32 tensor, one value per point")
+        check(_lib.lib().ws_sampler_add_cloud(self.h, ptr(sub_points), ptr(sub_labels), sub_points.shape[0], ptr(pot_points),
+                                              ptr(potentials), pot_points.shape[0], current_stream()))
+        self.keep.append((sub_points, sub_labels, pot_points, potentials))
+
+    def batch(self, h_draws, max_spheres, resume, batch_limit, in_radius, augment_noise, seed, seq0, fd, label_lut, labels_zero,
+              update_potentials, out, capacity_rows, state):
+        """queues the chain of one batch (asynchronous).  h_draws: host address of the draw records; out: the nine output
+        tensors in the order of ws_sampler_batch; state: uint8 device tensor of ws_sampler_state_bytes()."""
+        import ctypes as C
+        check(_lib.lib().ws_sampler_batch(self.h, C.c_void_p(h_draws), int(max_spheres), int(resume), int(batch_limit),
+                                          float(in_radius), float(augment_noise), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          int(seq0) & 0xFFFFFFFFFFFFFFFF, int(fd), ptr(label_lut),
+                                          0 if label_lut is None else label_lut.shape[0], int(labels_zero), int(update_potentials),
+                                          *[ptr(t) for t in out], int(capacity_rows), ptr(state), current_stream()))
+
+    def close(self):
+        if self.h:
+            _lib.lib().ws_sampler_destroy(self.h)
+            self.h = None
+            self.keep = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -33,7 +33,9 @@ class _Replay:
 
 class PyramidPrefetcher:
     """Iterates PyramidBatch objects built ahead of time from `source`, an iterable of
-    (points, features, labels, lengths) with device tensors and host lengths.
+    (points, features, labels, lengths) with device tensors and host lengths, or of the nine-entry tuples of
+    sampler.SphereSampler, whose trailing (scales, rots, cloud_inds, point_inds, input_inds) become the batch's
+    scales / rots / cloud_inds / center_inds / input_inds (datasets/DALES_PseudoLabel.py:456, :1410-1421).
 
     `workers` background threads, each with its OWN HIP stream and geometry workspaces, build alternate batches and hand
     them over in source order.  One pyramid needs five host round trips (the subsampled sizes of the four levels and the
@@ -121,9 +123,14 @@ class PyramidPrefetcher:
                     got = self._take()
                     if got is None:
                         break
-                    seq, (points, features, labels, lengths), rng = got
+                    seq, item, rng = got
+                    points, features, labels, lengths = item[:4]
                     batch = pyramid.build_batch(self.config, points, features, labels, lengths, self.limits, self.rgo,
                                                 rng=rng if rng is not None else self.rngs[w], for_training=self.for_training)
+                    if len(item) == 9:
+                        batch.scales, batch.rots, batch.cloud_inds, batch.center_inds, batch.input_inds = item[4:]
+                    elif len(item) != 4:
+                        raise ValueError("prefetcher: a source item has 4 or 9 entries, not %d" % len(item))
                     with self._cv:
                         self._done[seq] = batch
                         self._cv.notify_all()

@@ -422,6 +422,9 @@ class PyramidBatch:
             yield from getattr(self, name)
         yield self.features
         yield self.labels
+        for name in ("scales", "rots", "cloud_inds", "center_inds", "input_inds"):
+            if hasattr(self, name):
+                yield getattr(self, name)
         for _, o in self.point_orders:
             yield o
         for _, _, tb in self.tables + self.col0_tables:

@@ -1,0 +1,224 @@
+"""The sphere sampler of the potential-based datasets on tiles resident in HBM (last part).
+
+Reference: datasets/DALES_PseudoLabel.py:265-518 (`DALESPLDataset.potential_item`) and datasets/common.py:252-334
+(`PointCloudDataset.augmentation_transform`): ten forked workers behind one lock, two sklearn KD-tree radius queries per
+sphere, numpy, then a host-to-device copy of every batch.  Here the tiles stay on the device (weasal_amd.cloud_cache) and a
+whole batch is cut by one chain of kernels (ws_sampler_batch, csrc/sampler.hip): the host draws what the reference draws
+per sphere -- the centre noise, the rotation, the scales -- for every slot in advance, queues the chain, and reads ONE small
+state block back (the sphere count and the lengths).
+
+Differences from the reference, all deliberate:
+  * the potential points do not drift: the reference adds the centre noise into the KD-tree's own data (`center_point` is
+    a view, :329-333); here the centre is a copy;
+  * `input_inds` of a sphere are in ascending index order (the KD-tree returns its traversal order; same set);
+  * the per-point augmentation noise comes from a counter-based generator on the device, keyed by (seed, sphere sequence
+    number, row, column), not from the host's stream;
+  * a batch is cut from at most `max_spheres` attempts (a dropped sphere, n < 2, uses one).
+"""
+import numpy as np
+import torch
+
+from . import _lib, ops
+from .cloud_cache import coarse_potential_points
+from .kernel_points import create_3D_rotations
+
+MAX_SPHERES = 64                 # WS_PYRAMID_MAX_BATCH
+DRAW_DTYPE = np.dtype([('noise', np.float64, (3,)), ('R', np.float32, (3, 3)), ('scale', np.float32, (3,))])
+_STATE_HEAD = ('done', 'overflow', 'n_spheres', 'n_fail', 'row_off', 'attempts', 'cur_slot', 'cur_flags')
+
+
+def draw_augmentation(config, rng):
+    """(R float32 [3,3], scale float32 [3]) of one sphere, the draws of datasets/common.py:260-302 in their order"""
+    R = np.eye(3)
+    if config.augment_rotation == 'vertical':
+        theta = rng.rand() * 2 * np.pi
+        c, s = np.cos(theta), np.sin(theta)
+        R = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]], dtype=np.float32)
+    elif config.augment_rotation == 'all':
+        theta = rng.rand() * 2 * np.pi
+        phi = (rng.rand() - 0.5) * np.pi
+        u = np.array([np.cos(theta) * np.cos(phi), np.sin(theta) * np.cos(phi), np.sin(phi)])
+        alpha = rng.rand() * 2 * np.pi
+        R = create_3D_rotations(np.reshape(u, (1, -1)), np.reshape(alpha, (1, -1)))[0]
+    R = R.astype(np.float32)
+    min_s, max_s = config.augment_scale_min, config.augment_scale_max
+    if config.augment_scale_anisotropic:
+        scale = rng.rand(3) * (max_s - min_s) + min_s
+    else:
+        scale = rng.rand() * (max_s - min_s) + min_s
+    symmetries = np.array(config.augment_symmetries).astype(np.int32)
+    symmetries *= rng.randint(2, size=3)
+    scale = (scale * (1 - symmetries * 2)).astype(np.float32)
+    return R, scale
+
+
+def label_lut(label_values):
+    """int32 table raw label value -> position in the sorted label values, -1 elsewhere (`label_to_idx`,
+    datasets/common.py:245-250, with its exception: the uncertain pseudo label 10 stays 10)"""
+    lv = np.sort(np.asarray(label_values, np.int64))
+    lut = np.full(int(lv.max()) + 1, -1, np.int32)
+    lut[lv] = np.arange(len(lv), dtype=np.int32)
+    if 10 in lv:
+        lut[10] = 10
+    return lut
+
+
+class SphereSampler:
+    """Iterable of (points, features, labels, lengths, scales, rots, cloud_inds, point_inds, input_inds): device tensors,
+    `lengths` a host int32 array (its device copy is `lengths_dev`) -- the `source` a PyramidPrefetcher takes.
+
+    clouds: [(sub_points [N,3] float32, sub_labels [N] int32 or None), ...] device tensors, what
+    cloud_cache.load_subsampled_cloud returns.  set: 'training' / 'validation' (labels through label_values), 'test' (zero
+    labels), 'ERF' (zero labels, no centre noise, potentials not updated: DALES_PseudoLabel.py:241-244, :332, :344).
+    `batch_limit` is an attribute (calibration.BatchLimitController drives it; the reference starts at 1, :202).
+    Data parallelism: one sampler per rank with seed = base + rank."""
+
+    def __init__(self, config, clouds, set='training', label_values=None, ignored_labels=(), seed=None, max_spheres=None,
+                 device=None, batch_limit=1.0):
+        if config.in_features_dim not in (1, 3):
+            raise ValueError('Only accepted input dimensions are 1 and 3')
+        if not clouds:
+            raise ValueError("SphereSampler needs at least one cloud")
+        self.config = config
+        self.set = set
+        self.device = device if device is not None else clouds[0][0].device
+        self.rng = np.random.RandomState(seed) if seed is not None else np.random
+        self.max_spheres = int(max_spheres if max_spheres is not None else MAX_SPHERES)
+        if not 1 <= self.max_spheres <= MAX_SPHERES:
+            raise ValueError("max_spheres must lie in [1, %d]" % MAX_SPHERES)
+        self.batch_limit = batch_limit
+        self.ignored_labels = tuple(ignored_labels)     # the loss ignores them; the sampler's label map covers every value
+        self.labels_zero = set in ('test', 'ERF')
+        self.lut = None
+        if label_values is not None and not self.labels_zero:
+            self.lut = torch.from_numpy(label_lut(label_values)).to(self.device)
+        lib = _lib.lib()
+        self._state_bytes = int(lib.ws_sampler_state_bytes())
+        assert int(lib.ws_sampler_draw_bytes()) == DRAW_DTYPE.itemsize
+        self.handle = ops.SamplerHandle()
+        self.sub_points, self.sub_labels, self.pot_points, self.potentials = [], [], [], []
+        for pts, lab in clouds:
+            pts = ops._f32c(pts)
+            lab = None if lab is None else lab.detach().to(torch.int32).reshape(-1).contiguous()
+            if lab is None and not self.labels_zero:
+                raise ValueError("set '%s' needs the labels of every cloud" % set)
+            pot_pts = coarse_potential_points(pts, config.in_radius).contiguous()
+            pot = torch.from_numpy(self.rng.rand(pot_pts.shape[0]) * 1e-3).to(self.device)      # :211
+            self.handle.add_cloud(pts, lab, pot_pts, pot)
+            self.sub_points.append(pts); self.sub_labels.append(lab); self.pot_points.append(pot_pts); self.potentials.append(pot)
+        self.noise_seed = int(seed) if seed is not None else int(self.rng.randint(2 ** 31 - 1))
+        self.seq = 0                      # sphere sequence number of the next slot
+        self.failed = 0                   # dropped spheres so far
+        self.lengths_dev = None
+        self._sync_count = 0              # blocking device-to-host reads made by sample()
+        self._max_n = 0
+        self._h_draws = torch.empty(MAX_SPHERES * DRAW_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
+
+    # -----------------------------------------------------------------------------------------------------------
+    def draw(self, n=None):
+        """the host-drawn values of n sphere slots (centre noise :333, rotation and scales common.py:260-302), in the
+        order the reference consumes its stream for one sphere after the other"""
+        n = self.max_spheres if n is None else n
+        d = np.zeros(n, DRAW_DTYPE)
+        for k in range(n):
+            if self.set != 'ERF':
+                d['noise'][k] = self.rng.normal(scale=self.config.in_radius / 10, size=(1, 3))[0]
+            d['R'][k], d['scale'][k] = draw_augmentation(self.config, self.rng)
+        return d
+
+    def set_potentials(self, values):
+        """replace the potentials of every cloud (float64 arrays) and recompute the per-cloud (min, arg-min) pairs: a
+        restart from saved potentials"""
+        torch.cuda.current_stream(self.device).synchronize()
+        for p, v in zip(self.potentials, values):
+            p.copy_(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)))
+        self.handle.close()
+        self.handle = ops.SamplerHandle()
+        for args in zip(self.sub_points, self.sub_labels, self.pot_points, self.potentials):
+            self.handle.add_cloud(*args)
+
+    def _read_state(self, state):
+        """the single blocking read of a batch: the state block of ws_sampler_batch"""
+        self._sync_count += 1
+        words = state.cpu().numpy().view(np.int64)
+        head = dict(zip(_STATE_HEAD, (int(v) for v in words[:8])))
+        slots = words[8:].reshape(MAX_SPHERES, 8)
+        return head, slots
+
+    def _capacity(self):
+        return int(self.batch_limit) + max(2 * self._max_n, 4096)
+
+    def sample(self, draws=None, capacity_rows=None, augment_noise=None):
+        """One batch (DALES_PseudoLabel.py:287-456).  draws: a DRAW_DTYPE array (or a dict with 'noise' [S,3], 'R' [S,3,3],
+        'scale' [S,3]) for every one of the max_spheres slots, instead of drawing them here.  capacity_rows: rows of the
+        output buffers of the first attempt (grown and resumed when a sphere does not fit)."""
+        cfg = self.config
+        S = self.max_spheres
+        fd = int(cfg.in_features_dim)
+        if fd not in (1, 3):
+            raise ValueError('Only accepted input dimensions are 1 and 3')
+        injected = draws is not None
+        fails = 0
+        while True:
+            d = self.draw(S) if draws is None else draws
+            if isinstance(d, dict):
+                dd = np.zeros(S, DRAW_DTYPE)
+                for key in ('noise', 'R', 'scale'):
+                    dd[key] = np.asarray(d[key])[:S]
+                d = dd
+            if d.dtype != DRAW_DTYPE or d.shape[0] < S:
+                raise ValueError("draws must hold max_spheres = %d records of sampler.DRAW_DTYPE" % S)
+            host = self._h_draws.numpy().view(DRAW_DTYPE)
+            host[:S] = d[:S]
+            out = self._chain(host, S, fd, capacity_rows, cfg.augment_noise if augment_noise is None else augment_noise)
+            if out is not None:
+                return out
+            fails = self.last_failed if injected else fails + self.last_failed
+            if injected or fails > 100 * cfg.batch_num:                 # :369-370
+                raise ValueError('It seems this dataset only containes empty input spheres')
+
+    def _chain(self, host, S, fd, capacity_rows, augment_noise):
+        dev = self.device
+        cap = int(capacity_rows) if capacity_rows is not None else self._capacity()
+        state = torch.empty(self._state_bytes, dtype=torch.uint8, device=dev)
+        per_sphere = [torch.empty(S, dtype=torch.int32, device=dev), torch.empty((S, 3), dtype=torch.float32, device=dev),
+                      torch.empty((S, 3, 3), dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.int32, device=dev),
+                      torch.empty(S, dtype=torch.int32, device=dev)]
+        rows = None
+        resume = 0
+        while True:
+            new = [torch.empty((cap, 3), dtype=torch.float32, device=dev), torch.empty((cap, fd), dtype=torch.float32, device=dev),
+                   torch.empty(cap, dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.int64, device=dev)]
+            if rows is not None:                   # a sphere did not fit: keep what was written, go on with that sphere
+                for a, b in zip(new, rows):
+                    a[:head['row_off']].copy_(b[:head['row_off']])
+            rows = new
+            self.handle.batch(host.ctypes.data, S, resume, int(self.batch_limit), float(self.config.in_radius), augment_noise,
+                              self.noise_seed, self.seq, fd, self.lut, self.labels_zero, self.set != 'ERF',
+                              rows + per_sphere, cap, state)
+            head, slots = self._read_state(state)
+            if not head['overflow']:
+                break
+            need = int(slots[head['attempts'], 0])                      # the sphere that did not fit
+            cap = max(2 * cap, head['row_off'] + need + int(self.batch_limit))
+            resume = 1
+        B, total = head['n_spheres'], head['row_off']
+        self.seq += head['attempts']
+        self.last_failed = head['n_fail']
+        self.failed += head['n_fail']
+        self.last_state = (head, slots)
+        if B == 0:
+            return None
+        kept = slots[:head['attempts']]
+        kept = kept[kept[:, 4] >= 0]
+        lengths = kept[:, 0].astype(np.int32)
+        self._max_n = max(self._max_n, int(lengths.max()))
+        self.lengths_dev = per_sphere[0][:B]
+        self.last_centres = kept[:, 5:8].copy().view(np.float64)
+        points, features, labels, input_inds = (t[:total] for t in rows)
+        return (points, features, labels, lengths, per_sphere[1][:B], per_sphere[2][:B], per_sphere[3][:B], per_sphere[4][:B],
+                input_inds)
+
+    def __iter__(self):
+        while True:
+            yield self.sample()

@@ -790,9 +790,24 @@ int ws_kpconv_layer_fwd_fused(const float* q_pts, int64_t nq, const float* s_pts
                               const int32_t* order, const float* weights, int32_t co, const float* bias, int32_t act, float slope,
                               float* out, void* stream);
 /* name of the forward gather kernel the library launches for a layer of ci channels (mode 0 rigid, 1 deformable through the
- * generic entries, 2 deformable fast path): for reports, no device work */
+ * generic entries, 2 deformable fast path): for reports, no device work.  It assumes 16-byte aligned rows and a level of
+ * 4096 queries or more (no narrowed channel blocks, no csplit items); ws_kpconv_gather_variant answers for any arguments */
 int ws_kpconv_gather_fwd_variant(int32_t ci, int32_t mode, int32_t influence, int32_t aggregation, int32_t rows_bf16,
                                  int32_t rows_sorted, char* out, int32_t cap);
+/* the launch a KPConv gather entry makes for these arguments (the launchers' own plan functions; pointers are only tested for
+ * alignment, nothing is read or launched): "kernel<template arguments> grid=... [csplit=... | ilv=... | vec4=...]" into
+ * out[cap], or the entry's own refusal.  op names the entry family (its _bf16 / _ex / _gated forms included, rows_bf16 = 1
+ * for bf16 rows); rows_a, rows_b: its two feature-row operands (x and wf for the forward entries, dwf and dx for bwd_x*,
+ * x and dwf for bwd_geom*).  deformed / modulated: deformed_kp / modulations given (WS_GATHER_BWD_X_GRID_WIDE: kp4 given);
+ * rows_sorted as in the _ex / _def entries; ordered: a point order is passed.  The grid entries also follow
+ * ws_kpconv_grid_sorted.  Arguments an entry does not take are ignored. */
+enum {
+    WS_GATHER_FWD = 0, WS_GATHER_BWD_X = 1, WS_GATHER_BWD_GEOM = 2, WS_GATHER_BWD_X_GRID = 3,
+    WS_GATHER_FWD_DEF = 4, WS_GATHER_BWD_X_DEF = 5, WS_GATHER_BWD_X_GRID_WIDE = 6, WS_GATHER_BWD_GEOM_DEF = 7
+};
+int ws_kpconv_gather_variant(int32_t op, int64_t nq, int64_t ns, int32_t ci, const void* rows_a, const void* rows_b, int32_t deformed,
+                             int32_t modulated, int32_t influence, int32_t aggregation, int32_t rows_bf16, int32_t rows_sorted,
+                             int32_t ordered, char* out, int32_t cap);
 /* the launches the dense products make for these arguments (the dispatchers' own plan functions; pointers are only tested
  * for alignment, nothing is read or launched): "kernel<template arguments> key=value ..." into out[cap].
  * ws_gemm_xb_variant: any ws_gemm_xb* entry (b_row_stride < 0 = row-major [K, N]; gate_y / mask NULL when absent);

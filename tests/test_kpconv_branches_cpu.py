@@ -5,11 +5,14 @@ what the dispatch launches.
   kernel point of one channel, a partial last channel block shifted by one channel and a `closest` tie resolved to the
   later kernel point -- defects a per-tensor `max|a-b| <= tol * max|ref|` bound lets through where the values are small.
 * The rows meant to straddle SPLIT_ROWS / SPLIT_NT (read from kpconv.hip) and ops.GRID_NARROW_MAX still do.
-* Every row's kernel and template arguments agree with a restatement of the dispatch (gather_fwd_impl,
-  gather_bwd_x_impl, gather_bwd_geom_impl), and, where it applies, with the library's own name for the forward kernel:
-  ws_kpconv_gather_fwd_variant (bench.py's roofline line).  That reporter takes neither nq nor the row alignment, so it
-  does not describe the SPLIT_NT narrowing / csplit items (rigid linear / sum below SPLIT_ROWS queries) or the NT = 1
-  fallback of unaligned rows: it is asked only about aligned rows outside those branches.
+* Every row of BRANCHES, none excepted, agrees with the library's own statement of the launch: ws_kpconv_gather_variant,
+  which formats the plan the launcher itself follows (kernel, every template argument, csplit; K4 and K6 where the row
+  runs them), asked with stand-in addresses of the alignment the GPU run has (the view="offset" rows 4 bytes off).  The
+  GRID_SLAB / GRID_WIDE cases are checked the same way (G, MODE, VEC, SORT or NCH, ilv with and without a point order).
+* A sweep of the reporter over layer shapes lists the distinct plans in this module's scope (MODE 2 and FUSE belong to
+  other modules); the tables reach every one of them.
+* ws_kpconv_gather_fwd_variant (bench.py's roofline line) is the forward answer of that reporter for aligned rows at
+  nq = SPLIT_ROWS, wherever the launcher accepts the layer.
 """
 import ctypes as C
 import os
@@ -108,8 +111,8 @@ def test_bound_flags_a_tie_resolved_to_the_later_kernel_point():
 # ------------------------------------------------------------------------------------------------------------------
 # the table straddles the constants
 # ------------------------------------------------------------------------------------------------------------------
-def _nt(ci):
-    return 1 if ci <= 16 else 2 if ci <= 32 else 4 if ci <= 64 else 8 if ci <= 128 else 16
+def _nt(table_args):
+    return int(GB.table_launch(GB.MF, table_args)[1]["NT"])
 
 
 def test_table_straddles_split_rows():
@@ -124,9 +127,9 @@ def test_table_straddles_split_rows():
         assert below["nq"] == split_rows - 1 and at["nq"] == split_rows, (ci, dt)
         assert below["ci"] == at["ci"] == ci
         # on both sides of the row count the dispatch switches: nt narrows to SPLIT_NT and the query splits into items
-        assert _nt(ci) > split_nt and ci % split_nt == 0 and ci > 16 * split_nt, ci
-        assert "NT=%d," % split_nt in below["targs"] and below["csplit"] == -(-ci // (16 * split_nt)) > 1
-        assert "NT=%d," % _nt(ci) in at["targs"] and at["csplit"] == 1
+        assert _nt(at["targs"]) > split_nt and ci % split_nt == 0 and ci > 16 * split_nt, ci
+        assert _nt(below["targs"]) == split_nt and below["csplit"] == -(-ci // (16 * split_nt)) > 1
+        assert _nt(at["targs"]) == {128: 8, 256: 16}[ci] and at["csplit"] == 1
 
 
 def test_table_straddles_grid_narrow_max():
@@ -137,79 +140,147 @@ def test_table_straddles_grid_narrow_max():
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# the table agrees with the dispatch and with the library's own name
+# the tables agree with the library's own statement of each launch
 # ------------------------------------------------------------------------------------------------------------------
-def _fwd_dispatch(r, split_rows, split_nt):
-    """(kernel, template args, csplit) as gather_fwd_impl picks them"""
-    ci, bf = r["ci"], r["dtype"] == "bf16"
-    t = "bf16" if bf else "float"
-    aligned = r["view"] == "aligned"
-    deff = r["deform"] is not None
-    fast = r["influence"] == "linear" and r["aggregation"] == "sum"
-    if ci > 4:
-        fastm = fast and not deff
-        nt = _nt(ci)
-        vecrow = ci % nt == 0 and (nt == 1 or aligned)
-        if not vecrow:
-            nt = 1
-        if fastm and not r["rows_sorted"] and r["nq"] < split_rows and nt > split_nt and ci % split_nt == 0:
-            nt = split_nt
-        csplit = 1
-        if fastm and not r["rows_sorted"] and r["nq"] < split_rows and ci > 16 * nt:
-            csplit = -(-ci // (16 * nt))
-        mode = 0 if fastm else 1
-        return GB.MF, GB._mf(nt, mode, deff, t, cut=fastm and r["rows_sorted"]), csplit
-    vec4 = ci % 4 == 0 and aligned
-    mode = 0 if (fast and not deff) else 1
-    return GB.VF, GB._vf(1 if vec4 else 4, mode, deff, vec4, 4 if vec4 else 1, t), 1
+def _ns(r):
+    return {"self": r["nq"], "distinct": r["nq"] + 37, "hub": 2001, "dense": 2400}[r["queries"]]
 
 
-def test_table_matches_the_dispatch():
-    split_rows, split_nt = _hip_constant("SPLIT_ROWS"), _hip_constant("SPLIT_NT")
+def _row_ptr(r):
+    off = 1 if r["view"] == "offset" else 0        # x = flat[1:]; wf, dwf and dx are fresh allocations
+    return lambda name: GB.fake_ptr(name, off if name == "x" else 0, 2 if r["dtype"] == "bf16" else 4)
+
+
+def test_table_matches_the_reporter():
+    launches = 0
     for r in GB.BRANCHES:
-        assert (r["kernel"], r["targs"], r["csplit"]) == _fwd_dispatch(r, split_rows, split_nt), r["id"]
-        t = "bf16" if r["dtype"] == "bf16" else "float"
-        fast = r["influence"] == "linear" and r["aggregation"] == "sum" and r["deform"] is None
-        if r["bwd"]:
-            assert r["bwd"] == GB._k4(GB._k4g(r["ci"]), 0 if fast else 1, r["ci"] % 4 == 0, t), r["id"]
-        if r["geom"]:
-            assert r["geom"] == GB._k6(t, r["ci"] % 4 == 0), r["id"]
+        launches += GB.check_row_plan(r, _row_ptr(r), r["nq"], _ns(r))
         assert bool(r["geom"]) == (r["deform"] is not None and bool(r["bwd"])), r["id"]
         if r["dtype"] == "bf16":
             assert r["ci"] % 4 == 0 and r["view"] == "aligned", r["id"]
         if r["rows_sorted"]:
             assert r["entry"] == "ws_kpconv_gather_fwd_ex"
+    assert launches == len(GB.BRANCHES) + sum(bool(r["bwd"]) + bool(r["geom"]) for r in GB.BRANCHES)
 
 
-def _parse(name):
-    m = re.match(r"(\w+)<(.*)>", name.split(" (")[0])
-    assert m, name
-    args = {}
-    for a in m.group(2).split(","):
-        a = a.strip()
-        k, _, v = a.partition("=")
-        if not _:
-            k, v = "T", a
-        args[k.strip()] = v.strip()
-    args.pop("GS", None)
-    return m.group(1), args
+def _grid_report(ci, variant, dt, wide, ordered, ns=7000):
+    return GB.report("bwd_x_grid_wide" if wide else "bwd_x_grid", ns, ns, ci, GB.fake_ptr("dwf"), GB.fake_ptr("dx"), dtype=dt,
+                     deformed=variant == "deformable", modulated=variant == "deformable",
+                     influence="gaussian" if variant == "gaussian-closest" else "linear",
+                     aggregation="closest" if variant == "gaussian-closest" else "sum", ordered=ordered)
 
 
-def test_table_matches_the_variant_reporter():
+def test_grid_tables_match_the_reporter():
+    from weasal_amd import _lib
+    assert GB.GRID_ILV == _hip_constant("GRID_INTERLEAVE")
+    switch = C.c_int.in_dll(_lib.lib(), "ws_kpconv_grid_sorted")
+    cases = [(ci, v, dt, False) for ci, v, dt in GB.GRID_SLAB] + [(ci, "rigid", dt, True) for ci, dt in GB.GRID_WIDE]
+    try:
+        for sort in (False, True):
+            switch.value = int(sort)
+            for ci, variant, dt, wide in cases:
+                for ordered in (False, True):
+                    kernel, args, keys = _grid_report(ci, variant, dt, wide, ordered)
+                    want = GB.grid_plan(ci, variant, dt, wide, sort, ordered)
+                    assert (kernel, args, keys["ilv"]) == (want[0], GB.table_launch(*want[:2])[1], want[2]), (ci, variant, dt, wide)
+                    # the interleaved assignment: 8 XCDs x min(ilv, 32-support chunks) workgroups
+                    assert keys["grid"] == (8 * min(GB.GRID_ILV, -(-7000 // 32)) if ordered else 8 * -(-(-(-7000 // 4)) // 8))
+    finally:
+        switch.value = 0
+
+
+def _plan_key(launch):
+    kernel, args, keys = launch
+    return (kernel,) + tuple(sorted(args.items())) + ((("vec4", keys["vec4"]),) if "vec4" in keys else ())
+
+
+def test_tables_reach_every_plan_in_scope():
+    """the reporter swept over layer shapes: every distinct (kernel, template arguments) it can name for the generic entries
+    and the rigid wide form is one the tables run.  By family: matrix-core K3 5 NT x 2 row types x (MODE 0, MODE 0 + CUT,
+    MODE 1, MODE 1 + DEF) = 40; pool K3 (G 1 / 4 for f32, G 1 for bf16) x (MODE 0, MODE 1, MODE 1 + DEF) = 9; K4 5 G x 2 MODE
+    x (f32 VEC / scalar, bf16 VEC) = 30; K6 f32 vec4 0 / 1, bf16 vec4 1 = 3; K4G slab 30 x SORT = 60; K4G wide (G 1..8 with
+    NCH 1, G 16 with NCH 1 / 2 / 4) x 3 = 21."""
+    from weasal_amd import _lib
+    split_rows = _hip_constant("SPLIT_ROWS")
+    switch = C.c_int.in_dll(_lib.lib(), "ws_kpconv_grid_sorted")
+    swept = set()
+    try:
+        for ci in list(range(1, 70)) + [96, 100, 128, 130, 192, 256, 260, 300]:
+            for dt in ("f32", "bf16"):
+                for off in (0, 1):
+                    if dt == "bf16" and (ci % 4 or off):
+                        continue                       # refused by every entry (module docstring of the GPU side)
+                    es = 2 if dt == "bf16" else 4
+                    x, wf, dwf, dx = GB.fake_ptr("x", off, es), GB.fake_ptr("wf"), GB.fake_ptr("dwf"), GB.fake_ptr("dx")
+                    for influence, aggregation in (("linear", "sum"), ("gaussian", "sum"), ("constant", "closest")):
+                        for deform in (None, "def", "defmod"):
+                            kw = dict(dtype=dt, deformed=deform is not None, modulated=deform == "defmod", influence=influence,
+                                      aggregation=aggregation)
+                            for nq in (split_rows - 1, split_rows):
+                                for srt in (False, True):
+                                    swept.add(_plan_key(GB.report("fwd", nq, nq, ci, x, wf, rows_sorted=srt, **kw)))
+                            swept.add(_plan_key(GB.report("bwd_x", 600, 600, ci, dwf, dx, **kw)))
+                            if deform:
+                                swept.add(_plan_key(GB.report("bwd_geom", 600, 600, ci, x, dwf, **kw)))
+                            if not off:
+                                for sort in (0, 1):
+                                    switch.value = sort
+                                    swept.add(_plan_key(GB.report("bwd_x_grid", 600, 600, ci, dwf, dx, **kw)))
+                                switch.value = 0
+                                if influence == "linear" and not deform:
+                                    swept.add(_plan_key(GB.report("bwd_x_grid_wide", 600, 600, ci, dwf, dx, **kw)))
+    finally:
+        switch.value = 0
+    reached = set()
+    for r in GB.BRANCHES:
+        reached.add(_plan_key(GB.table_launch(r["kernel"], r["targs"])))
+        for key in ("bwd", "geom"):
+            if r[key]:
+                reached.add(_plan_key(GB.table_launch(*r[key])))
+    for ci, variant, dt in GB.GRID_SLAB:
+        for sort in (False, True):
+            reached.add(_plan_key(GB.table_launch(*GB.grid_plan(ci, variant, dt, False, sort)[:2])))
+    for ci, dt in GB.GRID_WIDE:
+        reached.add(_plan_key(GB.table_launch(*GB.grid_plan(ci, "rigid", dt, True)[:2])))
+    assert len(swept) == 40 + 9 + 30 + 3 + 60 + 21, len(swept)
+    assert swept - reached == set(), sorted(swept - reached)
+    assert reached - swept == set(), sorted(reached - swept)
+
+
+def test_old_reporter_is_the_forward_plan_at_split_rows():
+    """ws_kpconv_gather_fwd_variant = the forward answer of ws_kpconv_gather_variant for aligned rows at nq = SPLIT_ROWS"""
     from weasal_amd import _lib, ops
     lib = _lib.lib()
     split_rows = _hip_constant("SPLIT_ROWS")
     asked = 0
-    for r in GB.BRANCHES:
-        fastm = r["influence"] == "linear" and r["aggregation"] == "sum" and r["deform"] is None
-        if r["view"] != "aligned" or (r["ci"] > 4 and fastm and not r["rows_sorted"] and r["nq"] < split_rows):
-            continue           # the reporter knows neither the alignment nor nq (module docstring)
-        buf = C.create_string_buffer(256)
-        _lib.check(lib.ws_kpconv_gather_fwd_variant(r["ci"], 1 if r["deform"] else 0, ops.INFLUENCE[r["influence"]],
-                                                    ops.AGGREGATION[r["aggregation"]], 1 if r["dtype"] == "bf16" else 0,
-                                                    1 if r["rows_sorted"] else 0, buf, 256))
-        kernel, args = _parse(buf.value.decode())
-        want_kernel, want = _parse("%s<%s>" % (r["kernel"], r["targs"]))
-        assert kernel == want_kernel and args == want, (r["id"], buf.value.decode())
-        asked += 1
-    assert asked >= 30
+    for ci in range(1, 301):
+        for mode in (0, 1, 2):
+            for influence in ("linear", "constant", "gaussian"):
+                for aggregation in ("sum", "closest"):
+                    if mode == 2 and (influence, aggregation) != ("linear", "sum"):
+                        continue
+                    for dt in ("f32", "bf16"):
+                        for srt in (0, 1):
+                            new = C.create_string_buffer(256)
+                            rc = lib.ws_kpconv_gather_variant(GB.GATHER_OPS["fwd_def" if mode == 2 else "fwd"], split_rows, split_rows, ci,
+                                                              GB.fake_ptr("x"), GB.fake_ptr("wf"), int(mode == 1), 0,
+                                                              ops.INFLUENCE[influence], ops.AGGREGATION[aggregation], int(dt == "bf16"), srt, 0,
+                                                              new, 256)
+                            old = C.create_string_buffer(256)
+                            rc_old = lib.ws_kpconv_gather_fwd_variant(ci, mode, ops.INFLUENCE[influence], ops.AGGREGATION[aggregation],
+                                                                      int(dt == "bf16"), srt, old, 256)
+                            assert rc == rc_old, (ci, mode, dt)
+                            if rc != 0:
+                                assert dt == "bf16" and ci % 4, (ci, mode, dt)      # the launcher refuses the layer
+                                continue
+                            kernel, args, keys = GB.parse_launch(new.value.decode())
+                            text = old.value.decode()
+                            okernel, _, orest = text.partition("<")
+                            oargs = [a.strip() for a in orest.partition(">")[0].split(",")]
+                            oargs = dict(a.split("=") if "=" in a else ("T", a) for a in oargs)
+                            assert oargs.pop("GS", "default") == "default"
+                            assert (okernel, oargs) == (kernel, args), (text, new.value.decode())
+                            assert keys["csplit"] == 1
+                            assert text.endswith(" (sorted-row cutoff on)") == bool(keys.get("cut") and args["MODE"] == "0"), text
+                            asked += 1
+    assert asked > 300 * 2 * 14

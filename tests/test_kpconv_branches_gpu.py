@@ -1,24 +1,29 @@
 """Every launch branch of the KPConv gather dispatch (weasal_amd/csrc/kpconv.hip) held to a float64 reference, per element.
 
-`BRANCHES` names, row by row, the kernel instantiation a public entry launches and the inputs that reach it.  The
-dispatch code behind the rows:
-  forward, ci > 4   gather_fwd_impl (kpconv.hip, "if (ci > 4)"): nt from ci (<=16: 1, <=32: 2, <=64: 4, <=128: 8, else 16);
-                    nt = 1 unless ci % nt == 0 and the rows are 16-byte aligned; the rigid linear / sum form (fastm) on
-                    fewer than SPLIT_ROWS queries narrows nt to SPLIT_NT and splits a query into csplit items of one
-                    channel block each; rows_sorted + fastm launches the CUT form (ws_kpconv_gather_fwd_ex); WS_FWDM picks
-                    MODE 0 (fastm), 1 (anything else), DEF (deformed_kp given).  VECROW is always true in the dispatch:
-                    "masked rows" are NT = 1 with lanes past ci masked, several blocks looped in the kernel when csplit = 1.
-  forward, ci <= 4  gather_fwd_impl, WS_FWDV: vec4 (ci % 4 == 0 and aligned rows) -> G = 1, VEC, PW = 4; else (f32 only)
-                    G = 4, PW = 1.  MODE 0 = linear / sum, rigid; MODE 1 otherwise.
-  K4                gather_bwd_x_impl (the transposed table): G from ci (<=4: 1, <=8: 2, <=16: 4, <=32: 8, else 16), MODE 0
-                    = rigid linear / sum, VEC = ci % 4 == 0 and aligned dwf / dx.  Reached whenever the layer has no search
-                    grid (queries distinct from the supports, or no PyramidBatch.activate()).
-  K6                gather_bwd_geom_impl: one template per row type; vec4 (ci % 4 == 0, aligned) is a kernel argument.
-  K4G slab / wide   gather_bwd_x_grid_impl / gather_bwd_x_gridw_impl via ops._KPConvGather.backward on a self-query layer
-                    of an activated batch: wide when grid.max_count > ops.GRID_NARROW_MAX (rigid linear / sum only).
+`BRANCHES` names, row by row, the kernel instantiation a public entry launches and the inputs that reach it; GRID_SLAB /
+GRID_WIDE with GRID_PLAN do the same for the table-free backward.  The table is the independent statement; the library's
+own statement is ws_kpconv_gather_variant, which formats the plan functions the launchers call (kpconv.hip: fwd_plan,
+bwd_x_plan, bwd_geom_plan, bwd_x_grid_plan, bwd_x_gridw_plan).  Before anything is launched here the reporter is asked
+with the real device pointers and has to name the row's kernel, every template argument and csplit / ilv
+(tests/test_kpconv_branches_cpu.py asks it about every row with stand-in addresses).  The rules behind the rows:
+  forward, ci > 4   NT from ci (<=16: 1, <=32: 2, <=64: 4, <=128: 8, else 16); NT = 1 unless ci % NT == 0 and the rows are
+                    16-byte aligned; the rigid linear / sum form on fewer than SPLIT_ROWS queries narrows NT to SPLIT_NT and
+                    splits a query into csplit items of one channel block each; rows_sorted + rigid linear / sum launches
+                    the CUT form (ws_kpconv_gather_fwd_ex); MODE 0 (rigid linear / sum), 1 (anything else), DEF (deformed_kp
+                    given).  VECROW is always true: "masked rows" are NT = 1 with lanes past ci masked, several blocks
+                    looped in the kernel when csplit = 1.
+  forward, ci <= 4  vec4 (ci % 4 == 0 and aligned rows) -> G = 1, VEC, PW = 4; else (f32 only) G = 4, PW = 1.  MODE 0 = linear /
+                    sum, rigid; MODE 1 otherwise.
+  K4                the transposed table: G from ci (<=4: 1, <=8: 2, <=16: 4, <=32: 8, else 16), MODE 0 = rigid linear / sum,
+                    VEC = ci % 4 == 0 and aligned dwf / dx.  Reached whenever the layer has no search grid (queries distinct
+                    from the supports, or no PyramidBatch.activate()).
+  K6                one template per row type; vec4 (ci % 4 == 0, aligned) is a kernel argument.
+  K4G slab / wide   via ops._KPConvGather.backward on a self-query layer of an activated batch: wide when grid.max_count >
+                    ops.GRID_NARROW_MAX (rigid linear / sum only); G, MODE, VEC as K4, SORT = ws_kpconv_grid_sorted, NCH from ci
+                    (G = 16 only: <=64: 1, <=128: 2, else 4); ilv = GRID_INTERLEAVE when the supports have a point order.
 Unreachable through a public entry (so not in the table): kpconv_gather_fwd_mfma_kernel<..., VECROW=false> (never
 instantiated: the dispatch always passes VECROW = true and masks NT = 1 rows instead); bf16 rows that are not 8-byte
-aligned or have ci % 4 != 0 (the entries refuse them: WS_REQUIRE in every launcher).  Left to other modules: MODE 2 (the
+aligned or have ci % 4 != 0 (the entries refuse them: rows_vec4_or_f32 in every plan).  Left to other modules: MODE 2 (the
 deformable fast path, ws_kpconv_gather_*_def: test_deform_fast_gpu.py, test_bf16_deform_chain_gpu.py) and FUSE (the fused
 forward layer: test_infer_gpu.py).
 
@@ -139,6 +144,8 @@ BRANCHES += [
     _b("k3_offset_mode1_f32", FWD["f32"], MF, _mf(1, 1, False, "float"), 48, 600, view="offset", influence="gaussian",
        note="NT=1, 3 blocks looped in the kernel"),
     _b("k3_offset_def_f32", FWD["f32"], MF, _mf(1, 1, True, "float"), 40, 400, view="offset", deform="def"),
+    # ---- one channel per lane, deformable, bf16 rows (the f32 form: ties_def_f32): the reporter sweep names it
+    _b("k3_def_nt1_bf16", FWD["bf16"], MF, _mf(1, 1, True, "bf16"), 16, 400, deform="def"),
     # ---- K6 scalar form (ci % 4 != 0): f32 only
     _b("k3_defmod_ci30_f32", FWD["f32"], MF, _mf(2, 1, True, "float"), 30, 400, deform="defmod", bwd=_k4(8, 1, False, "float"),
        geom=_k6("float", False)),
@@ -206,6 +213,78 @@ GRID_SLAB = [(ci, variant, dt) for ci in (4, 3, 8, 6, 16, 14, 32, 30, 64, 50) fo
 GRID_SLAB_LIMITS = [20, 30, 40, 40, 30]          # every row <= ops.GRID_NARROW_MAX: the slab form
 GRID_WIDE_LIMITS = [422, 519, 472, 193, 34]      # the config-5 limits: level-0 rows > ops.GRID_NARROW_MAX, the wide form
 GRID_WIDE = [(ci, dt) for ci in (4, 3, 8, 6, 16, 14, 32, 30, 64, 50, 128, 98, 256, 198) for dt in (("f32", "bf16") if ci % 4 == 0 else ("f32",))]
+# what those cases launch: G per ci, NCH per ci (wide form), MODE per variant, VEC = ci % 4 == 0 (the rows are aligned),
+# SORT = ws_kpconv_grid_sorted, ilv = GRID_INTERLEAVE with a point order on the supports and 0 without
+GRID_G = {4: 1, 3: 1, 8: 2, 6: 2, 16: 4, 14: 4, 32: 8, 30: 8, 64: 16, 50: 16, 128: 16, 98: 16, 256: 16, 198: 16}
+GRID_NCH = {128: 2, 98: 2, 256: 4, 198: 4}
+GRID_MODE = {"rigid": 0, "gaussian-closest": 1, "deformable": 1}
+GRID_ILV = 512
+K4G = "kpconv_gather_bwd_x_grid_kernel"
+K4GW = "kpconv_gather_bwd_x_gridw_kernel"
+
+
+def grid_plan(ci, variant, dt, wide, sort=False, ordered=False):
+    """(kernel, template arguments, ilv) the table-free backward launches for a GRID_SLAB / GRID_WIDE case"""
+    tb = lambda v: "true" if v else "false"
+    if wide:
+        targs = "K=15, G=%d, MODE=%d, VEC=%s, NCH=%d, T=%s" % (GRID_G[ci], GRID_MODE[variant], tb(ci % 4 == 0), GRID_NCH.get(ci, 1), _tn(dt))
+    else:
+        targs = "K=15, G=%d, MODE=%d, VEC=%s, T=%s, SORT=%s" % (GRID_G[ci], GRID_MODE[variant], tb(ci % 4 == 0), _tn(dt), tb(sort))
+    return (K4GW if wide else K4G, targs, GRID_ILV if ordered else 0)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the library's own statement of a launch: ws_kpconv_gather_variant
+# ------------------------------------------------------------------------------------------------------------------
+GATHER_OPS = dict(fwd=0, bwd_x=1, bwd_geom=2, bwd_x_grid=3, fwd_def=4, bwd_x_def=5, bwd_x_grid_wide=6, bwd_geom_def=7)
+
+
+def parse_launch(text):
+    """'kernel<A=1, B=x> k=v ...' -> (kernel, {template argument: value}, {key: int})"""
+    kernel, _, rest = text.partition("<")
+    targs, _, keys = rest.partition(">")
+    args = dict(a.strip().split("=") for a in targs.split(","))
+    return kernel, args, {k: int(v) for k, v in (kv.split("=") for kv in keys.split())}
+
+
+def report(op, nq, ns, ci, rows_a, rows_b, dtype="f32", deformed=False, modulated=False, influence="linear", aggregation="sum",
+           rows_sorted=False, ordered=False):
+    """parse_launch of the reporter's answer for one entry; rows_a / rows_b are addresses (only their alignment counts)"""
+    from weasal_amd import _lib, ops
+    buf = C.create_string_buffer(256)
+    _lib.check(_lib.lib().ws_kpconv_gather_variant(GATHER_OPS[op], nq, ns, ci, rows_a, rows_b, int(deformed), int(modulated),
+                                                   ops.INFLUENCE[influence], ops.AGGREGATION[aggregation], int(dtype == "bf16"),
+                                                   int(rows_sorted), int(ordered), buf, 256))
+    return parse_launch(buf.value.decode())
+
+
+def fake_ptr(name, off=0, es=4):
+    """the addresses the GPU run sees, alignment-wise: every allocation at least 256-byte aligned"""
+    return 0x10000000 * (1 + ("x", "wf", "dwf", "dx").index(name)) + off * es
+
+
+def table_launch(kernel, targs):
+    """a (kernel, template arguments) pair of the table in parse_launch form (K6 carries its vec4 argument in the text)"""
+    targs, _, vec4 = targs.partition(" (vec4=")
+    return (kernel, dict(a.strip().split("=") for a in targs.split(",")), {"vec4": int(vec4[0])} if vec4 else {})
+
+
+def check_row_plan(row, ptr, nq, ns):
+    """the reporter names what the row says it launches: forward kernel, template arguments and csplit; K4 and K6 where the row
+    runs them.  ptr(name) -> address of x / wf / dwf / dx; -> the number of launches checked"""
+    kw = dict(dtype=row["dtype"], deformed=row["deform"] is not None, modulated=row["deform"] == "defmod",
+              influence=row["influence"], aggregation=row["aggregation"])
+    kernel, args, keys = report("fwd", nq, ns, row["ci"], ptr("x"), ptr("wf"), rows_sorted=row["rows_sorted"], ordered=row["order"], **kw)
+    want = table_launch(row["kernel"], row["targs"])
+    assert (kernel, args) == want[:2] and keys["csplit"] == row["csplit"], (row["id"], kernel, args, keys)
+    checked = 1
+    for key, op, a, b in (("bwd", "bwd_x", "dwf", "dx"), ("geom", "bwd_geom", "x", "dwf")):
+        if row[key]:
+            kernel, args, keys = report(op, nq, ns, row["ci"], ptr(a), ptr(b), ordered=row["order"], **kw)
+            want = table_launch(*row[key])
+            assert (kernel, args) == want[:2] and all(keys[k] == v for k, v in want[2].items()), (row["id"], key, kernel, args, keys)
+            checked += 1
+    return checked
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -280,12 +359,22 @@ def _gpu_x(x, dtype, view, gpu):
     return t
 
 
+def _check_plan_on_device(row, X, Q, S, dwf, gpu):
+    """check_row_plan with the device pointers of this run: x as passed, wf / dx as ops allocates them (torch.empty /
+    empty_like), dwf as the contiguous gradient autograd hands over"""
+    bufs = dict(x=X, wf=torch.empty((Q.shape[0], K, row["ci"]), dtype=X.dtype, device=gpu), dx=torch.empty_like(X))
+    if dwf is not None:
+        bufs["dwf"] = torch.from_numpy(dwf).to(gpu).to(X.dtype)
+    check_row_plan(row, lambda name: bufs[name].data_ptr(), Q.shape[0], S.shape[0])
+
+
 def _run(row, d, gpu, dwf=None, dmin=None):
     from weasal_amd import ops
     Q = torch.from_numpy(d["q"]).to(gpu)
     S = Q if row["queries"] == "self" else torch.from_numpy(d["s"]).to(gpu)
     inds = torch.from_numpy(d["inds"]).to(gpu)
     X = _gpu_x(d["x"], row["dtype"], row["view"], gpu)
+    _check_plan_on_device(row, X, Q, S, dwf, gpu)
     if dwf is not None:
         X = X.detach().requires_grad_(True)
     kw = {}
@@ -382,6 +471,7 @@ def _run_with_points(row, d, gpu, Q, S, dwf, dmin):
     from weasal_amd import ops
     inds = torch.from_numpy(d["inds"]).to(gpu)
     X = _gpu_x(d["x"], row["dtype"], row["view"], gpu)
+    _check_plan_on_device(row, X, Q, S, dwf, gpu)
     if dwf is not None:
         X = X.detach().requires_grad_(True)
     wf, _ = ops.kpconv_gather(X, Q, S, inds, torch.from_numpy(d["kp"]).to(gpu), EXTENT, row["influence"], row["aggregation"])
@@ -452,10 +542,22 @@ def _grid_case(gpu, batch, cfg, lvl, ci, variant, bf, wide):
         kw = dict(influence="gaussian", aggregation="closest")
     dt = torch.bfloat16 if bf else torch.float32
     dwf = torch.randn(p.shape[0], 15, ci, device=gpu, generator=gen).to(dt)
+    ordered = ops._order_for(p) is not None
+    dx_like = torch.empty(p.shape[0], ci, device=gpu, dtype=dt)
+
+    def asked(sort):
+        kernel, args, keys = report("bwd_x_grid_wide" if wide else "bwd_x_grid", p.shape[0], p.shape[0], ci, dwf.data_ptr(),
+                                    dx_like.data_ptr(), dtype="bf16" if bf else "f32", deformed=variant == "deformable",
+                                    modulated=variant == "deformable", influence=kw.get("influence", "linear"),
+                                    aggregation=kw.get("aggregation", "sum"), ordered=ordered)
+        want = grid_plan(ci, variant, "bf16" if bf else "f32", wide, sort, ordered)
+        assert (kernel, args, keys["ilv"]) == (want[0], table_launch(*want[:2])[1], want[2]), (kernel, args, keys)
     try:
         sorted_switch.value = 1
+        asked(True)
         idx_order = _grid_dx(p, inds, dwf, kp, extent, kw, True, dt)
         sorted_switch.value = 0
+        asked(False)
         walk = _grid_dx(p, inds, dwf, kp, extent, kw, True, dt)
         table = _grid_dx(p, inds, dwf, kp, extent, kw, False, dt)
         mag = _grid_dx(p, inds, dwf.abs(), kp, extent, kw, False, dt)

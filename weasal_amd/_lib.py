@@ -153,6 +153,7 @@ SIGNATURES = {
     "ws_kpconv_layer_fwd_fused": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _f32, _vp, _vp, _i32, _vp, _i32, _f32,
                                            _vp, _vp]),
     "ws_kpconv_gather_fwd_variant": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.c_char_p, _i32]),
+    "ws_kpconv_gather_variant": (C.c_int, [_i32, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_char_p, _i32]),
     "ws_gemm_xb_variant": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                                      _vp, _i64, C.c_char_p, _i32]),
     "ws_gemm_xty_variant": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _i64, _vp, _i64, _vp, _i32, C.c_char_p, _i32]),

@@ -2125,394 +2125,317 @@ __global__ __launch_bounds__(256) void kpconv_gather_bwd_x_gridw_kernel(
 extern "C" int ws_kpconv_grid_sorted;     // 1: ws_kpconv_gather_bwd_x_grid sums the incoming pairs in index order (the pair order of
 int ws_kpconv_grid_sorted = 0;            //    the transposed table: bit-identical to ws_kpconv_gather_bwd_x); 0: in grid-walk order
 
+#include <cstdio>
+#include <type_traits>
+
 namespace {
 
 constexpr int SPLIT_ROWS = 4096;   // matrix-core K3 on fewer queries than this: one item per (query, channel block)
 constexpr int SPLIT_NT = 4;        // ... with at most this many channels per lane (blocks of 16 x this many channels)
 constexpr int GRID_INTERLEAVE = 512;   // K4G and the wide-row K4G of config 5: workgroups per XCD of the interleaved assignment
 
-template <typename T>
-int gather_fwd_impl(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
-                    const int64_t* inds, int32_t h, const T* x, int32_t ci,
-                    const float* kernel_points, int32_t k, const float* deformed_kp,
-                    const float* modulations, float extent, int32_t influence, int32_t aggregation,
-                    const int32_t* order, T* wf, float* min_d2, void* stream, int rows_sorted = 0)
+// ---- plans: what a launcher launches, from its arguments alone (pointers only for their alignment).  The launchers below and the
+//      reporters (ws_kpconv_gather_variant, ws_kpconv_gather_fwd_variant) call the same plan function; every selection rule is here.
+enum { GK_FWD_MFMA, GK_FWD_POOL, GK_BWD_X, GK_BWD_GEOM, GK_BWD_X_GRID, GK_BWD_X_GRIDW, GK_BWD_GEOM_DEF };
+struct GatherPlan {
+    int kernel;         // GK_*: the kernel family
+    bool bf16;          // row type T: bf16_t instead of float
+    int n;              // NT (GK_FWD_MFMA), CK (GK_BWD_GEOM_DEF), G (the others; GK_BWD_GEOM has none)
+    int mode;           // MODE
+    bool def;           // DEF (the forward kernels)
+    bool vec;           // VEC: float4 / 4 x bf16 row pieces (GK_FWD_MFMA: VECROW, always true; GK_BWD_GEOM: the argument vec4)
+    int pw;             // PW (GK_FWD_POOL)
+    bool cut;           // CUT (GK_FWD_MFMA, GK_BWD_GEOM_DEF)
+    int nch;            // NCH (GK_BWD_X_GRIDW)
+    bool sort;          // SORT (GK_BWD_X_GRID)
+    bool areg;          // AREG (GK_BWD_GEOM_DEF)
+    int grid;           // workgroups of 256 threads
+    int csplit, ilv, rows_sorted;   // GeomParams::csplit (1 = a query is one item), ::ilv, ::cut
+};
+
+// NT of the matrix-core K3: channels per lane, from the row width; one channel per lane (any ci, any alignment: lanes past ci
+// are masked) unless the rows split into NT-channel pieces
+int nt_for_rows(int ci, const void* a, const void* b)
 {
-    constexpr bool F32 = sizeof(T) == 4;
-    int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, influence, aggregation);
-    if (rc) return rc;
-    if (nq == 0) return WS_OK;
-    WS_REQUIRE(inds && x && wf && (kernel_points || deformed_kp), "NULL argument");
-    GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, nullptr, 0.0f, nullptr, 0, nullptr, nullptr,
-                 rows_sorted ? 1 : 0};
-    hipStream_t st = (hipStream_t)stream;
-    int grid = ws_grid(nq, 4);
-    WS_REQUIRE(ns * (int64_t)ci < (1ll << 31), "ns*ci exceeds the 32-bit row offsets of the gather");
-    const int vec4 = (ci % 4 == 0) && ws_row_aligned<T>(x) && ws_row_aligned<T>(wf);
-    WS_REQUIRE(F32 || vec4, "bf16 feature rows need ci %% 4 == 0 and 8-byte aligned rows (ci=%d)", ci);
+    const int nt = ci <= 16 ? 1 : (ci <= 32 ? 2 : (ci <= 64 ? 4 : (ci <= 128 ? 8 : 16)));
+    return (ci % nt == 0 && (nt == 1 || (aligned16(a) && aligned16(b)))) ? nt : 1;
+}
+// G of K4 / K4G: groups of 4 channels per support
+int group_ladder(int ci) { return ci <= 4 ? 1 : (ci <= 8 ? 2 : (ci <= 16 ? 4 : (ci <= 32 ? 8 : 16))); }
+// VEC: both row sets move as float4 / 4 x bf16 pieces
+bool rows_vec4(bool bf16, int ci, const void* a, const void* b)
+{
+    return ci % 4 == 0 && (bf16 ? ws_row_aligned<bf16_t>(a) && ws_row_aligned<bf16_t>(b) : ws_row_aligned<float>(a) && ws_row_aligned<float>(b));
+}
+// ... and bf16 rows have no other form (VEC = false is not instantiated for them)
+int rows_vec4_or_f32(bool bf16, int ci, const void* a, const void* b, bool& vec4)
+{
+    vec4 = rows_vec4(bf16, ci, a, b);
+    WS_REQUIRE(!bf16 || vec4, "bf16 feature rows need ci %% 4 == 0 and 8-byte aligned rows (ci=%d)", ci);
+    return WS_OK;
+}
+// MODE 0 of the generic entries: rigid, not modulated, linear influence, sum
+bool rigid_fast(bool deformed, bool modulated, int influence, int aggregation)
+{
+    return !deformed && !modulated && influence == WS_INFLUENCE_LINEAR && aggregation == WS_AGGREGATION_SUM;
+}
+// K4G: with a point order the supports are dealt out interleaved, GRID_INTERLEAVE workgroups per XCD
+void grid_walk_plan(int64_t ns, bool ordered, GatherPlan& p)
+{
+    p.ilv = ordered ? GRID_INTERLEAVE : 0;
+    p.grid = p.ilv > 0 ? 8 * (int)std::max<int64_t>(1, std::min<int64_t>(p.ilv, ws_ceil_div(ns, 32))) : ws_grid(ns, 4);
+}
+
+GatherPlan new_plan(int kernel, bool bf16, int64_t items)
+{
+    GatherPlan p{};
+    p.kernel = kernel; p.bf16 = bf16; p.csplit = 1; p.grid = ws_grid(items, 4);
+    return p;
+}
+
+// ws_kpconv_gather_fwd / _bf16 / _ex
+int fwd_plan(bool bf16, int64_t nq, int32_t ci, const void* x, const void* wf, bool deformed, bool modulated, int32_t influence,
+             int32_t aggregation, bool rows_sorted, GatherPlan& p)
+{
+    p = new_plan(ci > 4 ? GK_FWD_MFMA : GK_FWD_POOL, bf16, nq);
+    p.def = deformed; p.rows_sorted = rows_sorted;
+    if (int rc = rows_vec4_or_f32(bf16, ci, x, wf, p.vec)) return rc;
     if (ci > 4) {      // (the 3..4-channel input layer: the narrow-row pool form is 10 % faster)
         // matrix-core form (kpconv_gather_fwd_mfma_kernel): NT consecutive channels per lane, 16 NT channels per block
-        const bool fastm = !deformed_kp && !modulations && influence == WS_INFLUENCE_LINEAR && aggregation == WS_AGGREGATION_SUM;
-        int nt = ci <= 16 ? 1 : (ci <= 32 ? 2 : (ci <= 64 ? 4 : (ci <= 128 ? 8 : 16)));
-        const bool al16 = aligned16(x) && aligned16(wf);
-        bool vecrow = (ci % nt == 0) && (nt == 1 || al16);
-        if (!vecrow) nt = 1;
-        if (nt == 1) vecrow = true;       // one channel per lane: any ci, any alignment (lanes past ci are masked)
-        if (fastm && !rows_sorted && nq < SPLIT_ROWS && vecrow && nt > SPLIT_NT && ci % SPLIT_NT == 0)
-            nt = SPLIT_NT;                                        // narrower blocks: more items per query
-        if (fastm && !rows_sorted && nq < SPLIT_ROWS && ci > 16 * nt) {
-            g.csplit = (ci + 16 * nt - 1) / (16 * nt);           // one channel block per item
-            grid = ws_grid(nq * g.csplit, 4);
+        const bool fastm = rigid_fast(deformed, modulated, influence, aggregation);
+        p.n = nt_for_rows(ci, x, wf);
+        p.mode = fastm ? 0 : 1; p.vec = true; p.cut = fastm && rows_sorted;
+        if (fastm && !rows_sorted && nq < SPLIT_ROWS) {
+            if (p.n > SPLIT_NT && ci % SPLIT_NT == 0) p.n = SPLIT_NT;       // narrower blocks: more items per query
+            if (ci > 16 * p.n) {
+                p.csplit = (ci + 16 * p.n - 1) / (16 * p.n);               // one channel block per item
+                p.grid = ws_grid(nq * p.csplit, 4);
+            }
         }
-#define WS_FWDM2(NTV, MODEV, DEFV)                                                                                  \
-    kpconv_gather_fwd_mfma_kernel<NTV, MODEV, DEFV, true, T><<<grid, 256, 0, st>>>(q_pts, nq, s_pts, ns, inds, h, x, ci, \
-                                                                                   kernel_points, deformed_kp, modulations, g, wf, min_d2, order)
-#define WS_FWDM(NTV)                                    \
-    do {                                                \
-        if (deformed_kp) WS_FWDM2(NTV, 1, true);        \
-        else if (fastm && rows_sorted)                  \
-            kpconv_gather_fwd_mfma_kernel<NTV, 0, false, true, T, 0, true><<<grid, 256, 0, st>>>(                      \
-                q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, deformed_kp, modulations, g, wf, min_d2, order);  \
-        else if (fastm) WS_FWDM2(NTV, 0, false);        \
-        else WS_FWDM2(NTV, 1, false);                   \
-    } while (0)
-        if (nt == 1) WS_FWDM(1);
-        else if (nt == 2) WS_FWDM(2);
-        else if (nt == 4) WS_FWDM(4);
-        else if (nt == 8) WS_FWDM(8);
-        else WS_FWDM(16);
-#undef WS_FWDM
-#undef WS_FWDM2
-        WS_LAUNCH_CHECK();
         return WS_OK;
     }
-    // the 3..4-channel input layer: entry pool + VALU accumulate (kpconv_gather_fwd_kernel)
-#define WS_FWDV(G, MODEV, DEFV, VECV, PW)                                                                             \
-    kpconv_gather_fwd_kernel<15, G, MODEV, DEFV, VECV, PW, T><<<grid, 256, 0, st>>>(                                  \
-        q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, deformed_kp, modulations, g, wf, min_d2, order)
-    const bool fast = influence == WS_INFLUENCE_LINEAR && aggregation == WS_AGGREGATION_SUM;
-    if (vec4) {
-        if (deformed_kp) WS_FWDV(1, 1, true, true, 4);
-        else if (fast) WS_FWDV(1, 0, false, true, 4);
-        else WS_FWDV(1, 1, false, true, 4);
-    } else if constexpr (F32) {
-        // narrow rows that are not float4 (the 3-channel input layer): 4-byte pieces, 16 slots of 4 lanes
-        if (deformed_kp) WS_FWDV(4, 1, true, false, 1);
-        else if (fast) WS_FWDV(4, 0, false, false, 1);
-        else WS_FWDV(4, 1, false, false, 1);
-    }
-#undef WS_FWDV
-    WS_LAUNCH_CHECK();
+    // the 3..4-channel input layer: entry pool + VALU accumulate (kpconv_gather_fwd_kernel); rows that are not float4 (the
+    // 3-channel input layer) in 4-byte pieces, 16 slots of 4 lanes
+    p.mode = (!deformed && influence == WS_INFLUENCE_LINEAR && aggregation == WS_AGGREGATION_SUM) ? 0 : 1;
+    p.n = p.vec ? 1 : 4; p.pw = p.vec ? 4 : 1;
     return WS_OK;
 }
 
-template <typename T>
-int gather_bwd_x_impl(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
-                      const int64_t* inds, int32_t h, const int32_t* t_offsets, const int32_t* t_pairs,
-                      const T* dwf, int32_t ci, const float* kernel_points, int32_t k,
-                      const float* deformed_kp, const float* modulations, float extent,
-                      int32_t influence, int32_t aggregation, const int32_t* order, T* dx, void* stream,
-                      const T* gate = nullptr, float gate_slope = 0.0f)
+// ws_kpconv_gather_fwd_def: no narrowing, no csplit; bf16 rows move in pairs at least
+int fwd_def_plan(bool bf16, int64_t nq, int32_t ci, const void* x, const void* wf, bool rows_sorted, GatherPlan& p)
 {
-    constexpr bool F32 = sizeof(T) == 4;
-    (void)inds;
-    int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, influence, aggregation);
-    if (rc) return rc;
+    p = new_plan(GK_FWD_MFMA, bf16, nq);
+    p.n = nt_for_rows(ci, x, wf);
+    p.mode = 2; p.def = true; p.vec = true; p.cut = rows_sorted;
+    if (bf16 && p.n == 1 && (ci % 2)) return ws_fail(WS_ERR_UNSUPPORTED, "bf16 rows need an even channel count (ci=%d)", ci);
+    return WS_OK;
+}
+
+// ws_kpconv_gather_bwd_x / _bf16 / _gated (mode 0 = rigid_fast, else 1) and ws_kpconv_gather_bwd_x_def (mode 2)
+int bwd_x_plan(bool bf16, int64_t ns, int32_t ci, const void* dwf, const void* dx, int mode, GatherPlan& p)
+{
+    p = new_plan(GK_BWD_X, bf16, ns);
+    p.n = group_ladder(ci); p.mode = mode;
+    return rows_vec4_or_f32(bf16, ci, dwf, dx, p.vec);
+}
+
+// ws_kpconv_gather_bwd_geom / _bf16
+int bwd_geom_plan(bool bf16, int64_t nq, int32_t ci, const void* x, const void* dwf, GatherPlan& p)
+{
+    p = new_plan(GK_BWD_GEOM, bf16, nq);
+    p.mode = 1; p.vec = rows_vec4(bf16, ci, x, dwf);
+    return WS_OK;
+}
+
+// ws_kpconv_gather_bwd_x_grid / _bf16 / _gated (mode 0 = rigid_fast, else 1)
+int bwd_x_grid_plan(bool bf16, int64_t ns, int32_t ci, const void* dwf, const void* dx, int mode, bool ordered, GatherPlan& p)
+{
+    p = new_plan(GK_BWD_X_GRID, bf16, ns);
+    p.n = group_ladder(ci); p.mode = mode; p.sort = ws_kpconv_grid_sorted != 0;
+    grid_walk_plan(ns, ordered, p);
+    return rows_vec4_or_f32(bf16, ci, dwf, dx, p.vec);
+}
+
+// ws_kpconv_gather_bwd_x_grid_wide: rigid (MODE 0) or the deformable fast path (MODE 2); NCH 64-channel chunks per item, G = 16 only
+int bwd_x_gridw_plan(bool bf16, int64_t ns, int32_t ci, const void* dwf, const void* dx, bool deformed, bool ordered, GatherPlan& p)
+{
+    p = new_plan(GK_BWD_X_GRIDW, bf16, ns);
+    p.n = group_ladder(ci); p.mode = deformed ? 2 : 0;
+    p.nch = (p.n < 16 || ci <= 64) ? 1 : (ci <= 128 ? 2 : 4);
+    grid_walk_plan(ns, ordered, p);
+    return rows_vec4_or_f32(bf16, ci, dwf, dx, p.vec);
+}
+
+// ws_kpconv_gather_bwd_geom_def: CK 4-channel pieces per lane; up to 128 channels the accumulators stay in registers (AREG)
+int bwd_geom_def_plan(bool bf16, int64_t nq, int32_t ci, const void* x, const void* dwf, bool rows_sorted, GatherPlan& p)
+{
+    p = new_plan(GK_BWD_GEOM_DEF, bf16, nq);
+    if (ci % 16 != 0 || !aligned16(x) || !aligned16(dwf))
+        return ws_fail(WS_ERR_UNSUPPORTED, "geometry backward on the matrix core needs ci %% 16 == 0 and 16-byte aligned rows (ci=%d)", ci);
+    p.mode = 2; p.vec = true; p.cut = rows_sorted;
+    p.areg = ci == 16 || ci == 32 || ci == 64 || ci == 128;
+    p.n = p.areg ? ci / 4 : (ci % 128 == 0 ? 32 : (ci % 64 == 0 ? 16 : (ci % 32 == 0 ? 8 : 4)));
+    return WS_OK;
+}
+
+// "kernel<template arguments> key=value ..." of a plan
+void plan_text(const GatherPlan& p, char* out, size_t n)
+{
+    const char* t = p.bf16 ? "bf16" : "float";
+    auto b = [](bool v) { return v ? "true" : "false"; };
+    switch (p.kernel) {
+    case GK_FWD_MFMA:
+        snprintf(out, n, "kpconv_gather_fwd_mfma_kernel<NT=%d, MODE=%d, DEF=%s, VECROW=%s, T=%s, CUT=%s> grid=%d csplit=%d", p.n, p.mode,
+                 b(p.def), b(p.vec), t, b(p.cut), p.grid, p.csplit);
+        break;
+    case GK_FWD_POOL:
+        snprintf(out, n, "kpconv_gather_fwd_kernel<K=15, G=%d, MODE=%d, DEF=%s, VEC=%s, PW=%d, T=%s> grid=%d csplit=%d cut=%d", p.n, p.mode,
+                 b(p.def), b(p.vec), p.pw, t, p.grid, p.csplit, p.rows_sorted);
+        break;
+    case GK_BWD_X:
+        snprintf(out, n, "kpconv_gather_bwd_x_kernel<K=15, G=%d, MODE=%d, VEC=%s, T=%s> grid=%d", p.n, p.mode, b(p.vec), t, p.grid);
+        break;
+    case GK_BWD_GEOM:
+        snprintf(out, n, "kpconv_gather_bwd_geom_kernel<K=15, T=%s> grid=%d vec4=%d", t, p.grid, p.vec ? 1 : 0);
+        break;
+    case GK_BWD_X_GRID:
+        snprintf(out, n, "kpconv_gather_bwd_x_grid_kernel<K=15, G=%d, MODE=%d, VEC=%s, T=%s, SORT=%s> grid=%d ilv=%d", p.n, p.mode, b(p.vec),
+                 t, b(p.sort), p.grid, p.ilv);
+        break;
+    case GK_BWD_X_GRIDW:
+        snprintf(out, n, "kpconv_gather_bwd_x_gridw_kernel<K=15, G=%d, MODE=%d, VEC=%s, NCH=%d, T=%s> grid=%d ilv=%d", p.n, p.mode,
+                 b(p.vec), p.nch, t, p.grid, p.ilv);
+        break;
+    default:
+        snprintf(out, n, "kpconv_gather_bwd_geom_def_kernel<CK=%d, AREG=%s, T=%s, CUT=%s> grid=%d", p.n, b(p.areg), t, b(p.cut), p.grid);
+    }
+}
+
+// ---- dispatch: a plan's runtime values onto template arguments.  dispatch(f, Pick<1, 2, 4>{v}, ...) calls f with one
+//      std::integral_constant per Pick: the value of its list that equals v (none: f is not called).  What a kernel family does not
+//      instantiate is pruned with if constexpr at the launch.  The row type is one more Pick: Flag{p.bf16} -> Row<bf>.
+template <int... Vs> struct Pick { int v; };
+using Flag = Pick<0, 1>;
+template <typename F> void dispatch(F&& f) { f(); }
+template <typename F, int... Vs, typename... Rest>
+void dispatch(F&& f, Pick<Vs...> a, Rest... rest)
+{
+    (void)(((a.v == Vs) && (dispatch([&](auto... cs) { f(std::integral_constant<int, Vs>{}, cs...); }, rest...), true)) || ...);
+}
+template <int BF> using Row = std::conditional_t<BF != 0, bf16_t, float>;
+int launched() { WS_LAUNCH_CHECK(); return WS_OK; }      // the end of every launcher
+
+// the grid blob of the search (ws_grid.h) as K4G reads it
+struct GridView {
+    const CloudGrid* grids;
+    const int32_t* cell_start;
+    const float4* sorted;
+    const unsigned long long* key_last;
+    float r2;
+};
+GridView grid_view(const void* grid_blob, int32_t nb, int64_t cells, const uint64_t* key_last, float radius)
+{
+    const char* base = (const char*)grid_blob;
+    return GridView{(const CloudGrid*)base, (const int32_t*)(base + ws_grid_blob_cells_off(nb)),
+                    (const float4*)(base + ws_grid_blob_sorted_off(nb, cells)), reinterpret_cast<const unsigned long long*>(key_last),
+                    radius * radius};                       // neighbors.cpp:226, as in the search
+}
+
+// ---- launchers: validate, plan, one dispatch on the plan ---------------------------------------------------------------
+// kpconv_gather_fwd_mfma_kernel for ws_kpconv_gather_fwd* (MODE 0 / 1) and ws_kpconv_gather_fwd_def (MODE 2).  MODE 0 is rigid and
+// MODE 2 deformable, only MODE 1 takes either; CUT exists for MODE 0 and 2; VECROW = false stays uninstantiated.
+void launch_fwd_mfma(const GatherPlan& p, void* stream, const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int64_t* inds,
+                     int32_t h, const void* x, int32_t ci, const float* kernel_points, const float* deformed_kp, const float* modulations,
+                     const GeomParams& g, void* wf, float* min_d2, const int32_t* order)
+{
+    dispatch([&](auto bf, auto nt, auto mode, auto def, auto cut) {
+        using T = Row<bf.value>;
+        if constexpr (mode.value == 1 ? !cut.value : def.value == (mode.value == 2))
+            kpconv_gather_fwd_mfma_kernel<nt.value, mode.value, def.value != 0, true, T, 0, cut.value != 0><<<p.grid, 256, 0, (hipStream_t)stream>>>(
+                q_pts, nq, s_pts, ns, inds, h, (const T*)x, ci, kernel_points, deformed_kp, modulations, g, (T*)wf, min_d2, order);
+    }, Flag{p.bf16}, Pick<1, 2, 4, 8, 16>{p.n}, Pick<0, 1, 2>{p.mode}, Flag{p.def}, Flag{p.cut});
+}
+
+// kpconv_gather_bwd_x_kernel for ws_kpconv_gather_bwd_x* (MODE 0 / 1) and ws_kpconv_gather_bwd_x_def (MODE 2); bf16 rows are VEC only
+void launch_bwd_x(const GatherPlan& p, void* stream, const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, int32_t h,
+                  const int32_t* t_offsets, const int32_t* t_pairs, const void* dwf, int32_t ci, const float* kernel_points,
+                  const float* deformed_kp, const float* modulations, const GeomParams& g, void* dx, const int32_t* order)
+{
+    dispatch([&](auto bf, auto gr, auto mode, auto vec) {
+        using T = Row<bf.value>;
+        if constexpr (!bf.value || vec.value)
+            kpconv_gather_bwd_x_kernel<15, gr.value, mode.value, vec.value != 0, T><<<p.grid, 256, 0, (hipStream_t)stream>>>(
+                q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, (const T*)dwf, ci, kernel_points, deformed_kp, modulations, g, (T*)dx, order);
+    }, Flag{p.bf16}, Pick<1, 2, 4, 8, 16>{p.n}, Pick<0, 1, 2>{p.mode}, Flag{p.vec});
+}
+
+int gather_bwd_x_impl(bool bf16, const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, int32_t h, const int32_t* t_offsets,
+                      const int32_t* t_pairs, const void* dwf, int32_t ci, const float* kernel_points, int32_t k, const float* deformed_kp,
+                      const float* modulations, float extent, int32_t influence, int32_t aggregation, const int32_t* order, void* dx,
+                      void* stream, const void* gate = nullptr, float gate_slope = 0.0f)
+{
+    if (int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, influence, aggregation)) return rc;
     if (ns == 0) return WS_OK;
     WS_REQUIRE(t_offsets && t_pairs && dwf && dx && (kernel_points || deformed_kp), "NULL argument");
     WS_REQUIRE(nq * (int64_t)h < (1ll << 31), "nq*h exceeds int32");
     WS_REQUIRE(nq * (int64_t)k * ci < (1ll << 31), "nq*k*ci exceeds the 32-bit row offsets of the gather");
+    GatherPlan p;
+    if (int rc = bwd_x_plan(bf16, ns, ci, dwf, dx, rigid_fast(deformed_kp, modulations, influence, aggregation) ? 0 : 1, p)) return rc;
     GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, gate, gate_slope, nullptr, 0};
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = ws_grid(ns, 4);
-    const int vec4 = (ci % 4 == 0) && ws_row_aligned<T>(dwf) && ws_row_aligned<T>(dx);
-    WS_REQUIRE(F32 || vec4, "bf16 feature rows need ci %% 4 == 0 and 8-byte aligned rows (ci=%d)", ci);
-#define WS_BWD2(G, MODEV, VECV)                                                                                       \
-    do {                                                                                                              \
-        if constexpr (F32 || VECV)                                                                                    \
-            kpconv_gather_bwd_x_kernel<15, G, MODEV, VECV, T><<<grid, 256, 0, st>>>(                                   \
-                q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, dwf, ci, kernel_points, deformed_kp, modulations, g, dx, order); \
-    } while (0)
-#define WS_BWD(G)                                                                       \
-    do {                                                                                \
-        if (fast) { if (vec4) WS_BWD2(G, 0, true); else WS_BWD2(G, 0, false); }          \
-        else { if (vec4) WS_BWD2(G, 1, true); else WS_BWD2(G, 1, false); }               \
-    } while (0)
-    const bool fast = !deformed_kp && !modulations && influence == WS_INFLUENCE_LINEAR && aggregation == WS_AGGREGATION_SUM;
-    if (ci <= 4) WS_BWD(1);
-    else if (ci <= 8) WS_BWD(2);
-    else if (ci <= 16) WS_BWD(4);
-    else if (ci <= 32) WS_BWD(8);
-    else WS_BWD(16);
-#undef WS_BWD2
-#undef WS_BWD
-    WS_LAUNCH_CHECK();
-    return WS_OK;
+    launch_bwd_x(p, stream, q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, dwf, ci, kernel_points, deformed_kp, modulations, g, dx, order);
+    return launched();
 }
 
-template <typename T>
-int gather_bwd_geom_impl(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
-                         const int64_t* inds, int32_t h, const T* x, int32_t ci, const T* dwf,
-                         const float* kernel_points, int32_t k, const float* deformed_kp,
-                         const float* modulations, const float* d_min_d2, float extent,
-                         int32_t influence, int32_t aggregation, float* d_deformed_kp,
+int gather_bwd_geom_impl(bool bf16, const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int64_t* inds, int32_t h,
+                         const void* x, int32_t ci, const void* dwf, int32_t k, const float* deformed_kp, const float* modulations,
+                         const float* d_min_d2, float extent, int32_t influence, int32_t aggregation, float* d_deformed_kp,
                          float* d_modulations, void* stream)
 {
-    (void)kernel_points;
-    int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, influence, aggregation);
-    if (rc) return rc;
+    if (int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, influence, aggregation)) return rc;
     if (nq == 0) return WS_OK;
     WS_REQUIRE(inds && x && dwf && deformed_kp && d_deformed_kp, "NULL argument");
+    GatherPlan p;
+    if (int rc = bwd_geom_plan(bf16, nq, ci, x, dwf, p)) return rc;
     GeomParams g{extent, influence, aggregation, 1, nullptr, 0.0f, nullptr, 0};
-    hipStream_t st = (hipStream_t)stream;
-    kpconv_gather_bwd_geom_kernel<15, T><<<ws_grid(nq, 4), 256, 0, st>>>(q_pts, nq, s_pts, ns, inds, h, x, ci, dwf,
-                                                                          deformed_kp, modulations, d_min_d2, g,
-                                                                          d_deformed_kp, d_modulations,
-                                                                          (ci % 4 == 0) && ws_row_aligned<T>(x) && ws_row_aligned<T>(dwf));
-    WS_LAUNCH_CHECK();
-    return WS_OK;
+    dispatch([&](auto bf) {
+        using T = Row<bf.value>;
+        kpconv_gather_bwd_geom_kernel<15, T><<<p.grid, 256, 0, (hipStream_t)stream>>>(
+            q_pts, nq, s_pts, ns, inds, h, (const T*)x, ci, (const T*)dwf, deformed_kp, modulations, d_min_d2, g, d_deformed_kp, d_modulations,
+            p.vec);
+    }, Flag{p.bf16});
+    return launched();
 }
 
-template <typename T>
-int gather_bwd_x_grid_impl(const float* s_pts, int64_t ns, const void* grid_blob, int32_t nb, int64_t cells,
-                           const uint64_t* key_last, float radius, const T* dwf, int32_t ci,
-                           const float* kernel_points, int32_t k, const float* deformed_kp, const float* modulations,
-                           float extent, int32_t influence, int32_t aggregation, const int32_t* order, T* dx,
-                           int32_t* overflow, void* stream, const T* gate = nullptr, float gate_slope = 0.0f,
-                           const int64_t* rows = nullptr, int32_t rows_h = 0)
+int gather_bwd_x_grid_impl(bool bf16, const float* s_pts, int64_t ns, const void* grid_blob, int32_t nb, int64_t cells,
+                           const uint64_t* key_last, float radius, const void* dwf, int32_t ci, const float* kernel_points, int32_t k,
+                           const float* deformed_kp, const float* modulations, float extent, int32_t influence, int32_t aggregation,
+                           const int32_t* order, void* dx, int32_t* overflow, void* stream, const void* gate = nullptr,
+                           float gate_slope = 0.0f, const int64_t* rows = nullptr, int32_t rows_h = 0)
 {
-    constexpr bool F32 = sizeof(T) == 4;
-    int rc = check_common(s_pts, ns, s_pts, ns, 1, ci, k, extent, influence, aggregation);
-    if (rc) return rc;
+    if (int rc = check_common(s_pts, ns, s_pts, ns, 1, ci, k, extent, influence, aggregation)) return rc;
     if (ns == 0) return WS_OK;
     WS_REQUIRE(grid_blob && key_last && dwf && dx && overflow && (kernel_points || deformed_kp), "NULL argument");
     WS_REQUIRE(nb >= 1 && cells >= 1, "bad grid nb=%d cells=%lld", nb, (long long)cells);
     WS_REQUIRE(ns * (int64_t)k * ci < (1ll << 31), "ns*k*ci exceeds the 32-bit row offsets of the gather");
     WS_REQUIRE(!rows || rows_h >= 1, "index rows given without their width");
-    GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, gate, gate_slope, rows, rows_h};
-    hipStream_t st = (hipStream_t)stream;
-    const char* base = (const char*)grid_blob;
-    const CloudGrid* grids = (const CloudGrid*)base;
-    const int32_t* cell_start = (const int32_t*)(base + ws_grid_blob_cells_off(nb));
-    const float4* sorted = (const float4*)(base + ws_grid_blob_sorted_off(nb, cells));
-    const float r2 = radius * radius;                       // neighbors.cpp:226, as in the search
-    const unsigned long long* kl = reinterpret_cast<const unsigned long long*>(key_last);
-    g.ilv = order ? GRID_INTERLEAVE : 0;
-    const int grid = g.ilv > 0 ? 8 * (int)std::max<int64_t>(1, std::min<int64_t>(g.ilv, ws_ceil_div(ns, 32))) : ws_grid(ns, 4);
-    const int vec4 = (ci % 4 == 0) && ws_row_aligned<T>(dwf) && ws_row_aligned<T>(dx);
-    WS_REQUIRE(F32 || vec4, "bf16 feature rows need ci %% 4 == 0 and 8-byte aligned rows (ci=%d)", ci);
-#define WS_BWDG2(G, MODEV, VECV)                                                                                     \
-    do {                                                                                                             \
-        if constexpr (F32 || VECV) {                                                                                 \
-            if (ws_kpconv_grid_sorted)                                                                               \
-                kpconv_gather_bwd_x_grid_kernel<15, G, MODEV, VECV, T, true><<<grid, 256, 0, st>>>(                   \
-                    s_pts, ns, grids, nb, cell_start, sorted, kl, r2, dwf, ci, kernel_points, deformed_kp, modulations, g, dx, order, overflow); \
-            else                                                                                                     \
-                kpconv_gather_bwd_x_grid_kernel<15, G, MODEV, VECV, T, false><<<grid, 256, 0, st>>>(                  \
-                    s_pts, ns, grids, nb, cell_start, sorted, kl, r2, dwf, ci, kernel_points, deformed_kp, modulations, g, dx, order, overflow); \
-        }                                                                                                            \
-    } while (0)
-#define WS_BWDG(G)                                                                      \
-    do {                                                                                \
-        if (fast) { if (vec4) WS_BWDG2(G, 0, true); else WS_BWDG2(G, 0, false); }        \
-        else { if (vec4) WS_BWDG2(G, 1, true); else WS_BWDG2(G, 1, false); }             \
-    } while (0)
-    const bool fast = !deformed_kp && !modulations && influence == WS_INFLUENCE_LINEAR && aggregation == WS_AGGREGATION_SUM;
-    if (ci <= 4) WS_BWDG(1);
-    else if (ci <= 8) WS_BWDG(2);
-    else if (ci <= 16) WS_BWDG(4);
-    else if (ci <= 32) WS_BWDG(8);
-    else WS_BWDG(16);
-#undef WS_BWDG2
-#undef WS_BWDG
-    WS_LAUNCH_CHECK();
-    return WS_OK;
-}
-
-// ---- deformable fast path (MODE 2) and the wide-row grid backward: launchers -------------------------------------------
-template <typename T>
-int gather_fwd_def_impl(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int64_t* inds, int32_t h,
-                        const T* x, int32_t ci, const float4* kp4, int32_t k, float extent, const int32_t* order, T* wf,
-                        float* min_d2, void* stream, int rows_sorted)
-{
-    int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM);
-    if (rc) return rc;
-    if (nq == 0) return WS_OK;
-    WS_REQUIRE(inds && x && wf && kp4, "NULL argument");
-    WS_REQUIRE(aligned16(kp4), "kp4 must be 16-byte aligned");
-    WS_REQUIRE(ns * (int64_t)ci < (1ll << 31), "ns*ci exceeds the 32-bit row offsets of the gather");
-    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 1, nullptr, 0.0f, nullptr, 0, kp4};
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = ws_grid(nq, 4);
-    int nt = ci <= 16 ? 1 : (ci <= 32 ? 2 : (ci <= 64 ? 4 : (ci <= 128 ? 8 : 16)));
-    if (!((ci % nt == 0) && (nt == 1 || (aligned16(x) && aligned16(wf))))) nt = 1;
-    if (sizeof(T) == 2 && nt == 1 && (ci % 2)) return ws_fail(WS_ERR_UNSUPPORTED, "bf16 rows need an even channel count (ci=%d)", ci);
-#define WS_FWDD(NTV)                                                                                                     \
-    do {                                                                                                                 \
-        if (rows_sorted)                                                                                                 \
-            kpconv_gather_fwd_mfma_kernel<NTV, 2, true, true, T, 0, true><<<grid, 256, 0, st>>>(                          \
-                q_pts, nq, s_pts, ns, inds, h, x, ci, nullptr, nullptr, nullptr, g, wf, min_d2, order);                   \
-        else                                                                                                             \
-            kpconv_gather_fwd_mfma_kernel<NTV, 2, true, true, T><<<grid, 256, 0, st>>>(                                   \
-                q_pts, nq, s_pts, ns, inds, h, x, ci, nullptr, nullptr, nullptr, g, wf, min_d2, order);                   \
-    } while (0)
-    if (nt == 1) WS_FWDD(1);
-    else if (nt == 2) WS_FWDD(2);
-    else if (nt == 4) WS_FWDD(4);
-    else if (nt == 8) WS_FWDD(8);
-    else WS_FWDD(16);
-#undef WS_FWDD
-    WS_LAUNCH_CHECK();
-    return WS_OK;
-}
-
-template <typename T>
-int gather_bwd_x_def_impl(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, int32_t h,
-                          const int32_t* t_offsets, const int32_t* t_pairs, const T* dwf, int32_t ci, const float4* kp4,
-                          int32_t k, float extent, const int32_t* order, T* dx, void* stream)
-{
-    constexpr bool F32 = sizeof(T) == 4;
-    int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM);
-    if (rc) return rc;
-    if (ns == 0) return WS_OK;
-    WS_REQUIRE(t_offsets && t_pairs && dwf && dx && kp4 && aligned16(kp4), "NULL / unaligned argument");
-    WS_REQUIRE(nq * (int64_t)h < (1ll << 31), "nq*h exceeds int32");
-    WS_REQUIRE(nq * (int64_t)k * ci < (1ll << 31), "nq*k*ci exceeds the 32-bit row offsets of the gather");
-    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 1, nullptr, 0.0f, nullptr, 0, kp4};
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = ws_grid(ns, 4);
-    const int vec4 = (ci % 4 == 0) && ws_row_aligned<T>(dwf) && ws_row_aligned<T>(dx);
-    WS_REQUIRE(F32 || vec4, "bf16 feature rows need ci %% 4 == 0 and 8-byte aligned rows (ci=%d)", ci);
-#define WS_BWDD2(G, VECV)                                                                                            \
-    do {                                                                                                             \
-        if constexpr (F32 || VECV)                                                                                   \
-            kpconv_gather_bwd_x_kernel<15, G, 2, VECV, T><<<grid, 256, 0, st>>>(q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, dwf, ci, \
-                                                                               nullptr, nullptr, nullptr, g, dx, order); \
-    } while (0)
-#define WS_BWDD(G) do { if (vec4) WS_BWDD2(G, true); else WS_BWDD2(G, false); } while (0)
-    if (ci <= 4) WS_BWDD(1);
-    else if (ci <= 8) WS_BWDD(2);
-    else if (ci <= 16) WS_BWDD(4);
-    else if (ci <= 32) WS_BWDD(8);
-    else WS_BWDD(16);
-#undef WS_BWDD2
-#undef WS_BWDD
-    WS_LAUNCH_CHECK();
-    return WS_OK;
-}
-
-template <typename T>
-int gather_bwd_x_gridw_impl(const float* s_pts, int64_t ns, const void* grid_blob, int32_t nb, int64_t cells,
-                            const uint64_t* key_last, float radius, const T* dwf, int32_t ci, const float* kernel_points,
-                            int32_t k, const float4* kp4, float extent, const int32_t* order, const int64_t* rows, int32_t rows_h,
-                            T* dx, void* stream, const float* rmax)
-{
-    constexpr bool F32 = sizeof(T) == 4;
-    int rc = check_common(s_pts, ns, s_pts, ns, 1, ci, k, extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM);
-    if (rc) return rc;
-    if (ns == 0) return WS_OK;
-    WS_REQUIRE(grid_blob && key_last && dwf && dx && (kernel_points || kp4), "NULL argument");
-    WS_REQUIRE(!kp4 || aligned16(kp4), "kp4 must be 16-byte aligned");
-    WS_REQUIRE(nb >= 1 && cells >= 1, "bad grid nb=%d cells=%lld", nb, (long long)cells);
-    WS_REQUIRE(ns * (int64_t)k * ci < (1ll << 31), "ns*k*ci exceeds the 32-bit row offsets of the gather");
-    WS_REQUIRE(!rows || rows_h >= 1, "index rows given without their width");
-    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, kp4 ? 1 : 0, nullptr, 0.0f, rows, rows_h, kp4,
-                 kp4 ? rmax : nullptr, 0};
-    hipStream_t st = (hipStream_t)stream;
-    const char* base = (const char*)grid_blob;
-    const CloudGrid* grids = (const CloudGrid*)base;
-    const int32_t* cell_start = (const int32_t*)(base + ws_grid_blob_cells_off(nb));
-    const float4* sorted = (const float4*)(base + ws_grid_blob_sorted_off(nb, cells));
-    const float r2 = radius * radius;
-    const unsigned long long* kl = reinterpret_cast<const unsigned long long*>(key_last);
-    g.ilv = order ? GRID_INTERLEAVE : 0;
-    const int grid = g.ilv > 0 ? 8 * (int)std::max<int64_t>(1, std::min<int64_t>(g.ilv, ws_ceil_div(ns, 32))) : ws_grid(ns, 4);
-    const int vec4 = (ci % 4 == 0) && ws_row_aligned<T>(dwf) && ws_row_aligned<T>(dx);
-    WS_REQUIRE(F32 || vec4, "bf16 feature rows need ci %% 4 == 0 and 8-byte aligned rows (ci=%d)", ci);
-#define WS_GW3(G, MODEV, VECV, NCHV)                                                                                  \
-    kpconv_gather_bwd_x_gridw_kernel<15, G, MODEV, VECV, NCHV, T><<<grid, 256, 0, st>>>(                              \
-        s_pts, ns, grids, nb, cell_start, sorted, kl, r2, dwf, ci, kernel_points, nullptr, nullptr, g, dx, order)
-#define WS_GW2(G, MODEV, VECV)                                                                                        \
-    do {                                                                                                              \
-        if constexpr (F32 || VECV) {                                                                                  \
-            if (G < 16 || ci <= 64) WS_GW3(G, MODEV, VECV, 1);                                                        \
-            else if constexpr (G == 16) {                                                                             \
-                if (ci <= 128) WS_GW3(G, MODEV, VECV, 2);                                                             \
-                else WS_GW3(G, MODEV, VECV, 4);                                                                       \
-            }                                                                                                         \
-        }                                                                                                             \
-    } while (0)
-#define WS_GW(G)                                                                        \
-    do {                                                                                \
-        if (kp4) { if (vec4) WS_GW2(G, 2, true); else WS_GW2(G, 2, false); }             \
-        else { if (vec4) WS_GW2(G, 0, true); else WS_GW2(G, 0, false); }                 \
-    } while (0)
-    if (ci <= 4) WS_GW(1);
-    else if (ci <= 8) WS_GW(2);
-    else if (ci <= 16) WS_GW(4);
-    else if (ci <= 32) WS_GW(8);
-    else WS_GW(16);
-#undef WS_GW3
-#undef WS_GW2
-#undef WS_GW
-    WS_LAUNCH_CHECK();
-    return WS_OK;
-}
-
-template <typename T>
-int gather_bwd_geom_def_impl(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int64_t* inds, int32_t h,
-                             const T* x, int32_t ci, const T* dwf, const float4* kp4, int32_t k, const float* d_min_d2,
-                             float extent, const int32_t* order, float4* d_kp4, void* stream, int rows_sorted)
-{
-    int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM);
-    if (rc) return rc;
-    if (nq == 0) return WS_OK;
-    WS_REQUIRE(inds && x && dwf && kp4 && d_kp4 && aligned16(kp4) && aligned16(d_kp4), "NULL / unaligned argument");
-    WS_REQUIRE(ns * (int64_t)ci < (1ll << 31) && nq * (int64_t)k * ci < (1ll << 31), "row offsets exceed 32 bits");
-    if (ci % 16 != 0 || !aligned16(x) || !aligned16(dwf))
-        return ws_fail(WS_ERR_UNSUPPORTED, "geometry backward on the matrix core needs ci %% 16 == 0 and 16-byte aligned rows (ci=%d)", ci);
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = ws_grid(nq, 4);
-#define WS_K6(CKV, AREGV)                                                                                                 \
-    do {                                                                                                                  \
-        if (rows_sorted)                                                                                                  \
-            kpconv_gather_bwd_geom_def_kernel<CKV, AREGV, T, true><<<grid, 256, 0, st>>>(q_pts, nq, s_pts, ns, inds, h, x, ci, dwf, kp4, \
-                                                                                         d_min_d2, extent, d_kp4, order); \
-        else                                                                                                              \
-            kpconv_gather_bwd_geom_def_kernel<CKV, AREGV, T, false><<<grid, 256, 0, st>>>(q_pts, nq, s_pts, ns, inds, h, x, ci, dwf, kp4, \
-                                                                                          d_min_d2, extent, d_kp4, order); \
-    } while (0)
-    if (ci == 16) WS_K6(4, true);
-    else if (ci == 32) WS_K6(8, true);
-    else if (ci == 64) WS_K6(16, true);
-    else if (ci == 128) WS_K6(32, true);
-    else if (ci % 128 == 0) WS_K6(32, false);
-    else if (ci % 64 == 0) WS_K6(16, false);
-    else if (ci % 32 == 0) WS_K6(8, false);
-    else WS_K6(4, false);
-#undef WS_K6
-    WS_LAUNCH_CHECK();
-    return WS_OK;
+    GatherPlan p;
+    const int mode = rigid_fast(deformed_kp, modulations, influence, aggregation) ? 0 : 1;
+    if (int rc = bwd_x_grid_plan(bf16, ns, ci, dwf, dx, mode, order != nullptr, p)) return rc;
+    GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, gate, gate_slope, rows, rows_h, nullptr, nullptr, 0, p.ilv};
+    const GridView v = grid_view(grid_blob, nb, cells, key_last, radius);
+    dispatch([&](auto bf, auto gr, auto md, auto vec, auto sort) {
+        using T = Row<bf.value>;
+        if constexpr (!bf.value || vec.value)
+            kpconv_gather_bwd_x_grid_kernel<15, gr.value, md.value, vec.value != 0, T, sort.value != 0><<<p.grid, 256, 0, (hipStream_t)stream>>>(
+                s_pts, ns, v.grids, nb, v.cell_start, v.sorted, v.key_last, v.r2, (const T*)dwf, ci, kernel_points, deformed_kp, modulations, g,
+                (T*)dx, order, overflow);
+    }, Flag{p.bf16}, Pick<1, 2, 4, 8, 16>{p.n}, Pick<0, 1>{p.mode}, Flag{p.vec}, Flag{p.sort});
+    return launched();
 }
 
 }  // namespace
 
 extern "C" {
-
-// ---- deformable fast path: deformable (+ modulated) KPConv with linear influence and sum aggregation, the per-query kernel
-//      points packed as kp4 [nq, 15] float4 (x, y, z, modulation; ws_kpconv_deform_prepare).  rows_bf16: feature rows
-//      (x, wf, dwf, dx) are bf16 instead of f32.
-int ws_kpconv_gather_fwd_def(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int64_t* inds, int32_t h,
-                             const void* x, int32_t ci, const float* kp4, int32_t k, float extent, const int32_t* order,
-                             void* wf, float* min_d2, int32_t rows_bf16, int32_t rows_sorted, void* stream)
-{
-    const float4* kq = reinterpret_cast<const float4*>(kp4);
-    if (rows_bf16)
-        return gather_fwd_def_impl<bf16_t>(q_pts, nq, s_pts, ns, inds, h, (const bf16_t*)x, ci, kq, k, extent, order, (bf16_t*)wf, min_d2,
-                                           stream, rows_sorted);
-    return gather_fwd_def_impl<float>(q_pts, nq, s_pts, ns, inds, h, (const float*)x, ci, kq, k, extent, order, (float*)wf, min_d2, stream,
-                                      rows_sorted);
-}
 
 // ws_kpconv_gather_fwd / _bf16 for index rows that are sorted by distance from their query (rows_sorted != 0: what the radius
 // search delivers): the rigid linear / sum forms then stop at the reach of the kernel points (see CUT above); other modes and
@@ -2522,21 +2445,79 @@ int ws_kpconv_gather_fwd_ex(const float* q_pts, int64_t nq, const float* s_pts, 
                             const float* modulations, float extent, int32_t influence, int32_t aggregation, const int32_t* order,
                             void* wf, float* min_d2, int32_t rows_bf16, int32_t rows_sorted, void* stream)
 {
-    if (rows_bf16)
-        return gather_fwd_impl<bf16_t>(q_pts, nq, s_pts, ns, inds, h, (const bf16_t*)x, ci, kernel_points, k, deformed_kp, modulations,
-                                       extent, influence, aggregation, order, (bf16_t*)wf, min_d2, stream, rows_sorted);
-    return gather_fwd_impl<float>(q_pts, nq, s_pts, ns, inds, h, (const float*)x, ci, kernel_points, k, deformed_kp, modulations, extent,
-                                  influence, aggregation, order, (float*)wf, min_d2, stream, rows_sorted);
+    if (int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, influence, aggregation)) return rc;
+    if (nq == 0) return WS_OK;
+    WS_REQUIRE(inds && x && wf && (kernel_points || deformed_kp), "NULL argument");
+    WS_REQUIRE(ns * (int64_t)ci < (1ll << 31), "ns*ci exceeds the 32-bit row offsets of the gather");
+    GatherPlan p;
+    if (int rc = fwd_plan(rows_bf16 != 0, nq, ci, x, wf, deformed_kp, modulations, influence, aggregation, rows_sorted != 0, p)) return rc;
+    GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, nullptr, 0.0f, nullptr, 0, nullptr, nullptr, p.rows_sorted, 0, p.csplit};
+    if (p.kernel == GK_FWD_MFMA)
+        launch_fwd_mfma(p, stream, q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, deformed_kp, modulations, g, wf, min_d2, order);
+    else
+        dispatch([&](auto bf, auto vec, auto mode, auto def) {
+            using T = Row<bf.value>;
+            if constexpr ((!bf.value || vec.value) && (mode.value == 1 || !def.value))
+                kpconv_gather_fwd_kernel<15, vec.value ? 1 : 4, mode.value, def.value != 0, vec.value != 0, vec.value ? 4 : 1, T>
+                    <<<p.grid, 256, 0, (hipStream_t)stream>>>(
+                    q_pts, nq, s_pts, ns, inds, h, (const T*)x, ci, kernel_points, deformed_kp, modulations, g, (T*)wf, min_d2, order);
+        }, Flag{p.bf16}, Flag{p.vec}, Pick<0, 1>{p.mode}, Flag{p.def});
+    return launched();
+}
+
+int ws_kpconv_gather_fwd(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
+                         const int64_t* inds, int32_t h, const float* x, int32_t ci,
+                         const float* kernel_points, int32_t k, const float* deformed_kp,
+                         const float* modulations, float extent, int32_t influence, int32_t aggregation,
+                         const int32_t* order, float* wf, float* min_d2, void* stream)
+{
+    return ws_kpconv_gather_fwd_ex(q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, k, deformed_kp, modulations, extent, influence,
+                                   aggregation, order, wf, min_d2, 0, 0, stream);
+}
+
+int ws_kpconv_gather_fwd_bf16(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
+                              const int64_t* inds, int32_t h, const uint16_t* x, int32_t ci,
+                              const float* kernel_points, int32_t k, const float* deformed_kp,
+                              const float* modulations, float extent, int32_t influence, int32_t aggregation,
+                              const int32_t* order, uint16_t* wf, float* min_d2, void* stream)
+{
+    return ws_kpconv_gather_fwd_ex(q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, k, deformed_kp, modulations, extent, influence,
+                                   aggregation, order, wf, min_d2, 1, 0, stream);
+}
+
+// ---- deformable fast path: deformable (+ modulated) KPConv with linear influence and sum aggregation, the per-query kernel
+//      points packed as kp4 [nq, 15] float4 (x, y, z, modulation; ws_kpconv_deform_prepare).  rows_bf16: feature rows
+//      (x, wf, dwf, dx) are bf16 instead of f32.
+int ws_kpconv_gather_fwd_def(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int64_t* inds, int32_t h,
+                             const void* x, int32_t ci, const float* kp4, int32_t k, float extent, const int32_t* order,
+                             void* wf, float* min_d2, int32_t rows_bf16, int32_t rows_sorted, void* stream)
+{
+    if (int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM)) return rc;
+    if (nq == 0) return WS_OK;
+    WS_REQUIRE(inds && x && wf && kp4, "NULL argument");
+    WS_REQUIRE(aligned16(kp4), "kp4 must be 16-byte aligned");
+    WS_REQUIRE(ns * (int64_t)ci < (1ll << 31), "ns*ci exceeds the 32-bit row offsets of the gather");
+    GatherPlan p;
+    if (int rc = fwd_def_plan(rows_bf16 != 0, nq, ci, x, wf, rows_sorted != 0, p)) return rc;
+    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 1, nullptr, 0.0f, nullptr, 0, reinterpret_cast<const float4*>(kp4)};
+    launch_fwd_mfma(p, stream, q_pts, nq, s_pts, ns, inds, h, x, ci, nullptr, nullptr, nullptr, g, wf, min_d2, order);
+    return launched();
 }
 
 int ws_kpconv_gather_bwd_x_def(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, int32_t h,
                                const int32_t* t_offsets, const int32_t* t_pairs, const void* dwf, int32_t ci, const float* kp4,
                                int32_t k, float extent, const int32_t* order, void* dx, int32_t rows_bf16, void* stream)
 {
-    const float4* kq = reinterpret_cast<const float4*>(kp4);
-    if (rows_bf16)
-        return gather_bwd_x_def_impl<bf16_t>(q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, (const bf16_t*)dwf, ci, kq, k, extent, order, (bf16_t*)dx, stream);
-    return gather_bwd_x_def_impl<float>(q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, (const float*)dwf, ci, kq, k, extent, order, (float*)dx, stream);
+    if (int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM)) return rc;
+    if (ns == 0) return WS_OK;
+    WS_REQUIRE(t_offsets && t_pairs && dwf && dx && kp4 && aligned16(kp4), "NULL / unaligned argument");
+    WS_REQUIRE(nq * (int64_t)h < (1ll << 31), "nq*h exceeds int32");
+    WS_REQUIRE(nq * (int64_t)k * ci < (1ll << 31), "nq*k*ci exceeds the 32-bit row offsets of the gather");
+    GatherPlan p;
+    if (int rc = bwd_x_plan(rows_bf16 != 0, ns, ci, dwf, dx, 2, p)) return rc;
+    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 1, nullptr, 0.0f, nullptr, 0, reinterpret_cast<const float4*>(kp4)};
+    launch_bwd_x(p, stream, q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, dwf, ci, nullptr, nullptr, nullptr, g, dx, order);
+    return launched();
 }
 
 // the table-free backward for any in-degree (rows wider than 128): rigid (kp4 NULL, kernel_points given) or deformable (kp4)
@@ -2546,12 +2527,26 @@ int ws_kpconv_gather_bwd_x_grid_wide(const float* s_pts, int64_t ns, const void*
                                      const int32_t* order, const int64_t* rows, int32_t rows_h, void* dx, int32_t rows_bf16,
                                      void* stream)
 {
-    const float4* kq = reinterpret_cast<const float4*>(kp4);
-    if (rows_bf16)
-        return gather_bwd_x_gridw_impl<bf16_t>(s_pts, ns, grid_blob, nb, cells, key_last, radius, (const bf16_t*)dwf, ci, kernel_points, k,
-                                               kq, extent, order, rows, rows_h, (bf16_t*)dx, stream, kp_rmax);
-    return gather_bwd_x_gridw_impl<float>(s_pts, ns, grid_blob, nb, cells, key_last, radius, (const float*)dwf, ci, kernel_points, k, kq,
-                                          extent, order, rows, rows_h, (float*)dx, stream, kp_rmax);
+    if (int rc = check_common(s_pts, ns, s_pts, ns, 1, ci, k, extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM)) return rc;
+    if (ns == 0) return WS_OK;
+    WS_REQUIRE(grid_blob && key_last && dwf && dx && (kernel_points || kp4), "NULL argument");
+    WS_REQUIRE(!kp4 || aligned16(kp4), "kp4 must be 16-byte aligned");
+    WS_REQUIRE(nb >= 1 && cells >= 1, "bad grid nb=%d cells=%lld", nb, (long long)cells);
+    WS_REQUIRE(ns * (int64_t)k * ci < (1ll << 31), "ns*k*ci exceeds the 32-bit row offsets of the gather");
+    WS_REQUIRE(!rows || rows_h >= 1, "index rows given without their width");
+    GatherPlan p;
+    if (int rc = bwd_x_gridw_plan(rows_bf16 != 0, ns, ci, dwf, dx, kp4 != nullptr, order != nullptr, p)) return rc;
+    GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, kp4 ? 1 : 0, nullptr, 0.0f, rows, rows_h,
+                 reinterpret_cast<const float4*>(kp4), kp4 ? kp_rmax : nullptr, 0, p.ilv};
+    const GridView v = grid_view(grid_blob, nb, cells, key_last, radius);
+    dispatch([&](auto bf, auto gr, auto mode, auto vec, auto nch) {
+        using T = Row<bf.value>;
+        if constexpr ((!bf.value || vec.value) && (nch.value == 1 || gr.value == 16))
+            kpconv_gather_bwd_x_gridw_kernel<15, gr.value, mode.value, vec.value != 0, nch.value, T><<<p.grid, 256, 0, (hipStream_t)stream>>>(
+                s_pts, ns, v.grids, nb, v.cell_start, v.sorted, v.key_last, v.r2, (const T*)dwf, ci, kernel_points, nullptr, nullptr, g, (T*)dx,
+                order);
+    }, Flag{p.bf16}, Pick<1, 2, 4, 8, 16>{p.n}, Pick<0, 2>{p.mode}, Flag{p.vec}, Pick<1, 2, 4>{p.nch});
+    return launched();
 }
 
 int ws_kpconv_gather_bwd_geom_def(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns, const int64_t* inds, int32_t h,
@@ -2559,13 +2554,19 @@ int ws_kpconv_gather_bwd_geom_def(const float* q_pts, int64_t nq, const float* s
                                   float extent, const int32_t* order, float* d_kp4, int32_t rows_bf16, int32_t rows_sorted,
                                   void* stream)
 {
-    const float4* kq = reinterpret_cast<const float4*>(kp4);
-    float4* dk = reinterpret_cast<float4*>(d_kp4);
-    if (rows_bf16)
-        return gather_bwd_geom_def_impl<bf16_t>(q_pts, nq, s_pts, ns, inds, h, (const bf16_t*)x, ci, (const bf16_t*)dwf, kq, k, d_min_d2,
-                                                extent, order, dk, stream, rows_sorted);
-    return gather_bwd_geom_def_impl<float>(q_pts, nq, s_pts, ns, inds, h, (const float*)x, ci, (const float*)dwf, kq, k, d_min_d2, extent,
-                                           order, dk, stream, rows_sorted);
+    if (int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM)) return rc;
+    if (nq == 0) return WS_OK;
+    WS_REQUIRE(inds && x && dwf && kp4 && d_kp4 && aligned16(kp4) && aligned16(d_kp4), "NULL / unaligned argument");
+    WS_REQUIRE(ns * (int64_t)ci < (1ll << 31) && nq * (int64_t)k * ci < (1ll << 31), "row offsets exceed 32 bits");
+    GatherPlan p;
+    if (int rc = bwd_geom_def_plan(rows_bf16 != 0, nq, ci, x, dwf, rows_sorted != 0, p)) return rc;
+    dispatch([&](auto bf, auto ck, auto areg, auto cut) {
+        using T = Row<bf.value>;
+        kpconv_gather_bwd_geom_def_kernel<ck.value, areg.value != 0, T, cut.value != 0><<<p.grid, 256, 0, (hipStream_t)stream>>>(
+            q_pts, nq, s_pts, ns, inds, h, (const T*)x, ci, (const T*)dwf, reinterpret_cast<const float4*>(kp4), d_min_d2, extent,
+            reinterpret_cast<float4*>(d_kp4), order);
+    }, Flag{p.bf16}, Pick<4, 8, 16, 32>{p.n}, Flag{p.areg}, Flag{p.cut});
+    return launched();
 }
 
 // Forward-only KPConv layer in ONE launch (inference: the testers' forward passes, utils/tester_PseudoLabel.py:164):
@@ -2592,50 +2593,55 @@ int ws_kpconv_layer_fwd_fused(const float* q_pts, int64_t nq, const float* s_pts
     return WS_OK;
 }
 
-// Name of the forward gather kernel the dispatchers above launch for a layer (bench.py's roofline.kernel): same selection
-// rules as gather_fwd_impl / gather_fwd_def_impl for 16-byte aligned rows.  mode: 0 rigid (kernel_points), 1 deformable
-// through the generic entries, 2 deformable fast path (kp4).
+// What the launchers of this file launch for these arguments, as "kernel<template arguments> key=value ..." (grid, csplit, ilv):
+// the plan function of the entry named by op (WS_GATHER_*, weasal_hip.h), nothing read or launched.  rows_a / rows_b: the two
+// feature-row operands of that entry (x and wf, dwf and dx, or x and dwf), tested for alignment only.
+int ws_kpconv_gather_variant(int32_t op, int64_t nq, int64_t ns, int32_t ci, const void* rows_a, const void* rows_b, int32_t deformed,
+                             int32_t modulated, int32_t influence, int32_t aggregation, int32_t rows_bf16, int32_t rows_sorted,
+                             int32_t ordered, char* out, int32_t cap)
+{
+    WS_REQUIRE(out && cap > 0 && ci >= 1 && nq >= 0 && ns >= 0, "bad argument");
+    const bool bf = rows_bf16 != 0, def = deformed != 0, mod = modulated != 0, srt = rows_sorted != 0, ord = ordered != 0;
+    const int mode = rigid_fast(def, mod, influence, aggregation) ? 0 : 1;
+    GatherPlan p;
+    int rc;
+    switch (op) {
+    case WS_GATHER_FWD: rc = fwd_plan(bf, nq, ci, rows_a, rows_b, def, mod, influence, aggregation, srt, p); break;
+    case WS_GATHER_BWD_X: rc = bwd_x_plan(bf, ns, ci, rows_a, rows_b, mode, p); break;
+    case WS_GATHER_BWD_GEOM: rc = bwd_geom_plan(bf, nq, ci, rows_a, rows_b, p); break;
+    case WS_GATHER_BWD_X_GRID: rc = bwd_x_grid_plan(bf, ns, ci, rows_a, rows_b, mode, ord, p); break;
+    case WS_GATHER_FWD_DEF: rc = fwd_def_plan(bf, nq, ci, rows_a, rows_b, srt, p); break;
+    case WS_GATHER_BWD_X_DEF: rc = bwd_x_plan(bf, ns, ci, rows_a, rows_b, 2, p); break;
+    case WS_GATHER_BWD_X_GRID_WIDE: rc = bwd_x_gridw_plan(bf, ns, ci, rows_a, rows_b, def, ord, p); break;
+    case WS_GATHER_BWD_GEOM_DEF: rc = bwd_geom_def_plan(bf, nq, ci, rows_a, rows_b, srt, p); break;
+    default: return ws_fail(WS_ERR_INVALID, "unknown gather operation %d", op);
+    }
+    if (rc == WS_OK) plan_text(p, out, (size_t)cap);
+    return rc;
+}
+
+// Name of the forward gather kernel a layer launches (bench.py's roofline.kernel): the forward plan for 16-byte aligned rows at
+// nq = SPLIT_ROWS (a level too large for the SPLIT_NT narrowing and csplit), in the form this entry has always printed.  mode: 0 rigid
+// (kernel_points), 1 deformable through the generic entries, 2 deformable fast path (kp4).
 int ws_kpconv_gather_fwd_variant(int32_t ci, int32_t mode, int32_t influence, int32_t aggregation, int32_t rows_bf16,
                                  int32_t rows_sorted, char* out, int32_t cap)
 {
     WS_REQUIRE(out && cap > 0 && ci >= 1, "bad argument");
-    const char* t = rows_bf16 ? "bf16" : "float";
-    const bool fast = influence == WS_INFLUENCE_LINEAR && aggregation == WS_AGGREGATION_SUM;
-    if (mode == 2 || ci > 4) {
-        int nt = ci <= 16 ? 1 : (ci <= 32 ? 2 : (ci <= 64 ? 4 : (ci <= 128 ? 8 : 16)));
-        if (ci % nt) nt = 1;
-        const int m = mode == 2 ? 2 : (mode == 1 ? 1 : (fast ? 0 : 1));
-        const bool cut = rows_sorted && (m == 2 || m == 0);
-        snprintf(out, (size_t)cap, "kpconv_gather_fwd_mfma_kernel<NT=%d, MODE=%d, DEF=%s, VECROW=true, %s, GS=default, CUT=%s>", nt, m,
-                 mode ? "true" : "false", t, cut ? "true" : "false");
-        return WS_OK;
-    }
-    const int vec4 = ci % 4 == 0;
-    snprintf(out, (size_t)cap, "kpconv_gather_fwd_kernel<K=15, G=%d, MODE=%d, DEF=%s, VEC=%s, PW=%d, %s>%s", vec4 ? 1 : 4,
-             (mode || !fast) ? 1 : 0, mode ? "true" : "false", vec4 ? "true" : "false", vec4 ? 4 : 1, t,
-             (rows_sorted && !mode && fast) ? " (sorted-row cutoff on)" : "");
+    alignas(16) static const char row[16] = {};
+    const bool bf = rows_bf16 != 0, srt = rows_sorted != 0;
+    GatherPlan p;
+    if (int rc = mode == 2 ? fwd_def_plan(bf, SPLIT_ROWS, ci, row, row, srt, p)
+                           : fwd_plan(bf, SPLIT_ROWS, ci, row, row, mode != 0, false, influence, aggregation, srt, p))
+        return rc;
+    const char* t = bf ? "bf16" : "float";
+    auto b = [](bool v) { return v ? "true" : "false"; };
+    if (p.kernel == GK_FWD_MFMA)
+        snprintf(out, (size_t)cap, "kpconv_gather_fwd_mfma_kernel<NT=%d, MODE=%d, DEF=%s, VECROW=true, %s, GS=default, CUT=%s>", p.n, p.mode,
+                 b(p.def), t, b(p.cut));
+    else
+        snprintf(out, (size_t)cap, "kpconv_gather_fwd_kernel<K=15, G=%d, MODE=%d, DEF=%s, VEC=%s, PW=%d, %s>%s", p.n, p.mode, b(p.def),
+                 b(p.vec), p.pw, t, (p.rows_sorted && p.mode == 0) ? " (sorted-row cutoff on)" : "");
     return WS_OK;
-}
-
-int ws_kpconv_gather_fwd(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
-                         const int64_t* inds, int32_t h, const float* x, int32_t ci,
-                         const float* kernel_points, int32_t k, const float* deformed_kp,
-                         const float* modulations, float extent, int32_t influence, int32_t aggregation,
-                         const int32_t* order, float* wf, float* min_d2, void* stream)
-{
-    return gather_fwd_impl<float>(q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, k, deformed_kp, modulations, extent,
-                                  influence, aggregation, order, wf, min_d2, stream);
-}
-
-int ws_kpconv_gather_fwd_bf16(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
-                              const int64_t* inds, int32_t h, const uint16_t* x, int32_t ci,
-                              const float* kernel_points, int32_t k, const float* deformed_kp,
-                              const float* modulations, float extent, int32_t influence, int32_t aggregation,
-                              const int32_t* order, uint16_t* wf, float* min_d2, void* stream)
-{
-    return gather_fwd_impl<bf16_t>(q_pts, nq, s_pts, ns, inds, h, reinterpret_cast<const bf16_t*>(x), ci, kernel_points, k,
-                                   deformed_kp, modulations, extent, influence, aggregation, order,
-                                   reinterpret_cast<bf16_t*>(wf), min_d2, stream);
 }
 
 int ws_kpconv_gather_bwd_x(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
@@ -2644,8 +2650,8 @@ int ws_kpconv_gather_bwd_x(const float* q_pts, int64_t nq, const float* s_pts, i
                            const float* deformed_kp, const float* modulations, float extent,
                            int32_t influence, int32_t aggregation, const int32_t* order, float* dx, void* stream)
 {
-    return gather_bwd_x_impl<float>(q_pts, nq, s_pts, ns, inds, h, t_offsets, t_pairs, dwf, ci, kernel_points, k, deformed_kp,
-                                    modulations, extent, influence, aggregation, order, dx, stream);
+    return gather_bwd_x_impl(false, q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, dwf, ci, kernel_points, k, deformed_kp, modulations, extent,
+                             influence, aggregation, order, dx, stream);
 }
 
 int ws_kpconv_gather_bwd_x_bf16(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
@@ -2654,9 +2660,8 @@ int ws_kpconv_gather_bwd_x_bf16(const float* q_pts, int64_t nq, const float* s_p
                                 const float* deformed_kp, const float* modulations, float extent,
                                 int32_t influence, int32_t aggregation, const int32_t* order, uint16_t* dx, void* stream)
 {
-    return gather_bwd_x_impl<bf16_t>(q_pts, nq, s_pts, ns, inds, h, t_offsets, t_pairs, reinterpret_cast<const bf16_t*>(dwf), ci,
-                                     kernel_points, k, deformed_kp, modulations, extent, influence, aggregation, order,
-                                     reinterpret_cast<bf16_t*>(dx), stream);
+    return gather_bwd_x_impl(true, q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, dwf, ci, kernel_points, k, deformed_kp, modulations, extent,
+                             influence, aggregation, order, dx, stream);
 }
 
 int ws_kpconv_gather_bwd_geom(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
@@ -2666,8 +2671,8 @@ int ws_kpconv_gather_bwd_geom(const float* q_pts, int64_t nq, const float* s_pts
                               int32_t influence, int32_t aggregation, float* d_deformed_kp,
                               float* d_modulations, void* stream)
 {
-    return gather_bwd_geom_impl<float>(q_pts, nq, s_pts, ns, inds, h, x, ci, dwf, kernel_points, k, deformed_kp, modulations,
-                                       d_min_d2, extent, influence, aggregation, d_deformed_kp, d_modulations, stream);
+    return gather_bwd_geom_impl(false, q_pts, nq, s_pts, ns, inds, h, x, ci, dwf, k, deformed_kp, modulations, d_min_d2, extent, influence,
+                                aggregation, d_deformed_kp, d_modulations, stream);
 }
 
 int ws_kpconv_gather_bwd_geom_bf16(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
@@ -2677,9 +2682,8 @@ int ws_kpconv_gather_bwd_geom_bf16(const float* q_pts, int64_t nq, const float* 
                                    int32_t influence, int32_t aggregation, float* d_deformed_kp,
                                    float* d_modulations, void* stream)
 {
-    return gather_bwd_geom_impl<bf16_t>(q_pts, nq, s_pts, ns, inds, h, reinterpret_cast<const bf16_t*>(x), ci,
-                                        reinterpret_cast<const bf16_t*>(dwf), kernel_points, k, deformed_kp, modulations,
-                                        d_min_d2, extent, influence, aggregation, d_deformed_kp, d_modulations, stream);
+    return gather_bwd_geom_impl(true, q_pts, nq, s_pts, ns, inds, h, x, ci, dwf, k, deformed_kp, modulations, d_min_d2, extent, influence,
+                                aggregation, d_deformed_kp, d_modulations, stream);
 }
 
 int ws_kpconv_gather_bwd_x_grid(const float* s_pts, int64_t ns, const void* grid_blob, int32_t nb, int64_t cells,
@@ -2688,8 +2692,8 @@ int ws_kpconv_gather_bwd_x_grid(const float* s_pts, int64_t ns, const void* grid
                                 float extent, int32_t influence, int32_t aggregation, const int32_t* order, float* dx,
                                 int32_t* overflow, void* stream)
 {
-    return gather_bwd_x_grid_impl<float>(s_pts, ns, grid_blob, nb, cells, key_last, radius, dwf, ci, kernel_points, k, deformed_kp,
-                                         modulations, extent, influence, aggregation, order, dx, overflow, stream);
+    return gather_bwd_x_grid_impl(false, s_pts, ns, grid_blob, nb, cells, key_last, radius, dwf, ci, kernel_points, k, deformed_kp,
+                                  modulations, extent, influence, aggregation, order, dx, overflow, stream);
 }
 
 int ws_kpconv_gather_bwd_x_grid_bf16(const float* s_pts, int64_t ns, const void* grid_blob, int32_t nb, int64_t cells,
@@ -2698,9 +2702,8 @@ int ws_kpconv_gather_bwd_x_grid_bf16(const float* s_pts, int64_t ns, const void*
                                      float extent, int32_t influence, int32_t aggregation, const int32_t* order, uint16_t* dx,
                                      int32_t* overflow, void* stream)
 {
-    return gather_bwd_x_grid_impl<bf16_t>(s_pts, ns, grid_blob, nb, cells, key_last, radius, reinterpret_cast<const bf16_t*>(dwf), ci,
-                                          kernel_points, k, deformed_kp, modulations, extent, influence, aggregation, order,
-                                          reinterpret_cast<bf16_t*>(dx), overflow, stream);
+    return gather_bwd_x_grid_impl(true, s_pts, ns, grid_blob, nb, cells, key_last, radius, dwf, ci, kernel_points, k, deformed_kp,
+                                  modulations, extent, influence, aggregation, order, dx, overflow, stream);
 }
 
 // K4 / K4G with the activation backward of the preceding unary block folded into the store: dx * LeakyReLU'(gate_y)
@@ -2712,8 +2715,8 @@ int ws_kpconv_gather_bwd_x_gated(const float* q_pts, int64_t nq, const float* s_
                                  int32_t influence, int32_t aggregation, const int32_t* order, const float* gate_y,
                                  float gate_slope, float* dx, void* stream)
 {
-    return gather_bwd_x_impl<float>(q_pts, nq, s_pts, ns, inds, h, t_offsets, t_pairs, dwf, ci, kernel_points, k, deformed_kp,
-                                    modulations, extent, influence, aggregation, order, dx, stream, gate_y, gate_slope);
+    return gather_bwd_x_impl(false, q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, dwf, ci, kernel_points, k, deformed_kp, modulations, extent,
+                             influence, aggregation, order, dx, stream, gate_y, gate_slope);
 }
 
 int ws_kpconv_gather_bwd_x_grid_gated(const float* s_pts, int64_t ns, const void* grid_blob, int32_t nb, int64_t cells,
@@ -2723,9 +2726,8 @@ int ws_kpconv_gather_bwd_x_grid_gated(const float* s_pts, int64_t ns, const void
                                       const float* gate_y, float gate_slope, const int64_t* rows, int32_t rows_h, float* dx,
                                       int32_t* overflow, void* stream)
 {
-    return gather_bwd_x_grid_impl<float>(s_pts, ns, grid_blob, nb, cells, key_last, radius, dwf, ci, kernel_points, k, deformed_kp,
-                                         modulations, extent, influence, aggregation, order, dx, overflow, stream, gate_y,
-                                         gate_slope, rows, rows_h);
+    return gather_bwd_x_grid_impl(false, s_pts, ns, grid_blob, nb, cells, key_last, radius, dwf, ci, kernel_points, k, deformed_kp,
+                                  modulations, extent, influence, aggregation, order, dx, overflow, stream, gate_y, gate_slope, rows, rows_h);
 }
 
 }  // extern "C"

@@ -652,6 +652,32 @@ int ws_potentials_update(const float* pot_points, int64_t n, const double* h_cen
                          double* out_min, int64_t* out_argmin, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Active-learning selection on the votes of a pass over the training clouds (csrc/active.hip).
+ * ws_al_point_scores: utils/tester_PseudoLabel.py:400-414 -- per row of probs [n,c] (float32 votes, c <= 32, else
+ *   WS_ERR_UNSUPPORTED): entropy = -sum_k p_k * log2f(p_k + 1e-12f), float32, summed in column order; preds = the first
+ *   maximum (np.argmax); score = (double)entropy * class_score[pred], class_score [c] float64 on the device =
+ *   exp(class_w), computed by the caller.  A row without votes gives (0, 0, 0).
+ * ws_al_anchor_scores: utils/tester_WeakLabel.py:436-454 -- anchors as CSR (anchor_ptr [n_anchors + 1], anchor_idx [nnz],
+ *   int64, point ids in [0, n)): out[a] = float32(mean_f32(entropy[idx]) * sum of class_score over the classes that
+ *   occur among preds[idx]); class_score = exp(-label_sum / len(used)) (:428-434) from the caller.  An empty anchor: 0.
+ * ws_topk_select: tester_PseudoLabel.py:416-429, tester_WeakLabel.py:456-465 -- ids [k] = the first k entries of
+ *   argsort(-score) once the excluded ids are removed.  The order is exact: descending score, ascending index among
+ *   equal scores, -0.0 == +0.0, NaN below every number.  h_exclude [m] is a HOST array (the id lists live on the host in
+ *   the reference too), any order, duplicates allowed; an id outside [0, n) or k > n - |unique exclude| is
+ *   WS_ERR_INVALID, found before the device is touched.  score [n] float64, ids and scratch (ws_topk_scratch_bytes)
+ *   on the device; every kernel is queued on `stream` and nothing is read back.  The ids travel as an n-bit map built
+ *   on the host and uploaded from pageable memory: that copy returns only when the work queued on `stream` before it
+ *   has finished, so the call waits for its predecessors on the stream (never for its own kernels).  n <= 2^30.
+ * ------------------------------------------------------------------------------------------ */
+int ws_al_point_scores(const float* probs, int64_t n, int32_t c, const double* class_score, float* entropy, int32_t* preds,
+                       double* score, void* stream);
+int ws_al_anchor_scores(const float* entropy, const int32_t* preds, int64_t n, const int64_t* anchor_ptr, const int64_t* anchor_idx,
+                        int64_t nnz, int64_t n_anchors, const double* class_score, int32_t c, float* out, void* stream);
+int64_t ws_topk_scratch_bytes(int64_t n, int64_t k);
+int ws_topk_select(const double* score, int64_t n, const int64_t* h_exclude, int64_t m, int64_t k, int64_t* ids, void* scratch,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The sphere sampler on tiles resident in device memory: datasets/DALES_PseudoLabel.py:265-518 (`potential_item`) with
  * datasets/common.py:252-334 (`augmentation_transform`), a whole batch per call and no host round trip per sphere.
  *

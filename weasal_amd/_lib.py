@@ -129,6 +129,10 @@ SIGNATURES = {
     "ws_project_confusion": (C.c_int, [_vp, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
     "ws_potentials_scratch_bytes": (_i64, [_i64]),
     "ws_potentials_update": (C.c_int, [_vp, _i64, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "ws_al_point_scores": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ws_al_anchor_scores": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
+    "ws_topk_scratch_bytes": (_i64, [_i64, _i64]),
+    "ws_topk_select": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "ws_sampler_create": (C.c_int, [C.POINTER(_vp)]),
     "ws_sampler_destroy": (None, [_vp]),
     "ws_sampler_add_cloud": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),

@@ -137,6 +137,28 @@ class SphereSampler:
         for args in zip(self.sub_points, self.sub_labels, self.pot_points, self.potentials):
             self.handle.add_cloud(*args)
 
+    def reveal_labels(self, cloud, ids, truth_labels):
+        """Give the points `ids` of tile `cloud` their true label (datasets/Vaihingen3D_PseudoLabel.py:775:
+        sub_labels[ids] = truth[ids]), in place in the resident label buffer the kernels read: the next sample() serves
+        the truth at those points and the tile is not uploaded again.  truth_labels: raw label values of every point of
+        the tile [N] (host or device); ids: host or device int64.  The constructor keeps a label tensor that is already
+        contiguous int32 on the device as it is, without a copy: such a tensor of the caller is the resident buffer and
+        is the one overwritten here."""
+        lab = self.sub_labels[cloud]
+        if lab is None:
+            raise ValueError("set '%s' holds no labels to reveal" % self.set)
+        if lab.data_ptr() != self.handle.keep[cloud][1].data_ptr():         # the buffer ws_sampler_add_cloud was given
+            raise RuntimeError("sub_labels[%d] is not the buffer the sampler handle reads" % cloud)
+        ids = torch.as_tensor(ids, dtype=torch.int64).reshape(-1).to(self.device)
+        truth = torch.as_tensor(truth_labels).reshape(-1).to(self.device)
+        if truth.shape[0] != lab.shape[0]:
+            raise ValueError("truth_labels must hold one label per point of the tile")
+        if ids.numel():
+            lo, hi = torch.stack(torch.aminmax(ids)).tolist()               # one read for both ends
+            if lo < 0 or hi >= lab.shape[0]:
+                raise ValueError("ids outside [0, %d)" % lab.shape[0])
+        lab.index_copy_(0, ids, truth[ids].to(torch.int32))
+
     def _read_state(self, state):
         """the single blocking read of a batch: the state block of ws_sampler_batch"""
         self._sync_count += 1

@@ -236,3 +236,19 @@ def cloud_segmentation_test(net, batches, config, votes, test_radius_ratio=0.7, 
     if val_proportions is not None:
         Cm *= np.expand_dims(np.asarray(val_proportions, np.float32) / (np.sum(Cm, axis=1) + 1e-6), 1)
     return IoU_from_confusions(Cm)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# active-learning selection after a pass over the training clouds (tester_PseudoLabel.py:393-438)
+# ---------------------------------------------------------------------------------------------------------------
+def active_learning_selection(votes, class_w, used_ids_per_cloud, k):
+    """The reference's `active_learning=True` branch on votes resident on the device: for every cloud the k points with
+    the highest entropy score that carry no ground-truth label yet (weasal_amd.active.select_points).  used_ids_per_cloud:
+    one id array per cloud (the `*_al_groundTruth_IDs` lists).  Returns the appended lists, host int64 arrays: the old ids
+    followed by the new ones in selection order (:434).  Raises the reference's ValueError when a cloud has fewer than k
+    unlabelled points left."""
+    from . import active
+    if len(used_ids_per_cloud) != len(votes.probs):
+        raise ValueError("one list of used ids per cloud: got %d for %d clouds" % (len(used_ids_per_cloud), len(votes.probs)))
+    new = [active.select_points(votes, i, class_w, used, k) for i, used in enumerate(used_ids_per_cloud)]
+    return [np.append(active._host_ids(used), ids.cpu().numpy()).astype(np.int64) for used, ids in zip(used_ids_per_cloud, new)]

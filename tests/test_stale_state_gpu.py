@@ -198,7 +198,7 @@ def _sorted_scene(gpu):
 
 
 def _stale_matrix(gpu, how):
-    """a distance-sorted matrix M registered with set_sorted_rows, then `how`:
+    """a distance-sorted matrix M registered as sorted rows, then `how`:
     'recycled' -- M dropped, a new matrix U with the same neighbour sets in shuffled column order at M's address;
     'in_place' -- M's columns shuffled in place (same object, same address, bumped _version).  -> (points, U)"""
     from weasal_amd import ops
@@ -212,7 +212,7 @@ def _stale_matrix(gpu, how):
     with torch.cuda.use_mem_pool(pool):
         M = torch.empty_like(M0)
     M.copy_(M0)
-    ops.set_sorted_rows([(M, 2 * RC)])
+    ops.active_hints().add(M, radius=2 * RC)
     assert ops.rows_cutoff_pays(M, RC)       # the hint applies to M itself
     addr, version = M.data_ptr(), M._version
     if how == "recycled":
@@ -337,6 +337,49 @@ def test_col0_table_does_not_outlive_an_in_place_change(gpu):
     check()
 
 
+@pytest.mark.parametrize("how", ["in_place", "recycled"])
+def test_demand_built_table_does_not_outlive_its_matrix(gpu, how):
+    """max_pool's backward builds the full transposed table of a matrix the batch brought none for and leaves it in the
+    active store; after the matrix changed in place, or was dropped and another allocated at its address, the backward must
+    scatter along the new matrix.  Reference: float64 index_add_ of dy along the argmax; bar: 1e-5 of its maximum"""
+    from weasal_amd import ops
+    nq, h, ns, c = 2000, 8, 300, 32
+    torch.manual_seed(11)
+    x = torch.randn(ns, c, device=gpu, requires_grad=True)
+    dy = torch.randn(nq, c, device=gpu)
+    first, second = (torch.rand(nq, ns, device=gpu).argsort(dim=1)[:, :h].contiguous() for _ in range(2))      # no support twice in a row
+
+    def check(inds):
+        y = ops.max_pool(x, inds)
+        dx, = torch.autograd.grad(y, x, dy)
+        vals = x.detach()[inds]                                                  # [nq, h, c]
+        arg = torch.gather(inds[:, :, None].expand(-1, -1, c), 1, vals.argmax(dim=1, keepdim=True))[:, 0]      # [nq, c]
+        assert torch.equal(y.detach(), vals.max(dim=1).values)
+        want = torch.zeros(ns * c, dtype=torch.float64, device=gpu)
+        want = want.index_add_(0, (arg * c + torch.arange(c, device=gpu)).reshape(-1), dy.double().reshape(-1)).view(ns, c)
+        assert float((dx.double() - want).abs().max()) <= 1e-5 * float(want.abs().max())
+
+    pool = torch.cuda.MemPool()             # a private pool: the next same-size request gets the freed block back
+    with torch.cuda.use_mem_pool(pool):
+        M = torch.empty_like(first)
+    M.copy_(first)
+    check(M)
+    old = ops.transposed_table(M, ns)
+    assert ops.transposed_table(M, ns) is old            # held for M itself
+    addr, version = M.data_ptr(), M._version
+    if how == "recycled":
+        del M
+        with torch.cuda.use_mem_pool(pool):
+            U = torch.empty((nq, h), dtype=torch.int64, device=gpu)
+        assert U.data_ptr() == addr          # precondition: the address of the matrix the table was built for is recycled
+    else:
+        U = M
+    U.copy_(second)
+    assert U.data_ptr() == addr and (how == "recycled" or U._version != version)
+    check(U)
+    assert ops.transposed_table(U, ns) is not old
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # ... while the fast paths still apply where they should
 # ---------------------------------------------------------------------------------------------------------------------
@@ -406,4 +449,37 @@ def test_clear_batch_hints_drops_every_hint(gpu):
     ops.clear_batch_hints()
     assert ops._grid_for(batch.neighbors[0]) is None and ops.sorted_rows_radius(batch.neighbors[0]) is None
     assert ops._pool_orders_for(batch.pools[0]) == (None, None)
-    assert not ops._tables and not ops._col0_tables
+    assert not ops.active_hints().tables()
+
+
+def test_one_route_function_serves_the_callers(gpu, monkeypatch):
+    """the dX route of a KPConv backward comes from ops.dx_route: the grid walk the batch's max_count dictates on the
+    self-query matrix, the transposed table on the pooling matrix (not a self-query)"""
+    from weasal_amd import config as wcfg, ops, pyramid
+    from weasal_amd.blocks import KPConv
+    cfg = wcfg.DALESDeformF32Config()
+    rng = np.random.default_rng(9)
+    n = 2500
+    pts = rng.uniform(-3, 3, size=(n, 3)).astype(np.float32)
+    P = torch.from_numpy(pts).to(gpu)
+    np.random.seed(0)
+    batch = pyramid.build_batch(cfg, P, torch.ones(n, 3, device=gpu), torch.zeros(n, dtype=torch.int64, device=gpu),
+                                np.array([n], np.int32), [200, 519, 472, 193, 34])
+    batch.activate()
+    calls = []
+    real = ops.dx_route
+    monkeypatch.setattr(ops, "dx_route", lambda *a, **kw: calls.append((a, real(*a, **kw))) or calls[-1][1])
+    np.random.seed(1)
+    torch.manual_seed(1)
+    conv = KPConv(15, 3, CI, CO, EXT, RC).to(gpu)
+    grid = batch.search_grids[0][1]
+    assert batch.search_grids[0][0] is batch.neighbors[0] and grid.max_count > 0
+    xg = torch.randn(n, CI, device=gpu, requires_grad=True)
+    conv(batch.points[0], batch.points[0], batch.neighbors[0], xg).square().sum().backward()
+    assert len(calls) == 1 and calls[0][0][0] is batch.neighbors[0]
+    assert calls[0][1] == (ops.QUEUE_GRID if grid.max_count > ops.GRID_NARROW_MAX else ops.SLAB_GRID, grid)
+    del calls[:]
+    xg = torch.randn(n, CI, device=gpu, requires_grad=True)
+    conv(batch.points[1], batch.points[0], batch.pools[0], xg).square().sum().backward()
+    assert len(calls) == 1 and calls[0][0][0] is batch.pools[0]
+    assert calls[0][1] == (ops.TABLE, None)

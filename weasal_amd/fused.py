@@ -110,7 +110,7 @@ def _scratch(nbytes, device):
 
 class _Geom:
     """geometry + widths of one block call (plain Python object carried through the autograd node)"""
-    __slots__ = ("q_pts", "s_pts", "inds", "kp", "extent", "order_q", "order_s", "grid", "table", "in_dim", "conv_in",
+    __slots__ = ("q_pts", "s_pts", "inds", "kp", "extent", "order_q", "order_s", "dx_route", "grid", "table", "in_dim", "conv_in",
                  "conv_out", "out_dim", "strided", "slope", "has", "rows_sorted", "infer", "skip_slot", "link_in", "link_out")
 
     def fill(self, d):
@@ -337,15 +337,10 @@ _KPCONV_GATHER = ops.kpconv_gather         # (oracle.kpconv_ref.cpu_reference_mo
 def _geometry(conv, q_pts, s_pts, inds, strided):
     g = _Geom()
     g.q_pts, g.s_pts = ops._f32c(q_pts), ops._f32c(s_pts)
-    inds = inds.contiguous()
-    g.inds = inds if inds.dtype == torch.int64 else inds.to(torch.int64)
+    g.inds = ops._as_index(inds)
     g.kp, g.extent = conv.kernel_points, conv.KP_extent
     g.order_q, g.order_s = ops._order_for(g.q_pts), ops._order_for(g.s_pts)
-    nq, ns = g.q_pts.shape[0], g.s_pts.shape[0]
-    self_query = nq == ns and g.q_pts.data_ptr() == g.s_pts.data_ptr()
-    grid = ops._grid_for(g.inds) if self_query else None
-    # (the block calls know the slab form of the grid backward only: rows up to 128 neighbours)
-    g.grid = grid if (grid is not None and grid.ns == ns and grid.max_count <= ops.GRID_NARROW_MAX) else None
+    g.dx_route, g.grid = ops.dx_route(g.inds, g.q_pts, g.s_pts, "block")
     g.table = None
     g.skip_slot = None
     g.link_in = g.link_out = None
@@ -379,7 +374,7 @@ def simple_block(block, x, batch, q_pts, s_pts, inds):
     g.in_dim = g.conv_in = conv.in_channels
     g.conv_out = g.out_dim = conv.out_channels
     g.slope = 0.1
-    if torch.is_grad_enabled() and x.requires_grad and g.grid is None:
+    if torch.is_grad_enabled() and x.requires_grad and g.dx_route == ops.TABLE:
         g.table = ops.transposed_table(g.inds, g.s_pts.shape[0])
     if getattr(batch, "skip_slot", None) is None:      # (a skip tensor has a second reader this block knows nothing about)
         g.link_in = _link_in(batch, x)
@@ -399,7 +394,7 @@ def resnetb_block(block, x, batch, q_pts, s_pts, inds):
         slot.armed = True
     g.in_dim, g.conv_in, g.conv_out, g.out_dim = block.in_dim, conv.in_channels, conv.out_channels, block.out_dim
     g.slope = 0.1
-    if torch.is_grad_enabled() and (g.grid is None or strided):       # (only a backward reads the table)
+    if torch.is_grad_enabled() and (g.dx_route == ops.TABLE or strided):       # (only a backward reads the table)
         g.table = ops.transposed_table(g.inds, g.s_pts.shape[0])
     u1 = block.unary1 if isinstance(block.unary1, torch.nn.Module) and hasattr(block.unary1, "mlp") else None
     us = block.unary_shortcut if hasattr(block.unary_shortcut, "mlp") else None
@@ -489,8 +484,7 @@ def upunary_eligible(x, skip, unary):
 def upunary(x, skip, unary, ups, drop=None, batch=None):
     """drop = (p, seed): nn.Dropout(p) applied to the step's output inside its last epilogue (the bits of ops.dropout with that
     seed); needs the unary's LeakyReLU"""
-    ups = ups.contiguous()
-    ups = ups if ups.dtype == torch.int64 else ups.to(torch.int64)
+    ups = ops._as_index(ups)
     table = ops.col0_table(ups, x.shape[0]) if torch.is_grad_enabled() else None      # (only the backward reads it)
     links = [_link_in(batch, x) if batch is not None else None, None]
     if drop is not None:

@@ -5,15 +5,14 @@ function below launches hand-written HIP kernels from libweasal_hip.so through c
 torch's current stream.  CPU tensors are rejected -- there is no CPU path in the product
 (the CPU restatement lives in oracle/ and is test infrastructure).
 """
-import collections
 import os
-import weakref
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check, current_stream, ptr
+from .hints import BatchHints
 
 # optional launch timer (bench.py): an object with begin(key) -> token / end(token); records HIP
 # events on the current stream around selected kernel launches.  None = no overhead.
@@ -51,8 +50,8 @@ def _f32c(t):
 
 
 # ------------------------------------------------------------------------------------------------
-# transposed neighbour tables, cached per index tensor (one per layer and batch; every block of
-# the layer and both pooling helpers reuse it)
+# transposed neighbour tables (one per index matrix and batch; every block of the layer and both
+# pooling helpers reuse it: transposed_table / col0_table below)
 # ------------------------------------------------------------------------------------------------
 class TransposedTable:
     __slots__ = ("offsets", "pairs", "nq", "h", "ns")
@@ -78,99 +77,61 @@ class TransposedTable:
         return t
 
 
-_tables = collections.OrderedDict()
-_TABLES_MAX = 32
+# ------------------------------------------------------------------------------------------------
+# index hints: what the batch being trained on knows about ONE index tensor (its tables, its search grid, that its rows are
+# sorted, its pooling orders) and about its point sets (scheduling orders).  They live in one hints.BatchHints, the active
+# store: PyramidBatch.activate installs the batch's own, clear_batch_hints an empty one.  A hint answers only for the tensor
+# object it was registered with, at the `_version` it had then (hints.BatchHints.get: a stale hint makes the kernels do the
+# wrong thing without any error).  The functions below are thin reads of the active store.
+# ------------------------------------------------------------------------------------------------
+_active = BatchHints()
+
+GRID_BACKWARD = os.environ.get("WEASAL_GRID_BACKWARD", "1") != "0"       # A/B switch (diagnostics, tests)
+SORTED_ROW_CUTOFF = os.environ.get("WEASAL_ROW_CUTOFF", "1") != "0"      # A/B switch (diagnostics, tests)
+GRID_NARROW_MAX = 128      # rows up to this length: the slab form of the grid backward (ws_kpconv_gather_bwd_x_grid); wider: _wide
 
 
-def transposed_table(inds, ns):
-    """Table for `inds` [nq,h] over `ns` supports, cached per index tensor.  The entry keeps a
-    reference to the tensor, so its memory (the cache key) cannot be recycled while cached; the
-    cache is a small LRU (a batch needs 3 tables per layer)."""
-    key = (inds.data_ptr(), tuple(inds.shape), ns, inds._version)
-    hit = _tables.get(key)
-    if hit is not None:
-        _tables.move_to_end(key)
-        return hit[1]
-    table = TransposedTable(inds, ns)
-    _tables[key] = (inds, table)
-    while len(_tables) > _TABLES_MAX:
-        _tables.popitem(last=False)
-    return table
+def install_hints(store):
+    """make `store` (a hints.BatchHints) the active one: replaces everything the previous batch brought or built"""
+    global _active
+    _active = store
+
+
+def active_hints():
+    return _active
+
+
+def clear_batch_hints():
+    """forget every hint (sorted rows, search grids, pooling and point orders, transposed tables): for a forward on a batch
+    that brings none (no PyramidBatch.activate), so that nothing of the previous batch applies to it"""
+    install_hints(BatchHints())
+
+
+clear_point_orders = clear_batch_hints      # (the orders live in the same store: there is one clearer)
 
 
 def clear_table_cache():
-    _tables.clear()
-    _col0_tables.clear()
+    _active.drop_tables()
 
 
-# ------------------------------------------------------------------------------------------------
-# index hints: what a registry knows about ONE index tensor (its table, its search grid, that its rows are sorted).  The
-# dictionaries are keyed by (data_ptr, shape) for an O(1) lookup, but an entry only answers for the tensor object it was
-# registered with, at the `_version` it had then: a matrix built later at a recycled address, or the same matrix changed in
-# place, gets nothing (a stale hint makes the kernels do the wrong thing without any error).
-# ------------------------------------------------------------------------------------------------
-def _hint_entry(t, payload):
-    return (weakref.ref(t), t._version, payload)
-
-
-def _hint(registry, key, t):
-    """payload of `registry[key]` if it was registered for `t` itself at its current version, else None"""
-    hit = registry.get(key)
-    if hit is None or hit[0]() is not t or hit[1] != t._version:
-        return None
-    return hit[2]
-
-
-_col0_tables = {}     # (inds.data_ptr(), shape, ns) -> hint entry: table of the first column (closest_pool backward)
-
-
-def col0_table(inds, ns):
-    """transposed table of the FIRST column of `inds` (closest_pool / nearest upsampling backward), cached per index
-    tensor like the full tables"""
-    key = (inds.data_ptr(), tuple(inds.shape), ns)
-    table = _hint(_col0_tables, key, inds)
-    if table is not None:
-        return table
-    table = TransposedTable(inds[:, :1].contiguous(), ns)
-    _col0_tables[key] = _hint_entry(inds, table)
+def _table(inds, ns, kind, build):
+    table = _active.get(inds, kind, ns)
+    if table is None:
+        # a matrix the batch brought no table for (operator tests, tools, a rare fallback): built now and held in the active
+        # store under the same rule, so it does not pin `inds` in device memory; the store bounds how many it holds
+        table = build()
+        _active.add(inds, ns, on_demand=True, **{kind: table})
     return table
 
 
-def install_tables(full, col0):
-    """pre-built tables of a prefetched batch (PyramidBatch.activate): `full` = [(inds, ns, table)],
-    `col0` = [(inds, ns, table of inds[:, :1])]"""
-    for inds, ns, table in full:
-        _tables[(inds.data_ptr(), tuple(inds.shape), ns, inds._version)] = (inds, table)
-    for inds, ns, table in col0:
-        _col0_tables[(inds.data_ptr(), tuple(inds.shape), ns)] = _hint_entry(inds, table)
+def transposed_table(inds, ns):
+    """table for `inds` [nq,h] over `ns` supports: the batch's pre-built one, else built once per index tensor"""
+    return _table(inds, ns, "table", lambda: TransposedTable(inds, ns))
 
 
-# ------------------------------------------------------------------------------------------------
-# scheduling orders: a spatially coherent permutation per point set (the cell order of the
-# neighbour search).  Pure performance hint -- results never depend on it.
-# ------------------------------------------------------------------------------------------------
-_orders = {}
-
-
-def register_point_order(points, order):
-    _orders[points.data_ptr()] = order
-
-
-def clear_point_orders():
-    _orders.clear()
-
-
-def set_point_orders(pairs):
-    """install the (points, order) pairs of the batch that is about to be trained on
-    (PyramidBatch.point_orders); replaces whatever the previous batch registered"""
-    _orders.clear()
-    for points, order in pairs:
-        _orders[points.data_ptr()] = order
-
-
-# grids of self-query searches (table-free KPConv backward): key = the index matrix the blocks pass in
-GRID_BACKWARD = os.environ.get("WEASAL_GRID_BACKWARD", "1") != "0"   # A/B switch (diagnostics, tests)
-_grids = {}
+def col0_table(inds, ns):
+    """transposed table of the FIRST column of `inds` (closest_pool / nearest upsampling backward), held like the full tables"""
+    return _table(inds, ns, "col0_table", lambda: TransposedTable(inds[:, :1].contiguous(), ns))
 
 
 class SearchGrid:
@@ -182,55 +143,17 @@ class SearchGrid:
         return (self.blob, self.key_last, self.overflow)
 
 
-_pool_orders = {}
-
-
-def set_pool_orders(triples):
-    """[(pooling index matrix [Nq, H], cell order of its queries or None, cell order of its supports or None)]: scheduling hints
-    of ops.max_pool for the batch about to be trained on (PyramidBatch.activate); results never depend on them"""
-    _pool_orders.clear()
-    for inds, oq, osup in triples:
-        if isinstance(inds, torch.Tensor) and inds.dim() == 2 and inds.shape[0] > 0:
-            _pool_orders[(inds.data_ptr(), tuple(inds.shape))] = _hint_entry(inds, (oq, osup))
-
-
-def _pool_orders_for(inds):
-    return _hint(_pool_orders, (inds.data_ptr(), tuple(inds.shape)), inds) or (None, None)
-
-
-def set_search_grids(pairs):
-    """install the (index matrix, SearchGrid) pairs of the batch about to be trained on (PyramidBatch.activate)"""
-    _grids.clear()
-    for inds, grid in pairs:
-        _grids[(inds.data_ptr(), tuple(inds.shape))] = _hint_entry(inds, grid)
-
-
-_sorted_rows = {}
-
-
-def set_sorted_rows(pairs):
-    """[(index matrix, search radius)]: matrices whose rows are sorted by distance from the query (the output of the radius
-    search), installed by PyramidBatch.activate for the batch about to be trained on.  Where the search radius exceeds the
-    reach of a layer's kernel points (the deformable radius of datasets/common.py:500-502) the linear-influence gather kernels
-    stop each row at that reach (exact: the skipped influences are zeros; include/weasal_hip.h `rows_sorted`)."""
-    _sorted_rows.clear()
-    for m, radius in pairs:
-        if isinstance(m, torch.Tensor) and m.dim() == 2 and m.shape[0] > 0:
-            _sorted_rows[(m.data_ptr(), tuple(m.shape))] = _hint_entry(m, float(radius))
-
-
-def clear_batch_hints():
-    """forget every hint a batch installed (sorted rows, search grids, pooling orders, transposed tables): for a forward on a
-    batch that brings none (no PyramidBatch.activate), so that nothing of the previous batch applies to it"""
-    _sorted_rows.clear()
-    _grids.clear()
-    _pool_orders.clear()
-    clear_table_cache()
+def _grid_for(inds):
+    """grid of the self-query search that wrote `inds` (table-free KPConv backward)"""
+    return _active.get(inds, "grid") if GRID_BACKWARD else None
 
 
 def sorted_rows_radius(inds):
-    """search radius of a registered distance-sorted matrix, None for anything else"""
-    return _hint(_sorted_rows, (inds.data_ptr(), tuple(inds.shape)), inds) if SORTED_ROW_CUTOFF else None
+    """search radius of a registered distance-sorted matrix (the output of the radius search), None for anything else.
+    Where it exceeds the reach of a layer's kernel points (the deformable radius of datasets/common.py:500-502) the
+    linear-influence gather kernels stop each row at that reach (exact: the skipped influences are zeros;
+    include/weasal_hip.h `rows_sorted`)."""
+    return _active.get(inds, "radius") if SORTED_ROW_CUTOFF else None
 
 
 def rows_cutoff_pays(inds, conv_radius):
@@ -240,19 +163,62 @@ def rows_cutoff_pays(inds, conv_radius):
     return r is not None and r > 1.2 * float(conv_radius)
 
 
-SORTED_ROW_CUTOFF = os.environ.get("WEASAL_ROW_CUTOFF", "1") != "0"      # A/B switch (diagnostics, tests)
-GRID_NARROW_MAX = 128      # rows up to this length: the slab form of the grid backward (ws_kpconv_gather_bwd_x_grid); wider: _wide
+def _pool_orders_for(inds, ns=None):
+    """(cell order of the queries of pooling matrix `inds`, cell order of its `ns` supports): scheduling hints of max_pool,
+    each None unless it fits; results never depend on them"""
+    oq, osup = _active.get(inds, "pool_orders") or (None, None)
+    if oq is not None and oq.numel() != inds.shape[0]:
+        oq = None
+    if osup is not None and osup.numel() != ns:
+        osup = None
+    return oq, osup
 
 
-def _grid_for(inds):
-    return _hint(_grids, (inds.data_ptr(), tuple(inds.shape)), inds) if GRID_BACKWARD else None
+def register_point_order(points, order):
+    """scheduling order of one point set: a spatially coherent permutation (the cell order of the neighbour search).  Pure
+    performance hint -- results never depend on it."""
+    _active.add_point_order(points, order)
 
 
 def _order_for(points):
-    o = _orders.get(points.data_ptr())
-    if o is not None and o.numel() == points.shape[0] and o.device == points.device:
-        return o
-    return None
+    return _active.order_for(points)
+
+
+def _as_index(inds):
+    """the index matrix as the kernels read it: contiguous int64 (itself when it already is: the hints are per tensor object)"""
+    inds = inds.contiguous()
+    return inds if inds.dtype == torch.int64 else inds.to(torch.int64)
+
+
+SLAB_GRID, QUEUE_GRID, TABLE = "slab grid walk", "queue grid walk", "transposed table"
+
+
+def dx_route(inds, q_pts, s_pts, caller, rigid_linear_sum=True):
+    """How dX of a gather over `inds` is computed -> (route, SearchGrid or None).  `caller` says what its kernels can do:
+    "generic" (kpconv_gather), "packed" (kpconv_gather_def: the packed deformable operator), "block" (fused block calls).
+
+      no grid for `inds` (not a self-query, GRID_BACKWARD off, grid.ns != ns)        every caller     TABLE
+      grid, rows <= GRID_NARROW_MAX                                                  generic, block   SLAB_GRID  (any influence)
+      grid, rows >  GRID_NARROW_MAX, rigid linear / sum                              generic          QUEUE_GRID
+      grid, rows >  GRID_NARROW_MAX, deformed / modulated / constant / gaussian /    generic          TABLE
+                                     closest
+      grid, rows >  GRID_NARROW_MAX                                                  block            TABLE      (slab form only)
+      grid, any width                                                                packed           QUEUE_GRID
+
+    The queue form covers rigid linear / sum only, unless the caller is the packed deformable path, whose queue kernel reads
+    the packed kernel points."""
+    ns = s_pts.shape[0]
+    self_query = q_pts.shape[0] == ns and q_pts.data_ptr() == s_pts.data_ptr()
+    grid = _grid_for(inds) if self_query else None
+    if grid is None or grid.ns != ns:
+        return TABLE, None
+    if caller == "packed":
+        return QUEUE_GRID, grid
+    if grid.max_count <= GRID_NARROW_MAX:
+        return SLAB_GRID, grid
+    if caller == "generic" and rigid_linear_sum:
+        return QUEUE_GRID, grid
+    return TABLE, None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -309,17 +275,15 @@ class _KPConvGather(torch.autograd.Function):
         dx = d_dkp = d_mod = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            grid = _grid_for(inds) if (nq == ns and q_pts.data_ptr() == s_pts.data_ptr()) else None
+            route, grid = dx_route(inds, q_pts, s_pts, "generic",
+                                   dkp is None and mod is None and influence == 0 and aggregation == 0)
             tok = _tbegin("kpconv_gather_bwd_x", nq, h, ci)
-            wide = grid is not None and grid.max_count > GRID_NARROW_MAX
-            if wide and not (dkp is None and mod is None and influence == 0 and aggregation == 0):
-                grid = None          # the queue form of the grid backward covers linear / sum only: transposed table
-            if grid is not None and grid.ns == ns and wide:
+            if route == QUEUE_GRID:
                 check(lib.ws_kpconv_gather_bwd_x_grid_wide(ptr(s_pts), ns, ptr(grid.blob), grid.nb, grid.cells, ptr(grid.key_last),
                                                            grid.radius, ptr(dwf), ci, ptr(kernel_points), k, None, None, extent,
                                                            ptr(_order_for(s_pts)), ptr(inds), h, ptr(dx), 1 if bf else 0,
                                                            current_stream()))
-            elif grid is not None and grid.ns == ns:
+            elif route == SLAB_GRID:
                 # self-query layer: incoming pairs re-derived from the search grid, no transposed table
                 check(f_grid(ptr(s_pts), ns, ptr(grid.blob), grid.nb, grid.cells,
                                                       ptr(grid.key_last), grid.radius, ptr(dwf), ci, ptr(kernel_points), k,
@@ -346,14 +310,11 @@ class _KPConvGather(torch.autograd.Function):
 def kpconv_gather(x, q_pts, s_pts, inds, kernel_points, extent, influence="linear", aggregation="sum",
                   deformed_kp=None, modulations=None, want_min_d2=False, rows_sorted=False):
     """Fused neighbour gather + kernel-point influence + aggregate -> wf [nq, K, ci] (and min_d2).
-    rows_sorted: the rows of `inds` are sorted by distance from their query (see set_sorted_rows)."""
+    rows_sorted: the rows of `inds` are sorted by distance from their query (see sorted_rows_radius)."""
     q_pts = _f32c(q_pts)
     s_pts = _f32c(s_pts)
     kernel_points = _f32c(kernel_points)
-    inds = inds.contiguous()
-    if inds.dtype != torch.int64:
-        inds = inds.to(torch.int64)
-    return _KPConvGather.apply(x, deformed_kp, modulations, q_pts, s_pts, inds, kernel_points, extent,
+    return _KPConvGather.apply(x, deformed_kp, modulations, q_pts, s_pts, _as_index(inds), kernel_points, extent,
                                INFLUENCE[influence], AGGREGATION[aggregation], want_min_d2, bool(rows_sorted))
 
 
@@ -452,9 +413,9 @@ class _KPConvGatherDef(torch.autograd.Function):
         dx = d_kp4 = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            grid = _grid_for(inds) if (nq == ns and q_pts.data_ptr() == s_pts.data_ptr()) else None
+            route, grid = dx_route(inds, q_pts, s_pts, "packed")
             tok = _tbegin("kpconv_gather_bwd_x", nq, h, ci)
-            if grid is not None and grid.ns == ns:
+            if route == QUEUE_GRID:
                 check(lib.ws_kpconv_gather_bwd_x_grid_wide(ptr(s_pts), ns, ptr(grid.blob), grid.nb, grid.cells, ptr(grid.key_last),
                                                            grid.radius, ptr(dwf), ci, None, k, ptr(kp4), ptr(rmax), extent,
                                                            ptr(_order_for(s_pts)), ptr(inds), h, ptr(dx), bf, current_stream()))
@@ -476,11 +437,8 @@ class _KPConvGatherDef(torch.autograd.Function):
 
 def kpconv_gather_def(x, kp4, q_pts, s_pts, inds, extent, kp_rmax=None, rows_sorted=False):
     """deformable fast path: -> (wf [nq,K,ci], min_d2 [nq,K]); kp_rmax: deform_prepare's device scalar (bounds the grid
-    backward's candidates); rows_sorted: see set_sorted_rows"""
-    inds = inds.contiguous()
-    if inds.dtype != torch.int64:
-        inds = inds.to(torch.int64)
-    return _KPConvGatherDef.apply(x, kp4, _f32c(q_pts), _f32c(s_pts), inds, float(extent), kp_rmax, bool(rows_sorted))
+    backward's candidates); rows_sorted: see sorted_rows_radius"""
+    return _KPConvGatherDef.apply(x, kp4, _f32c(q_pts), _f32c(s_pts), _as_index(inds), float(extent), kp_rmax, bool(rows_sorted))
 
 
 class _P2PRegularizer(torch.autograd.Function):
@@ -830,11 +788,7 @@ class _MaxPool(torch.autograd.Function):
         nq, h = inds.shape
         out = torch.empty((nq, c), dtype=x.dtype, device=x.device)
         arg = torch.empty((nq, c), dtype=torch.int32, device=x.device)
-        oq, osup = _pool_orders_for(inds)      # scheduling hints (PyramidBatch.activate)
-        if oq is not None and oq.numel() != nq:
-            oq = None
-        if osup is not None and osup.numel() != ns:
-            osup = None
+        oq, osup = _pool_orders_for(inds, ns)      # scheduling hints (PyramidBatch.activate)
         check(_by_dtype(lib, "ws_max_pool_fwd_ordered", x)(ptr(x), ns, c, ptr(inds), nq, h, ptr(out), ptr(arg), ptr(oq), current_stream()))
         ctx.save_for_backward(arg, inds)
         ctx.ns = ns
@@ -883,11 +837,6 @@ class _ClosestPool(torch.autograd.Function):
         check(_by_dtype(lib, "ws_closest_pool_bwd", dy)(ptr(dy), nq, 1, c, ptr(table.offsets), ptr(table.pairs), ctx.ns, ptr(dx),
                                       current_stream()))
         return dx, None
-
-
-def _as_index(inds):
-    inds = inds.contiguous()
-    return inds if inds.dtype == torch.int64 else inds.to(torch.int64)
 
 
 def max_pool(x, inds):

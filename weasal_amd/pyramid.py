@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .hints import BatchHints
 from .kernel_points import create_3D_rotations
 
 
@@ -416,6 +417,7 @@ class PyramidBatch:
         self.tables = []                         # pre-built transposed tables [(inds, ns, table)] (build_tables)
         self.col0_tables = []
         self.ready = None                        # event recorded on the stream that built the batch
+        self._register()
 
     def _tensors(self):
         for name in ("points", "neighbors", "pools", "upsamples", "lengths"):
@@ -440,11 +442,11 @@ class PyramidBatch:
         stream that builds the batch -- they are off the training stream's critical path."""
         self.tables, self.col0_tables = [], []
         L = len(self.points)
-        have_grid = {m.data_ptr() for m, _ in self.search_grids} if ops.GRID_BACKWARD else set()
+        gridded = [m for m, _ in self.search_grids] if ops.GRID_BACKWARD else []
         for l in range(L):
             ns = self.points[l].shape[0]
             for mat in (self.neighbors[l], self.pools[l]):
-                if mat.data_ptr() in have_grid:
+                if any(mat is m for m in gridded):
                     continue         # KPConv is the only reader of neighbors[l] and goes through the grid
                 if mat.shape[0] > 0 and mat.is_cuda:
                     self.tables.append((mat, ns, ops.TransposedTable(mat, ns)))
@@ -452,6 +454,24 @@ class PyramidBatch:
             if up.shape[0] > 0 and up.is_cuda and l + 1 < L:
                 nc = self.points[l + 1].shape[0]
                 self.col0_tables.append((up, nc, ops.TransposedTable(up[:, :1].contiguous(), nc)))
+        return self._register()
+
+    def _register(self):
+        """fill self.hints from the lists above: the store is how the operators find them once activate() has installed it.
+        Host work only; called where the batch is built."""
+        h = self.hints = BatchHints()
+        for points, order in self.point_orders:
+            h.add_point_order(points, order)
+        for mat, radius in self.search_radii:
+            h.add(mat, radius=float(radius))     # rows as the radius search wrote them: sorted by distance
+        for mat, grid in self.search_grids:
+            h.add(mat, grid=grid)
+        for l in range(len(self.points) - 1):    # a pooling matrix is walked in the cell orders of its queries and its supports
+            h.add(self.pools[l], pool_orders=(h.order_for(self.points[l + 1]), h.order_for(self.points[l])))
+        for mat, ns, table in self.tables:
+            h.add(mat, ns, table=table)
+        for mat, ns, table in self.col0_tables:
+            h.add(mat, ns, col0_table=table)
         return self
 
     def _map(self, fn):
@@ -472,8 +492,9 @@ class PyramidBatch:
 
     def activate(self, stream=None):
         """Make the batch usable on `stream` (default: the current one): wait for the stream that built
-        it, tell the caching allocator about the second user, install the scheduling orders.  Called by
-        KPFCNN.forward; a no-op for batches built on the same stream."""
+        it, tell the caching allocator about the second user, make the batch's hints (filled where the batch was built) the
+        active store of ops: everything of the previous batch is replaced.  Called by KPFCNN.forward; the stream part is a
+        no-op for batches built on the same stream."""
         if self.features.is_cuda:
             stream = stream or torch.cuda.current_stream(self.features.device)
             if self.ready is not None:
@@ -489,14 +510,7 @@ class PyramidBatch:
                     if isinstance(t, torch.Tensor) and t.is_cuda:
                         t.record_stream(stream)
                 self.ready = None
-            ops.set_point_orders(self.point_orders)
-            by_points = {p.data_ptr(): o for p, o in self.point_orders}
-            ops.set_pool_orders([(self.pools[l], by_points.get(self.points[l + 1].data_ptr()), by_points.get(self.points[l].data_ptr()))
-                                 for l in range(len(self.points) - 1)])
-            ops.set_sorted_rows(self.search_radii)     # rows as the radius search wrote them: sorted by distance
-            ops.set_search_grids(self.search_grids)
-            ops.clear_table_cache()              # tables belong to one batch
-            ops.install_tables(self.tables, self.col0_tables)
+            ops.install_hints(self.hints)
         return self
 
 
@@ -527,6 +541,7 @@ def build_batch(config, points, features, labels, lengths, neighborhood_limits=(
         batch.tables, batch.col0_tables = tables["full"], tables["col0"]
     elif with_tables and points.is_cuda:
         batch.build_tables()
+    batch._register()
     if points.is_cuda:
         batch.ready = torch.cuda.Event()
         batch.ready.record(torch.cuda.current_stream(points.device))

@@ -678,6 +678,35 @@ int ws_topk_select(const double* score, int64_t n, const int64_t* h_exclude, int
                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pseudo-label refinement on the votes of a pass over the training clouds (csrc/refine.hip): pseudoLabel_refinement.py.
+ * ws_weak_mask: :63-68 -- mask [n] uint32, bit k set while class k survives: every word starts as the low c bits
+ *   (weak = ones) and takes the AND of anchor_bits[a] (the 0/1 label row of anchor a, bit k = column k, packed by the
+ *   caller) for every selected anchor a that lists the point (weak[idx_a] *= lb_a).  Anchors as CSR like
+ *   ws_al_anchor_scores (anchor_ptr [n_anchors + 1], anchor_idx [nnz], int64).  anchor_sel [n_sel] int64: the rows that
+ *   take part, any order, duplicates allowed (the dictionary after active.select_anchors); NULL = all n_anchors rows
+ *   (n_sel is then ignored and must be 0); non-NULL with n_sel = 0 = none.  A duplicate index applies once (AND).
+ * ws_refine_labels: :123-151 -- for point i < n, r = proj[i] (int32; NULL: r = i, and m >= n is required) selects the
+ *   row of probs [m, c] float32 and preds [m] int32 (:123-125, :136, :144); mask [n] is NOT projected.
+ *   labels[i] = (double) max_k(mask bit k ? probs[r, k] : 0) < thr ? no_label : preds[r]  (:137, :143-145; thr is the
+ *   host's double 0.01 * threshold; for votes, which are >= 0, the maximum over the surviving classes, 0 without any);
+ *   counts[v] += 1 for every written label v in [0, n_counts) (:148-151: by value, after emptying), int64, ACCUMULATED:
+ *   one buffer serves all tiles, the caller zeroes it once.  n_counts <= 4096, else WS_ERR_UNSUPPORTED.
+ * Both: c <= 32, else WS_ERR_UNSUPPORTED; c < 1, a negative size or a NULL required pointer: WS_ERR_INVALID; n == 0:
+ *   WS_OK and nothing is queued; all found before the device is touched.  Every kernel is queued on `stream`; nothing
+ *   synchronises and nothing is read back.  An index outside its range -- anchor_idx outside [0, n), anchor_sel outside
+ *   [0, n_anchors), proj outside [0, m) -- is never dereferenced: the entry is skipped (a bad proj[i] writes no_label
+ *   and is counted in no class) and status[WS_REFINE_BAD_*] += 1.  status: 3 int64 words on the device, accumulated
+ *   like counts; the caller zeroes them and reads them with the counts.
+ * ------------------------------------------------------------------------------------------ */
+enum { WS_REFINE_BAD_ANCHOR_IDX = 0, WS_REFINE_BAD_ANCHOR_SEL = 1, WS_REFINE_BAD_PROJ = 2, WS_REFINE_STATUS_WORDS = 3 };
+int ws_weak_mask(uint32_t* mask, int64_t n, int32_t c, const int64_t* anchor_ptr, const int64_t* anchor_idx, int64_t nnz,
+                 const uint32_t* anchor_bits, int64_t n_anchors, const int64_t* anchor_sel, int64_t n_sel, int64_t* status,
+                 void* stream);
+int ws_refine_labels(const float* probs, const int32_t* preds, int64_t m, int32_t c, const uint32_t* mask, const int32_t* proj,
+                     int64_t n, double thr, int32_t no_label, int32_t* labels, int64_t* counts, int32_t n_counts, int64_t* status,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The sphere sampler on tiles resident in device memory: datasets/DALES_PseudoLabel.py:265-518 (`potential_item`) with
  * datasets/common.py:252-334 (`augmentation_transform`), a whole batch per call and no host round trip per sphere.
  *

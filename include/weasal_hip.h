@@ -707,6 +707,70 @@ int ws_refine_labels(const float* probs, const int32_t* preds, int64_t m, int32_
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The weak-label anchors of one tile (csrc/anchors.hip): utils/anchors.py, driven by datasets/DALES_WeakLabel.py:201-269.
+ * Distances: a float32 coordinate widened to float64, d = p - a per axis, d2 = (dx*dx + dy*dy) + dz*dz, every product
+ *   and sum rounded (no FMA); inside iff d2 <= radius*radius (sklearn's query_radius keeps the boundary).
+ * h_grid: HOST double [7] = { origin x, y, z, cell, nx, ny, nz } of a uniform grid over the searched centres, cell >=
+ *   radius, z the fastest axis; cell_start int32 [nx*ny*nz + 1] and cell_item int32 [items] list the items of every cell.
+ *   The grid proposes candidates (27 cells), the comparison above decides.
+ * ws_anchor_bounds: utils/anchors.py:33-38 -- bounds [6] float32 on the device = { x min, x max, y min, y max, z min,
+ *   z max } of points [n,3]; n >= 1.
+ * ws_anchor_members_plan: :83-99 -- per input anchor a < a0 (anchors [a0,3] float64): counts[a] = the points inside
+ *   (query_radius, :87), bits[a] = OR of 1 << labels[i] over them (np.unique + cloud_labels, :94-98); slot [a0 + 1] = the
+ *   exclusive scan of (counts > 0), i.e. the index among the survivors (:91), ptr32 [a0 + 1] that of counts.
+ *   totals[WS_ANCHOR_TOTAL_ROWS] = survivors, [WS_ANCHOR_TOTAL_NNZ] = members in all, summed in 64 bits.  A label
+ *   outside [0, n_class) sets no bit and status[WS_ANCHOR_BAD_LABEL] += 1 per such point (the reference: IndexError).
+ *   n_class <= 32 and n, a0 < 2^31, else WS_ERR_UNSUPPORTED.  scratch: ws_anchor_scratch_bytes(a0).
+ * ws_anchor_members_fill: :91-103 -- after ONE host read of totals: kept [A] = the input index of every survivor, in
+ *   order; anchor_ptr [A + 1], anchor_idx [nnz] ascending inside every anchor (filled through atomic cursors, then sorted
+ *   per anchor: the same bytes on every run); centres [A,3]; anchor_bits [A].  cursor: int32 [a0] scratch.  nnz >= 2^31:
+ *   WS_ERR_CAPACITY (the offsets are planned in 32 bits).
+ * ws_anchor_pairs_plan / _fill: :114-121 -- the candidates of the overlap pass: positions s < t of the selection
+ *   (sel [n_sel] int64 anchor ids, duplicates allowed, DALES_WeakLabel.py:241-263; NULL: all n_anchors, n_sel =
+ *   n_anchors) whose centres are within `radius` (1.5 * sub_radius), same recipe.  The grid lists POSITIONS.
+ *   pair_cnt / pair_ptr [n_sel + 1]; totals[WS_ANCHOR_TOTAL_ROWS] = pairs; then pair_i / pair_j [n_pairs] int32 in
+ *   (s, t) lexicographic order.  A sel entry outside [0, n_anchors) has no pairs and status[WS_ANCHOR_BAD_SEL] += 1.
+ * ws_anchor_overlap_plan: :122-134 -- inter_cnt[p] = |list(i) & list(j)| when the label bits differ (:134), else 0;
+ *   new_slot / new_ptr [n_pairs + 1] their scans, sel_ptr [n_sel + 1] the scan of the selected lists' lengths;
+ *   totals = { new anchors, their members, members of the selection }.  scratch: ws_anchor_scratch_bytes(max(n_pairs,
+ *   n_sel)).  One wave per pair, the shorter list binary-searched in the longer.
+ * ws_anchor_overlap_fill: :130-138 -- after ONE host read of totals: rows [0, n_sel) of the output copy the selected
+ *   anchors (select_anchors, :145-160), rows n_sel + new_slot[p] are the new ones in pair order: members = the
+ *   intersection, ascending (:130, ballot + prefix popcount, no atomics); bits = AND (:137); centre = float64 mean of
+ *   the members' widened coordinates (:135; summed in a fixed order).  New anchors are never paired themselves.
+ * All: every kernel is queued on `stream`, nothing synchronises, nothing is read back; sizes are checked before the
+ *   device is touched.  status: WS_ANCHOR_STATUS_WORDS int64 on the device, accumulated; totals: WS_ANCHOR_TOTAL_WORDS
+ *   int64 on the device, rewritten by every plan.
+ * ------------------------------------------------------------------------------------------ */
+enum { WS_ANCHOR_BAD_LABEL = 0, WS_ANCHOR_BAD_SEL = 1, WS_ANCHOR_STATUS_WORDS = 2 };
+enum { WS_ANCHOR_TOTAL_ROWS = 0, WS_ANCHOR_TOTAL_NNZ = 1, WS_ANCHOR_TOTAL_BASE = 2, WS_ANCHOR_TOTAL_WORDS = 3 };
+int ws_anchor_bounds(const float* points, int64_t n, float* bounds, void* stream);
+int64_t ws_anchor_scratch_bytes(int64_t items);
+int ws_anchor_members_plan(const float* points, const int32_t* labels, int64_t n, int32_t n_class, const double* anchors, int64_t a0,
+                           double radius, const double* h_grid, const int32_t* cell_start, const int32_t* cell_item,
+                           int32_t* counts, int32_t* slot, int32_t* ptr32, uint32_t* bits, int64_t* totals, int64_t* status,
+                           void* scratch, void* stream);
+int ws_anchor_members_fill(const float* points, int64_t n, const double* anchors, int64_t a0, double radius, const double* h_grid,
+                           const int32_t* cell_start, const int32_t* cell_item, int32_t* counts, const int32_t* slot,
+                           const int32_t* ptr32, const uint32_t* bits, int64_t n_kept, int64_t nnz, int64_t* kept, int64_t* anchor_ptr,
+                           int64_t* anchor_idx, double* centres, uint32_t* anchor_bits, int32_t* cursor, void* stream);
+int ws_anchor_pairs_plan(const double* centres, int64_t n_anchors, const int64_t* sel, int64_t n_sel, double radius,
+                         const double* h_grid, const int32_t* cell_start, const int32_t* cell_item, int32_t* pair_cnt,
+                         int32_t* pair_ptr, int64_t* totals, int64_t* status, void* scratch, void* stream);
+int ws_anchor_pairs_fill(const double* centres, int64_t n_anchors, const int64_t* sel, int64_t n_sel, double radius,
+                         const double* h_grid, const int32_t* cell_start, const int32_t* cell_item, const int32_t* pair_ptr,
+                         int64_t n_pairs, int32_t* pair_i, int32_t* pair_j, void* stream);
+int ws_anchor_overlap_plan(const int64_t* anchor_ptr, const int64_t* anchor_idx, int64_t nnz, const uint32_t* anchor_bits,
+                           int64_t n_anchors, const int64_t* sel, int64_t n_sel, const int32_t* pair_i, const int32_t* pair_j,
+                           int64_t n_pairs, int32_t* inter_cnt, int32_t* new_slot, int32_t* new_ptr, int32_t* sel_ptr, int64_t* totals,
+                           void* scratch, void* stream);
+int ws_anchor_overlap_fill(const float* points, int64_t n, const int64_t* anchor_ptr, const int64_t* anchor_idx, int64_t nnz,
+                           const uint32_t* anchor_bits, const double* centres, int64_t n_anchors, const int64_t* sel, int64_t n_sel,
+                           const int32_t* pair_i, const int32_t* pair_j, int64_t n_pairs, const int32_t* inter_cnt,
+                           const int32_t* new_slot, const int32_t* new_ptr, const int32_t* sel_ptr, int64_t n_new, int64_t nnz_new,
+                           int64_t nnz_sel, int64_t* out_ptr, int64_t* out_idx, uint32_t* out_bits, double* out_centres, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The sphere sampler on tiles resident in device memory: datasets/DALES_PseudoLabel.py:265-518 (`potential_item`) with
  * datasets/common.py:252-334 (`augmentation_transform`), a whole batch per call and no host round trip per sphere.
  *

@@ -135,6 +135,17 @@ SIGNATURES = {
     "ws_topk_select": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "ws_weak_mask": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "ws_refine_labels": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i64, C.c_double, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "ws_anchor_bounds": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "ws_anchor_scratch_bytes": (_i64, [_i64]),
+    "ws_anchor_members_plan": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp]),
+    "ws_anchor_members_fill": (C.c_int, [_vp, _i64, _vp, _i64, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp]),
+    "ws_anchor_pairs_plan": (C.c_int, [_vp, _i64, _vp, _i64, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ws_anchor_pairs_fill": (C.c_int, [_vp, _i64, _vp, _i64, C.c_double, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ws_anchor_overlap_plan": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ws_anchor_overlap_fill": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                        _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ws_sampler_create": (C.c_int, [C.POINTER(_vp)]),
     "ws_sampler_destroy": (None, [_vp]),
     "ws_sampler_add_cloud": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),

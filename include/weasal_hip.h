@@ -544,6 +544,9 @@ typedef struct ws_kpblock {
                                             the kernel that writes the shortcut's share instead of by a pass of its own */
 } ws_kpblock;
 
+/* Scratch: the size queries return a multiple of 256 bytes (-1: the descriptor is refused, ws_last_error says why); the
+ * runs return WS_ERR_CAPACITY for any scratch_bytes below what the query returns for the same descriptor (size the
+ * buffer by the query, not by hand; the size depends on ws_block_group_rows).  The same holds for ws_upunary_*. */
 int64_t ws_kpblock_fwd_scratch_bytes(const ws_kpblock* d);
 int64_t ws_kpblock_bwd_scratch_bytes(const ws_kpblock* d);
 int ws_kpblock_fwd(const ws_kpblock* d, void* scratch, int64_t scratch_bytes, void* stream);

@@ -13,41 +13,21 @@
 // diagnostics switch (WEASAL_BLOCK_GATES=0): activation backward as separate passes instead of epilogue / store gates
 extern "C" int ws_block_gates = 1;
 extern "C" int ws_block_gather_residual = 1;   // decoder step: 1 = the upsampled rows are gathered by the last epilogue, 0 = written out first (A/B)
-// Diagnostics (WEASAL_BLOCK_SIDE_ROWS=<rows>): blocks with fewer query rows than this run their weight-gradient products
-// (dW = X^T dZ: leaves of the backward, nothing on the chain to dX waits for them) on a side stream next to the dX chain.
-// Default 0 = off: measured on the DALES step the deep levels' products are bound by the matrix cores and by their
-// fixed launch / prologue latency, not by idle CUs -- 12.21 ms per step with the side stream, 12.11 without.
-extern "C" int64_t ws_block_side_rows = 0;
+// A/B switch (WEASAL_BLOCK_GROUP_ROWS=<rows>): blocks / decoder steps with fewer rows than this issue their mutually independent
+// dense products as grouped launches (ws_priv_gemm_xb_group / ws_priv_gemm_xty_group): the weight-gradient products -- leaves
+// of the backward, nothing waits for them -- are collected and launched at the end of the call, the two products that read
+// dz ride together, and so do the two that read a block's input.  Every member keeps the plan it gets alone: results are
+// bit-identical, only the launch count changes.  0 = off: the single launches in their old order.  The limit exists for the
+// tall levels: deferring a leaf product there moves its read of a 205 MB gradient behind the KPConv backward's stream.
+// Measured on the DALES step it does not hurt -- 12.55 ms with a limit of 32 768 or 80 000 rows, 12.47 without one, 12.69
+// with the switch at 0 -- so the default is no limit.
+extern "C" int64_t ws_block_group_rows = (int64_t)1 << 62;
 // A/B switch (WEASAL_FUSED_INFER=0): forward-only blocks run gather + contraction as two launches like the training path
 extern "C" int ws_block_fused_infer = 1;
 // A/B switch (WEASAL_POOL_ORDER=0): the strided blocks' max-pool walks its rows by index instead of in cell order
 extern "C" int ws_block_pool_order = 1;
 
 namespace {
-
-// One side stream and a few events per device, created on first use and kept for the life of the process.
-struct Side {
-    hipStream_t st = nullptr;
-    hipEvent_t fork[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t join = nullptr;
-};
-int side_for_current_device(Side** out)
-{
-    static Side sides[16];
-    int dev = 0;
-    WS_HIP(hipGetDevice(&dev));
-    WS_REQUIRE(dev >= 0 && dev < 16, "device index %d out of range", dev);
-    Side& sd = sides[dev];
-    if (!sd.st) {
-        hipStream_t st;
-        WS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        for (auto& e : sd.fork) WS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        WS_HIP(hipEventCreateWithFlags(&sd.join, hipEventDisableTiming));
-        sd.st = st;
-    }
-    *out = &sd;
-    return WS_OK;
-}
 
 struct Arena {
     char* base;
@@ -62,6 +42,9 @@ struct Arena {
     }
     bool fits() const { return off <= cap; }
 };
+
+// what the size queries report and the runs require: the plan, rounded up to the arena's 256-byte step, plus one step
+inline int64_t arena_bytes(const Arena& ar) { return ((ar.off + 255) & ~(int64_t)255) + 256; }
 
 inline int64_t max3(int64_t a, int64_t b, int64_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
 
@@ -107,6 +90,44 @@ int linear_fwd(const Lin& l, const float* x, int64_t m, int64_t ldx, const float
         int rc__ = (call);      \
         if (rc__) return rc__;  \
     } while (0)
+
+inline bool grouped_rows(int64_t rows) { return ws_block_group_rows > 0 && rows > 0 && rows < ws_block_group_rows; }
+
+inline ws_xb_problem xb_problem(const float* x, int64_t m, int k, int64_t ldx, const float* b, int64_t brs, int64_t bcs, int n,
+                                const float* bias, const float* residual, int64_t ldr, int act, float slope, const float* gate_y,
+                                int64_t ldg, float gate_slope, float* y, int64_t ldy, void* scratch, int64_t scratch_bytes)
+{
+    ws_xb_problem q{};
+    q.x = x; q.m = m; q.k = k; q.ldx = ldx; q.b = b; q.b_row_stride = brs; q.b_col_stride = bcs; q.n = n;
+    q.bias = bias; q.residual = residual; q.ldr = ldr; q.act = act; q.slope = slope;
+    q.gate_y = gate_y; q.ldg = ldg; q.gate_slope = gate_slope;
+    q.y = y; q.ldy = ldy; q.scratch = scratch; q.scratch_bytes = scratch_bytes;
+    return q;
+}
+
+// the weight-gradient products of one call: launched one by one where they stand (grouping off), or collected and launched
+// together by flush().  Collected members need their operands untouched until flush() and a scratch each.
+struct Leaves {
+    bool on;
+    hipStream_t st;
+    ws_xty_problem q[4];
+    int n = 0;
+    Leaves(bool on_, hipStream_t st_) : on(on_), st(st_) {}
+    int add(const float* x, int64_t m, int k, int64_t ldx, const float* y, int nn, int64_t ldy, float* out, int64_t ldo, void* scratch,
+            int64_t scratch_bytes)
+    {
+        if (!on) return ws_priv_gemm_xty_pitched(x, m, k, ldx, y, nn, ldy, out, ldo > nn ? ldo : nn, scratch, st);
+        WS_REQUIRE(n < 4, "more than 4 collected weight-gradient products");
+        q[n++] = ws_xty_problem{x, m, k, ldx, y, nn, ldy, out, ldo, scratch, scratch_bytes};
+        return WS_OK;
+    }
+    int flush()
+    {
+        const int c = n;
+        n = 0;
+        return c ? ws_priv_gemm_xty_group(q, c, st) : WS_OK;
+    }
+};
 
 // ---- launch timer (bench.py: HIP events around the K3 launch, on the launch stream) --------------------------
 struct TimerRec { hipEvent_t a, b, c; int64_t nq; int32_t h, ci; };      // a .. b: the K3 launch, a .. c: K3 + the contraction
@@ -157,10 +178,23 @@ int kpblock_fwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
     float* sc = (d->w2 && d->ws) ? ar.take<float>(nq * d->out_dim) : nullptr;
     const int64_t tmp_bytes = kpblock_tmp_fwd(d);
     void* tmp = ar.take<char>(tmp_bytes > 16 ? tmp_bytes : 16);
+    // unary1 (feat -> x1) and the shortcut projection (feat -> sc) of a non-strided block read the same rows: one grouped
+    // launch, the projection with a split-K scratch of its own
+    const bool pair_in = grouped_rows(nq) && d->w1 && d->w2 && d->ws && !d->strided && l1.in_place() && lsc.in_place();
+    const int64_t sc_bytes = pair_in ? ws_gemm_xb_scratch_bytes(nq, d->in_dim, d->out_dim) : 0;
+    void* tmp_sc = pair_in ? (void*)ar.take<char>(sc_bytes > 16 ? sc_bytes : 16) : nullptr;
     if (!run) return WS_OK;
     if (nq == 0) return WS_OK;
     const float* x1 = d->feat;
-    if (d->w1) {
+    if (pair_in) {
+        const ws_xb_problem q[2] = {
+            xb_problem(d->feat, ns, l1.k, d->in_dim, l1.w, 1, l1.ldw, l1.n, d->b1, nullptr, 0, 1, d->slope, nullptr, 0, 0.0f, d->x1, l1.n,
+                       tmp, tmp_bytes),
+            xb_problem(d->feat, nq, lsc.k, d->in_dim, lsc.w, 1, lsc.ldw, lsc.n, d->bs, nullptr, 0, 0, 0.0f, nullptr, 0, 0.0f, sc, lsc.n,
+                       tmp_sc, sc_bytes)};
+        WS_TRY(ws_priv_gemm_xb_group(q, 2, st));
+        x1 = d->x1;
+    } else if (d->w1) {
         WS_TRY(linear_fwd(l1, d->feat, ns, d->in_dim, d->b1, nullptr, 0, 1, d->slope, d->x1, tr1, tmp, tmp_bytes, st));
         x1 = d->x1;
     }
@@ -206,7 +240,7 @@ int kpblock_fwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
     const float* res = sc_in;
     int64_t ldr = d->in_dim;
     if (d->ws) {
-        WS_TRY(linear_fwd(lsc, sc_in, nq, d->in_dim, d->bs, nullptr, 0, 0, 0.0f, sc, trs, tmp, tmp_bytes, st));
+        if (!pair_in) WS_TRY(linear_fwd(lsc, sc_in, nq, d->in_dim, d->bs, nullptr, 0, 0, 0.0f, sc, trs, tmp, tmp_bytes, st));
         res = sc;
         ldr = d->out_dim;
     }
@@ -236,13 +270,21 @@ int kpblock_bwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
     tmp_bytes = max3(tmp_bytes, ws_gemm_xb_scratch_bytes(nq, d->conv_out, kc), ws_gemm_xb_scratch_bytes(nq, d->out_dim, d->conv_out));
     tmp_bytes = max3(tmp_bytes, ws_gemm_xb_scratch_bytes(nq, d->out_dim, d->in_dim), ws_gemm_xb_scratch_bytes(ns, d->conv_in, d->in_dim));
     void* tmp = ar.take<char>(tmp_bytes > 16 ? tmp_bytes : 16);
-    // the weight-gradient products of a short block run on the side stream with a scratch of their own
-    const bool use_side = ws_block_side_rows > 0 && nq > 0 && ns > 0 && nq < ws_block_side_rows;
-    int64_t side_bytes = ws_gemm_xty_scratch_bytes(nq, kc, d->conv_out);
-    if (d->w2) side_bytes = max3(side_bytes, ws_gemm_xty_scratch_bytes(nq, d->out_dim, d->conv_out),
-                                 d->ws ? ws_gemm_xty_scratch_bytes(nq, d->out_dim, d->in_dim) : 0);
-    if (d->w1) side_bytes = max3(side_bytes, ws_gemm_xty_scratch_bytes(ns, d->conv_in, d->in_dim), 0);
-    void* tmp_w = use_side ? (void*)ar.take<char>(side_bytes > 16 ? side_bytes : 16) : tmp;
+    // grouped: the collected weight-gradient products and the second member of the dz pair take a scratch each (a sum
+    // where the single launches share the maximum); the operands the collected products read -- dz (or dout when
+    // pregated), g2, dx1, wf, x2, feat, pooled -- stay untouched until the end of the call
+    const bool grp = grouped_rows(nq > ns ? nq : ns) && nq > 0 && ns > 0;
+    const int64_t b_dwk = ws_gemm_xty_scratch_bytes(nq, kc, d->conv_out);
+    const int64_t b_dw2 = d->w2 ? ws_gemm_xty_scratch_bytes(nq, d->out_dim, d->conv_out) : 0;
+    const int64_t b_dws = (d->w2 && d->ws) ? ws_gemm_xty_scratch_bytes(nq, d->out_dim, d->in_dim) : 0;
+    const int64_t b_dw1 = d->w1 ? ws_gemm_xty_scratch_bytes(ns, d->conv_in, d->in_dim) : 0;
+    const int64_t b_g2 = d->w2 ? ws_gemm_xb_scratch_bytes(nq, d->out_dim, d->conv_out) : 0;
+    auto own = [&](int64_t bytes) -> void* { return grp ? (void*)ar.take<char>(bytes > 16 ? bytes : 16) : tmp; };
+    void* t_dwk = own(b_dwk);
+    void* t_dw2 = d->w2 ? own(b_dw2) : tmp;
+    void* t_dws = (d->w2 && d->ws) ? own(b_dws) : tmp;
+    void* t_dw1 = d->w1 ? own(b_dw1) : tmp;
+    void* t_g2 = d->w2 ? own(b_g2) : tmp;
     if (!run) return WS_OK;
     WS_REQUIRE(d->dout && d->dwk, "NULL gradient buffer");
     WS_REQUIRE(!d->w1 || d->dw1, "dw1 missing");
@@ -262,16 +304,7 @@ int kpblock_bwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
         return WS_OK;
     }
     bool gated2 = false;
-    // stw: the stream of the dW products; fork(i) makes it wait for what the main stream has produced so far
-    Side* side = nullptr;
-    if (use_side) WS_TRY(side_for_current_device(&side));
-    hipStream_t stw = side ? side->st : st;
-    auto fork = [&](int i) -> int {
-        if (!side) return WS_OK;
-        WS_HIP(hipEventRecord(side->fork[i], st));
-        WS_HIP(hipStreamWaitEvent(stw, side->fork[i], 0));
-        return WS_OK;
-    };
+    Leaves leaves(grp, st);
     const float* sc_res = nullptr;          // the shortcut's gradient w.r.t. feat rows [ns,in_dim]
     bool added = false;                     // dfeat_add already summed in (by the pool backward's store)
     const float* gin = d->dout;             // gradient entering the convolution's activation
@@ -285,17 +318,30 @@ int kpblock_bwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
             dz = const_cast<float*>(d->dout);          // (read only from here on)
         } else
         WS_TRY(ws_act_bwd_colsum(d->dout, nq, d->out_dim, d->out_dim, d->out, d->out_dim, d->slope, dz, d->out_dim, d->db2, tmp, st));
-        WS_TRY(fork(0));
-        WS_TRY(ws_gemm_xty(dz, nq, d->out_dim, d->out_dim, d->x2, d->conv_out, d->conv_out, d->dw2, tmp_w, stw));
+        WS_TRY(leaves.add(dz, nq, d->out_dim, d->out_dim, d->x2, d->conv_out, d->conv_out, d->dw2, 0, t_dw2, b_dw2));
         if (d->ws) {
             const float* sc_in = d->strided ? d->pooled : d->feat;
-            WS_TRY(ws_gemm_xty(dz, nq, d->out_dim, d->out_dim, sc_in, d->in_dim, d->in_dim, d->dws, tmp_w, stw));
+            WS_TRY(leaves.add(dz, nq, d->out_dim, d->out_dim, sc_in, d->in_dim, d->in_dim, d->dws, 0, t_dws, b_dws));
+        }
+        // dx2 = dz @ w2; without a bias gradient to sum (use_bn: BatchNormBlock is an identity, blocks.py:453-463) the
+        // activation backward of the convolution's LeakyReLU rides on the epilogue: dz2 = dx2 * lrelu'(x2)
+        gated2 = !d->dbk && ws_block_gates;
+        // grouped: dscin = dz @ ws and g2 = dz @ w2 both wait for dz only -- one launch, one split epilogue
+        const bool pair_dz = grp && want_sc && d->ws;
+        if (pair_dz) {
+            const ws_xb_problem q[2] = {
+                xb_problem(dz, nq, d->out_dim, d->out_dim, d->ws, d->in_dim, 1, d->in_dim, nullptr, nullptr, 0, 0, 0.0f, nullptr, 0, 0.0f,
+                           dscin, d->in_dim, tmp, tmp_bytes),
+                xb_problem(dz, nq, d->out_dim, d->out_dim, d->w2, d->conv_out, 1, d->conv_out, nullptr, nullptr, 0, 0, 0.0f,
+                           gated2 ? d->x2 : nullptr, d->conv_out, d->slope, g2, d->conv_out, t_g2, b_g2)};
+            WS_TRY(ws_priv_gemm_xb_group(q, 2, st));
         }
         if (want_sc) {
             const float* dsc = dz;          // [nq, in_dim] when there is no projection (in_dim == out_dim)
             if (d->ws) {
-                WS_TRY(ws_gemm_xb_epilogue_strided(dz, nq, d->out_dim, d->out_dim, d->ws, d->in_dim, 1, d->in_dim, nullptr, nullptr, 0, 0,
-                                                   0.0f, dscin, d->in_dim, tmp, tmp_bytes, st));
+                if (!pair_dz)
+                    WS_TRY(ws_gemm_xb_epilogue_strided(dz, nq, d->out_dim, d->out_dim, d->ws, d->in_dim, 1, d->in_dim, nullptr, nullptr, 0,
+                                                       0, 0.0f, dscin, d->in_dim, tmp, tmp_bytes, st));
                 dsc = dscin;
             }
             if (d->strided) {
@@ -321,12 +367,10 @@ int kpblock_bwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
                 sc_res = dsc;
             }
         }
-        // dx2 = dz @ w2; without a bias gradient to sum (use_bn: BatchNormBlock is an identity, blocks.py:453-463) the
-        // activation backward of the convolution's LeakyReLU rides on the epilogue: dz2 = dx2 * lrelu'(x2)
-        gated2 = !d->dbk && ws_block_gates;
-        WS_TRY(ws_gemm_xb_gated_strided(dz, nq, d->out_dim, d->out_dim, d->w2, d->conv_out, 1, d->conv_out, nullptr, nullptr, 0, 0, 0.0f,
-                                        gated2 ? d->x2 : nullptr, d->conv_out, d->slope, nullptr, 0, 0.0f, g2, d->conv_out, tmp, tmp_bytes,
-                                        st));
+        if (!pair_dz)
+            WS_TRY(ws_gemm_xb_gated_strided(dz, nq, d->out_dim, d->out_dim, d->w2, d->conv_out, 1, d->conv_out, nullptr, nullptr, 0, 0, 0.0f,
+                                            gated2 ? d->x2 : nullptr, d->conv_out, d->slope, nullptr, 0, 0.0f, g2, d->conv_out, tmp,
+                                            tmp_bytes, st));
         gin = g2;
         yconv = d->x2;
     }
@@ -336,15 +380,8 @@ int kpblock_bwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
         g2 = const_cast<float*>(gin);              // (read only from here on)
     } else if (!gated2)
         WS_TRY(ws_act_bwd_colsum(gin, nq, d->conv_out, d->conv_out, yconv, d->conv_out, d->slope, g2, d->conv_out, d->dbk, tmp, st));
-    WS_TRY(fork(1));
-    WS_TRY(ws_gemm_xty(d->wf, nq, kc, kc, g2, d->conv_out, d->conv_out, d->dwk, tmp_w, stw));
-    auto join = [&]() -> int {              // the caller's stream continues after the side products
-        if (!side) return WS_OK;
-        WS_HIP(hipEventRecord(side->join, stw));
-        WS_HIP(hipStreamWaitEvent(st, side->join, 0));
-        return WS_OK;
-    };
-    if (!need_dx1) return join();
+    WS_TRY(leaves.add(d->wf, nq, kc, kc, g2, d->conv_out, d->conv_out, d->dwk, 0, t_dwk, b_dwk));
+    if (!need_dx1) return leaves.flush();
     // dwf = dz2 @ wk^T
     WS_TRY(linear_fwd(lk, g2, nq, d->conv_out, nullptr, nullptr, 0, 0, 0.0f, dwf, trk, tmp, tmp_bytes, st));
     float* dx1_out = d->w1 ? dx1 : d->dfeat;
@@ -366,8 +403,7 @@ int kpblock_bwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
     if (d->w1) {
         if (!gate1)
             WS_TRY(ws_act_bwd_colsum(dx1, ns, d->conv_in, d->conv_in, d->x1, d->conv_in, d->slope, dx1, d->conv_in, d->db1, tmp, st));
-        WS_TRY(fork(2));
-        WS_TRY(ws_gemm_xty(dx1, ns, d->conv_in, d->conv_in, d->feat, d->in_dim, d->in_dim, d->dw1, tmp_w, stw));
+        WS_TRY(leaves.add(dx1, ns, d->conv_in, d->conv_in, d->feat, d->in_dim, d->in_dim, d->dw1, 0, t_dw1, b_dw1));
         if (d->dfeat)
             WS_TRY(ws_gemm_xb_gated_strided(dx1, ns, d->conv_in, d->conv_in, d->w1, d->in_dim, 1, d->in_dim, nullptr, sc_res, d->in_dim,
                                             0, 0.0f, d->gate_dfeat ? d->feat : nullptr, d->in_dim, d->slope, nullptr, 0, 0.0f, d->dfeat,
@@ -384,7 +420,7 @@ int kpblock_bwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
         add_rows_kernel<<<ws_grid(n4, 256), 256, 0, st>>>(d->dfeat, d->dfeat_add, n4);
         WS_LAUNCH_CHECK();
     }
-    return join();
+    return leaves.flush();
 }
 
 // ---- decoder step ------------------------------------------------------------------------------------------------
@@ -434,6 +470,11 @@ int upunary_bwd(const ws_upunary* d, Arena& ar, hipStream_t st, bool run)
                              ws_gemm_xty_scratch_bytes(d->nc, d->out_dim, d->c_up));
     tmp_bytes = max3(tmp_bytes, ws_gemm_xb_scratch_bytes(d->nf, d->out_dim, d->c_skip), ws_gemm_xb_scratch_bytes(d->nc, d->out_dim, d->c_up));
     void* tmp = ar.take<char>(tmp_bytes > 16 ? tmp_bytes : 16);
+    // grouped: the two pitched halves of dw are leaves -- collected, launched together at the end, a scratch each
+    const bool grp = grouped_rows(d->nf > d->nc ? d->nf : d->nc) && d->nf > 0 && d->nc > 0;
+    const int64_t b_skip = ws_gemm_xty_scratch_bytes(d->nf, d->out_dim, d->c_skip), b_up = ws_gemm_xty_scratch_bytes(d->nc, d->out_dim, d->c_up);
+    void* t_skip = grp ? (void*)ar.take<char>(b_skip > 16 ? b_skip : 16) : tmp;
+    void* t_up = grp ? (void*)ar.take<char>(b_up > 16 ? b_up : 16) : tmp;
     if (!run) return WS_OK;
     WS_REQUIRE(d->dout && d->dw && d->dxc && d->dskip && d->t_offsets && d->t_pairs, "NULL gradient buffer / table");
     const int64_t cw = d->c_up + d->c_skip;
@@ -460,14 +501,16 @@ int upunary_bwd(const ws_upunary* d, Arena& ar, hipStream_t st, bool run)
     }
     // skip side
     // (the two halves of dw [out, c_up + c_skip] are written in place: column blocks of pitch cw)
-    WS_TRY(ws_priv_gemm_xty_pitched(g, d->nf, d->out_dim, d->out_dim, d->skip, d->c_skip, d->c_skip, d->dw + d->c_up, cw, tmp, st));
+    Leaves leaves(grp, (hipStream_t)st);
+    WS_TRY(leaves.add(g, d->nf, d->out_dim, d->out_dim, d->skip, d->c_skip, d->c_skip, d->dw + d->c_up, cw, t_skip, b_skip));
     WS_TRY(ws_gemm_xb_epilogue_strided(g, d->nf, d->out_dim, d->out_dim, d->w + d->c_up, d->ldw, 1, d->c_skip, nullptr, nullptr, 0, 0, 0.0f,
                                        d->dskip, d->c_skip, tmp, tmp_bytes, st));
     // coarse side: nearest upsampling backward, then the x-part of the unary
     WS_TRY(ws_closest_pool_bwd(g, d->nf, 1, d->out_dim, d->t_offsets, d->t_pairs, d->nc, dyc, st));
-    WS_TRY(ws_priv_gemm_xty_pitched(dyc, d->nc, d->out_dim, d->out_dim, d->xc, d->c_up, d->c_up, d->dw, cw, tmp, st));
-    return ws_gemm_xb_gated_strided(dyc, d->nc, d->out_dim, d->out_dim, d->w, d->ldw, 1, d->c_up, nullptr, nullptr, 0, 0, 0.0f,
-                                    d->gate_dxc ? d->xc : nullptr, d->c_up, d->slope, nullptr, 0, 0.0f, d->dxc, d->c_up, tmp, tmp_bytes, st);
+    WS_TRY(leaves.add(dyc, d->nc, d->out_dim, d->out_dim, d->xc, d->c_up, d->c_up, d->dw, cw, t_up, b_up));
+    WS_TRY(ws_gemm_xb_gated_strided(dyc, d->nc, d->out_dim, d->out_dim, d->w, d->ldw, 1, d->c_up, nullptr, nullptr, 0, 0, 0.0f,
+                                    d->gate_dxc ? d->xc : nullptr, d->c_up, d->slope, nullptr, 0, 0.0f, d->dxc, d->c_up, tmp, tmp_bytes, st));
+    return leaves.flush();
 }
 
 }  // namespace
@@ -479,7 +522,7 @@ int64_t ws_kpblock_fwd_scratch_bytes(const ws_kpblock* d)
     if (check_kpblock(d)) return -1;
     Arena ar(nullptr, 0);
     kpblock_fwd(d, ar, nullptr, false);
-    return ar.off + 256;
+    return arena_bytes(ar);
 }
 
 int64_t ws_kpblock_bwd_scratch_bytes(const ws_kpblock* d)
@@ -487,7 +530,7 @@ int64_t ws_kpblock_bwd_scratch_bytes(const ws_kpblock* d)
     if (check_kpblock(d)) return -1;
     Arena ar(nullptr, 0);
     kpblock_bwd(d, ar, nullptr, false);
-    return ar.off + 256;
+    return arena_bytes(ar);
 }
 
 int ws_kpblock_fwd(const ws_kpblock* d, void* scratch, int64_t scratch_bytes, void* stream)
@@ -496,7 +539,7 @@ int ws_kpblock_fwd(const ws_kpblock* d, void* scratch, int64_t scratch_bytes, vo
     WS_REQUIRE(scratch && ((uintptr_t)scratch & 15u) == 0, "scratch must be a 16-byte aligned device buffer");
     Arena plan(nullptr, 0);
     kpblock_fwd(d, plan, nullptr, false);
-    if (plan.off > scratch_bytes) return ws_fail(WS_ERR_CAPACITY, "scratch too small: %lld < %lld bytes", (long long)scratch_bytes, (long long)plan.off);
+    if (arena_bytes(plan) > scratch_bytes) return ws_fail(WS_ERR_CAPACITY, "scratch too small: %lld < %lld bytes", (long long)scratch_bytes, (long long)arena_bytes(plan));
     Arena ar(scratch, scratch_bytes);
     return kpblock_fwd(d, ar, (hipStream_t)stream, true);
 }
@@ -507,7 +550,7 @@ int ws_kpblock_bwd(const ws_kpblock* d, void* scratch, int64_t scratch_bytes, vo
     WS_REQUIRE(scratch && ((uintptr_t)scratch & 15u) == 0, "scratch must be a 16-byte aligned device buffer");
     Arena plan(nullptr, 0);
     kpblock_bwd(d, plan, nullptr, false);
-    if (plan.off > scratch_bytes) return ws_fail(WS_ERR_CAPACITY, "scratch too small: %lld < %lld bytes", (long long)scratch_bytes, (long long)plan.off);
+    if (arena_bytes(plan) > scratch_bytes) return ws_fail(WS_ERR_CAPACITY, "scratch too small: %lld < %lld bytes", (long long)scratch_bytes, (long long)arena_bytes(plan));
     Arena ar(scratch, scratch_bytes);
     return kpblock_bwd(d, ar, (hipStream_t)stream, true);
 }
@@ -517,7 +560,7 @@ int64_t ws_upunary_fwd_scratch_bytes(const ws_upunary* d)
     if (check_upunary(d)) return -1;
     Arena ar(nullptr, 0);
     upunary_fwd(d, ar, nullptr, false);
-    return ar.off + 256;
+    return arena_bytes(ar);
 }
 
 int64_t ws_upunary_bwd_scratch_bytes(const ws_upunary* d)
@@ -525,7 +568,7 @@ int64_t ws_upunary_bwd_scratch_bytes(const ws_upunary* d)
     if (check_upunary(d)) return -1;
     Arena ar(nullptr, 0);
     upunary_bwd(d, ar, nullptr, false);
-    return ar.off + 256;
+    return arena_bytes(ar);
 }
 
 int ws_upunary_fwd(const ws_upunary* d, void* scratch, int64_t scratch_bytes, void* stream)
@@ -534,7 +577,7 @@ int ws_upunary_fwd(const ws_upunary* d, void* scratch, int64_t scratch_bytes, vo
     WS_REQUIRE(scratch && ((uintptr_t)scratch & 15u) == 0, "scratch must be a 16-byte aligned device buffer");
     Arena plan(nullptr, 0);
     upunary_fwd(d, plan, nullptr, false);
-    if (plan.off > scratch_bytes) return ws_fail(WS_ERR_CAPACITY, "scratch too small: %lld < %lld bytes", (long long)scratch_bytes, (long long)plan.off);
+    if (arena_bytes(plan) > scratch_bytes) return ws_fail(WS_ERR_CAPACITY, "scratch too small: %lld < %lld bytes", (long long)scratch_bytes, (long long)arena_bytes(plan));
     Arena ar(scratch, scratch_bytes);
     return upunary_fwd(d, ar, (hipStream_t)stream, true);
 }
@@ -545,7 +588,7 @@ int ws_upunary_bwd(const ws_upunary* d, void* scratch, int64_t scratch_bytes, vo
     WS_REQUIRE(scratch && ((uintptr_t)scratch & 15u) == 0, "scratch must be a 16-byte aligned device buffer");
     Arena plan(nullptr, 0);
     upunary_bwd(d, plan, nullptr, false);
-    if (plan.off > scratch_bytes) return ws_fail(WS_ERR_CAPACITY, "scratch too small: %lld < %lld bytes", (long long)scratch_bytes, (long long)plan.off);
+    if (arena_bytes(plan) > scratch_bytes) return ws_fail(WS_ERR_CAPACITY, "scratch too small: %lld < %lld bytes", (long long)scratch_bytes, (long long)arena_bytes(plan));
     Arena ar(scratch, scratch_bytes);
     return upunary_bwd(d, ar, (hipStream_t)stream, true);
 }

@@ -321,11 +321,14 @@ __device__ __forceinline__ void xb_rows_epilogue_staged(const f32x16 (&acc)[NT],
 // Preconditions (checked by the launcher; everything else takes gemm_xb_kernel): k % 32 == 0, n % 4 == 0,
 // x / y / residual rows 16-byte aligned.  Rows past m and columns past n are clamped on the loads
 // (valid memory, results never stored), so the main loop has no divergent control flow at all.
+// The body runs for workgroup (bx, by, bz) of ONE product's own grid: gemm_xb2_kernel passes blockIdx, the grouped kernel
+// (gemm_xb2_group_kernel) the coordinates it derives from a linear index -- everything else is the same code.
 template <int NT, int WN>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void gemm_xb2_kernel(
+__device__ __forceinline__ void gemm_xb2_body(
+    const unsigned bx, const unsigned by, const unsigned bz,
     const float* __restrict__ x, int64_t m, int k, int64_t ldx, const float* __restrict__ b, int n, int ldb, int bcs,
     float* __restrict__ y, int64_t ldy, const float* __restrict__ bias, const float* __restrict__ residual, int64_t ldr,
-    int act, float slope, int csplit, float* __restrict__ partial, const XbGate gate, int staged)
+    int act, float slope, int csplit, float* __restrict__ partial, const XbGate& gate, int staged)
 {
     // split-K (gridDim.z > 1; few rows, deep k): workgroup z contracts chunks [z*csplit, (z+1)*csplit) and
     // writes its raw sums to partial[z][m][n]; splitk_epilogue_kernel adds them in a fixed order
@@ -341,9 +344,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
     const int wm = wave / WN, wn = wave % WN;
     const int lane = t & 63;
     const int idx = lane & 31, h = lane >> 5;
-    const int64_t row = (int64_t)blockIdx.x * (32 * WM) + wm * 32 + idx;
-    const int n0 = blockIdx.y * BN;
-    const int cbeg = blockIdx.z * csplit;
+    const int64_t row = (int64_t)bx * (32 * WM) + wm * 32 + idx;
+    const int n0 = by * BN;
+    const int cbeg = bz * csplit;
     const int cend = (cbeg + csplit) * KC < k ? cbeg + csplit : k / KC;
 
     f32x16 acc[NT];
@@ -361,7 +364,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
     // row-major [N,K'] matrix as its transpose (nn.Linear's weight, or a weight's transpose in a backward) in place
     const auto wsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b), 0,
                                                         (int)(((int64_t)(k - 1) * ldb + (int64_t)(n - 1) * bcs + 1) * 4), 0x00020000);
-    const int64_t brow0 = (int64_t)blockIdx.x * (32 * WM);
+    const int64_t brow0 = (int64_t)bx * (32 * WM);
     const int64_t brows = m - brow0 < 32 * WM ? m - brow0 : 32 * WM;
     const auto xsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + brow0 * ldx), 0,
                                                         (int)(((brows - 1) * ldx + k) * 4), 0x00020000);
@@ -448,20 +451,74 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void g
     }
     if (staged) {
         // (the main loop ended on a barrier: nobody reads the W buffers any more)
-        const int64_t row0 = (int64_t)blockIdx.x * (32 * WM) + wm * 32;
+        const int64_t row0 = (int64_t)bx * (32 * WM) + wm * 32;
         float* stage = &Ws[wave * XB_STAGE_FLOATS];
         if (partial)
-            xb_rows_epilogue_staged<NT>(acc, row0, m, n0 + wn * (32 * NT), n, lane, partial + (int64_t)blockIdx.z * m * n, n, nullptr,
+            xb_rows_epilogue_staged<NT>(acc, row0, m, n0 + wn * (32 * NT), n, lane, partial + (int64_t)bz * m * n, n, nullptr,
                                         nullptr, 0, 0, 0.0f, XbGate{}, stage);
         else
             xb_rows_epilogue_staged<NT>(acc, row0, m, n0 + wn * (32 * NT), n, lane, y, ldy, bias, residual, ldr, act, slope, gate, stage);
         return;
     }
     if (partial)
-        xb_rows_epilogue<NT>(acc, row, m, n0 + wn * (32 * NT), n, h, partial + (int64_t)blockIdx.z * m * n, n, nullptr, nullptr, 0,
+        xb_rows_epilogue<NT>(acc, row, m, n0 + wn * (32 * NT), n, h, partial + (int64_t)bz * m * n, n, nullptr, nullptr, 0,
                              0, 0.0f, XbGate{});
     else
         xb_rows_epilogue<NT>(acc, row, m, n0 + wn * (32 * NT), n, h, y, ldy, bias, residual, ldr, act, slope, gate);
+}
+
+template <int NT, int WN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void gemm_xb2_kernel(
+    const float* __restrict__ x, int64_t m, int k, int64_t ldx, const float* __restrict__ b, int n, int ldb, int bcs,
+    float* __restrict__ y, int64_t ldy, const float* __restrict__ bias, const float* __restrict__ residual, int64_t ldr,
+    int act, float slope, int csplit, float* __restrict__ partial, const XbGate gate, int staged)
+{
+    gemm_xb2_body<NT, WN>(blockIdx.x, blockIdx.y, blockIdx.z, x, m, k, ldx, b, n, ldb, bcs, y, ldy, bias, residual, ldr, act, slope,
+                          csplit, partial, gate, staged);
+}
+
+// ---- grouped launches: several mutually independent problems of ONE instantiation behind one grid -------------------------
+// The group struct travels by value in the kernel arguments (at most GROUP_MAX problems, < 4 KB).  end[j] = workgroups of
+// problems 0 .. j (running totals; entries past the last problem repeat the total).  A workgroup finds its problem with
+// GROUP_MAX - 1 compares on blockIdx.x -- wave-uniform, like everything read from the descriptor (scalar loads, no private
+// memory) -- takes its coordinates from that problem's OWN grid dimensions (x fastest, as the hardware deals a 3-D grid)
+// and runs the single kernel's body: a member computes exactly what it computes launched alone.  No member waits for
+// another: nothing is synchronised across workgroups.
+constexpr int GROUP_MAX = 8;
+struct GroupIndex { unsigned end[GROUP_MAX]; };
+__device__ __forceinline__ int group_find(const GroupIndex& gi, unsigned& local)
+{
+    const unsigned b = blockIdx.x;
+    int i = 0;
+    unsigned beg = 0;
+#pragma unroll
+    for (int j = 0; j < GROUP_MAX - 1; ++j) {
+        const bool past = b >= gi.end[j];
+        i += past ? 1 : 0;
+        beg = past ? gi.end[j] : beg;
+    }
+    local = b - beg;
+    return i;
+}
+
+struct Xb2Problem {
+    const float* x; int64_t m; int64_t ldx; const float* b; float* y; int64_t ldy; const float* bias; const float* residual;
+    int64_t ldr; float* partial; XbGate gate;
+    int k, n, ldb, bcs, act, csplit, staged; float slope;
+    unsigned gx, gy;        // the problem's own grid (x, y); z = local / (gx * gy)
+};
+struct Xb2Group { GroupIndex gi; Xb2Problem p[GROUP_MAX]; };
+static_assert(sizeof(Xb2Group) < 4096, "the group travels in the kernel arguments");
+
+template <int NT, int WN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void gemm_xb2_group_kernel(const Xb2Group g)
+{
+    unsigned l;
+    const Xb2Problem& p = g.p[group_find(g.gi, l)];
+    const unsigned gx = p.gx, gy = p.gy;
+    const unsigned bx = l % gx, q = l / gx;
+    gemm_xb2_body<NT, WN>(bx, q % gy, q / gy, p.x, p.m, p.k, p.ldx, p.b, p.n, p.ldb, p.bcs, p.y, p.ldy, p.bias, p.residual, p.ldr,
+                          p.act, p.slope, p.csplit, p.partial, p.gate, p.staged);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -554,14 +611,15 @@ __global__ __launch_bounds__(256) void gemm_xb_shallow_kernel(const float* __res
 }
 
 // y = act(sum_z partial[z] + bias + residual): the epilogue of a split-K gemm_xb2 (fixed order over z)
-__global__ __launch_bounds__(256) void splitk_epilogue_kernel(const float* __restrict__ partial, int splits, int64_t m, int n,
-                                                               float* __restrict__ y, int64_t ldy, const float* __restrict__ bias,
-                                                               const float* __restrict__ residual, int64_t ldr, int act, float slope,
-                                                               const XbGate gate)
+// (workgroup bx of nb: the single kernel's blockIdx.x / gridDim.x, or a member's share of a grouped grid)
+__device__ __forceinline__ void splitk_epilogue_body(const unsigned bx, const unsigned nb, const float* __restrict__ partial, int splits,
+                                                     int64_t m, int n, float* __restrict__ y, int64_t ldy,
+                                                     const float* __restrict__ bias, const float* __restrict__ residual, int64_t ldr,
+                                                     int act, float slope, const XbGate& gate)
 {
     const int n4 = n >> 2;
     const int64_t total = m * n4;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    for (int64_t e = (int64_t)bx * 256 + threadIdx.x; e < total; e += (int64_t)nb * 256) {
         const int64_t r = e / n4;
         const int c = (int)(e % n4) * 4;
         float4 v = *reinterpret_cast<const float4*>(partial + r * n + c);
@@ -584,6 +642,29 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const float* __res
         xb_gate4(v, gate, r, c);
         *reinterpret_cast<float4*>(y + r * ldy + c) = v;
     }
+}
+
+__global__ __launch_bounds__(256) void splitk_epilogue_kernel(const float* __restrict__ partial, int splits, int64_t m, int n,
+                                                               float* __restrict__ y, int64_t ldy, const float* __restrict__ bias,
+                                                               const float* __restrict__ residual, int64_t ldr, int act, float slope,
+                                                               const XbGate gate)
+{
+    splitk_epilogue_body(blockIdx.x, gridDim.x, partial, splits, m, n, y, ldy, bias, residual, ldr, act, slope, gate);
+}
+
+// the split-K epilogues of a grouped gemm_xb2 launch: member j takes nb workgroups (what it takes alone) and adds its
+// partial sums in the single kernel's order
+struct SplitkProblem {
+    const float* partial; int64_t m; float* y; int64_t ldy; const float* bias; const float* residual; int64_t ldr; XbGate gate;
+    int splits, n, act; float slope; unsigned nb;
+};
+struct SplitkGroup { GroupIndex gi; SplitkProblem p[GROUP_MAX]; };
+static_assert(sizeof(SplitkGroup) < 4096, "the group travels in the kernel arguments");
+__global__ __launch_bounds__(256) void splitk_epilogue_group_kernel(const SplitkGroup g)
+{
+    unsigned l;
+    const SplitkProblem& p = g.p[group_find(g.gi, l)];
+    splitk_epilogue_body(l, p.nb, p.partial, p.splits, p.m, p.n, p.y, p.ldy, p.bias, p.residual, p.ldr, p.act, p.slope, p.gate);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -738,10 +819,11 @@ __device__ __forceinline__ void xty_load_cols(__amdgpu_buffer_rsrc_t srd, int of
     }
 }
 
-template <int KT, int NT, int WK, int WN, typename TI = float>
-__global__ __launch_bounds__(256) void gemm_xty2_kernel(const TI* __restrict__ x, int64_t m, int k, int64_t ldx,
-                                                         const TI* __restrict__ yy, int n, int64_t ldy,
-                                                         float* __restrict__ partial, int64_t chunk)
+template <int KT, int NT, int WK, int WN, typename TI>
+__device__ __forceinline__ void gemm_xty2_body(const unsigned bx, const unsigned by, const unsigned bz,
+                                               const TI* __restrict__ x, int64_t m, int k, int64_t ldx,
+                                               const TI* __restrict__ yy, int n, int64_t ldy,
+                                               float* __restrict__ partial, int64_t chunk)
 {
     constexpr int ES = (int)sizeof(TI);
     constexpr int WR = 4 / (WK * WN);
@@ -752,9 +834,9 @@ __global__ __launch_bounds__(256) void gemm_xty2_kernel(const TI* __restrict__ x
     const int lane = t & 63;
     const int idx = lane & 31, h = lane >> 5;
     const int wr = wave / (WK * WN), wk = (wave / WN) % WK, wn = wave % WN;
-    const int c0 = (blockIdx.y * WK + wk) * (32 * KT);
-    const int n0 = (blockIdx.z * WN + wn) * (32 * NT);
-    const int64_t mbeg = (int64_t)blockIdx.x * chunk;
+    const int c0 = ((int)by * WK + wk) * (32 * KT);
+    const int n0 = ((int)bz * WN + wn) * (32 * NT);
+    const int64_t mbeg = (int64_t)bx * chunk;
     const int64_t mend = mbeg + chunk < m ? mbeg + chunk : m;
 
     f32x16 acc[KT][NT];
@@ -837,7 +919,7 @@ __global__ __launch_bounds__(256) void gemm_xty2_kernel(const TI* __restrict__ x
         }
     }
     if (wr == 0) {
-        float* out = partial + (int64_t)blockIdx.x * k * n;
+        float* out = partial + (int64_t)bx * k * n;
 #pragma unroll
         for (int a = 0; a < KT; ++a)
             if constexpr (NT == 2) {
@@ -874,16 +956,40 @@ __global__ __launch_bounds__(256) void gemm_xty2_kernel(const TI* __restrict__ x
     }
 }
 
+template <int KT, int NT, int WK, int WN, typename TI = float>
+__global__ __launch_bounds__(256) void gemm_xty2_kernel(const TI* __restrict__ x, int64_t m, int k, int64_t ldx,
+                                                         const TI* __restrict__ yy, int n, int64_t ldy,
+                                                         float* __restrict__ partial, int64_t chunk)
+{
+    gemm_xty2_body<KT, NT, WK, WN, TI>(blockIdx.x, blockIdx.y, blockIdx.z, x, m, k, ldx, yy, n, ldy, partial, chunk);
+}
+
+// grouped form (f32 rows): see gemm_xb2_group_kernel
+struct Xty2Problem {
+    const float* x; int64_t m; int64_t ldx; const float* y; int64_t ldy; float* partial; int64_t chunk;
+    int k, n; unsigned gx, gy;
+};
+struct Xty2Group { GroupIndex gi; Xty2Problem p[GROUP_MAX]; };
+template <int KT, int NT, int WK, int WN>
+__global__ __launch_bounds__(256) void gemm_xty2_group_kernel(const Xty2Group g)
+{
+    unsigned l;
+    const Xty2Problem& p = g.p[group_find(g.gi, l)];
+    const unsigned gx = p.gx, gy = p.gy;
+    const unsigned bx = l % gx, q = l / gx;
+    gemm_xty2_body<KT, NT, WK, WN, float>(bx, q % gy, q / gy, p.x, p.m, p.k, p.ldx, p.y, p.n, p.ldy, p.partial, p.chunk);
+}
+
 // out[e] = sum_c partial[c][e] in a fixed order (bitwise reproducible): 32 elements x 8 chunk groups
 // per workgroup, group g adds chunks g, g+8, ... (coalesced 128-byte reads), then the 8 group sums
 // are added in order.
 // (n, ldo: the output is [elems / n, n] with row pitch ldo; ldo == n = flat)
-__global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ partial, int64_t elems, int chunks,
-                                                               float* __restrict__ out, int n = 0, int64_t ldo = 0)
+__device__ __forceinline__ void reduce_partials_body(const unsigned bx, const float* __restrict__ partial, int64_t elems, int chunks,
+                                                     float* __restrict__ out, int n, int64_t ldo)
 {
     __shared__ float red[8][32];
     const int el = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int64_t e = (int64_t)blockIdx.x * 32 + el;
+    const int64_t e = (int64_t)bx * 32 + el;
     float s = 0.0f;
     if (e < elems) {
         int c = grp;
@@ -904,12 +1010,18 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
     }
 }
 
+__global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ partial, int64_t elems, int chunks,
+                                                               float* __restrict__ out, int n = 0, int64_t ldo = 0)
+{
+    reduce_partials_body(blockIdx.x, partial, elems, chunks, out, n, ldo);
+}
+
 // the same sum for LARGE outputs of few chunks (dW of the deep levels: k n up to 4 M elements, <= ~16 chunks): a thread owns
 // four consecutive elements and adds the chunks in order 0, 1, 2, ... (four 16-byte loads in flight)
-__global__ __launch_bounds__(256) void reduce_partials_wide_kernel(const float* __restrict__ partial, int64_t elems, int chunks,
-                                                                    float* __restrict__ out, int n = 0, int64_t ldo = 0)
+__device__ __forceinline__ void reduce_partials_wide_body(const unsigned bx, const float* __restrict__ partial, int64_t elems, int chunks,
+                                                          float* __restrict__ out, int n, int64_t ldo)
 {
-    const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const int64_t e = ((int64_t)bx * 256 + threadIdx.x) * 4;
     if (e >= elems) return;
     const float4* p = reinterpret_cast<const float4*>(partial + e);
     const int64_t st = elems / 4;
@@ -927,6 +1039,24 @@ __global__ __launch_bounds__(256) void reduce_partials_wide_kernel(const float* 
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
     *reinterpret_cast<float4*>(out + (ldo > n ? (e / n) * ldo + e % n : e)) = s;      // (n % 4 == 0: a quad stays in its row)
+}
+
+__global__ __launch_bounds__(256) void reduce_partials_wide_kernel(const float* __restrict__ partial, int64_t elems, int chunks,
+                                                                    float* __restrict__ out, int n = 0, int64_t ldo = 0)
+{
+    reduce_partials_wide_body(blockIdx.x, partial, elems, chunks, out, n, ldo);
+}
+
+// the chunk sums of a grouped gemm_xty2 launch: member j runs the form it takes alone (wide: reduce_partials_wide_kernel's
+// body, else reduce_partials_kernel's; the choice is uniform over a workgroup) over the workgroups it takes alone
+struct ReduceProblem { const float* partial; int64_t elems; float* out; int64_t ldo; int chunks, n, wide; };
+struct ReduceGroup { GroupIndex gi; ReduceProblem p[GROUP_MAX]; };
+__global__ __launch_bounds__(256) void reduce_partials_group_kernel(const ReduceGroup g)
+{
+    unsigned l;
+    const ReduceProblem& p = g.p[group_find(g.gi, l)];
+    if (p.wide) reduce_partials_wide_body(l, p.partial, p.elems, p.chunks, p.out, p.n, p.ldo);
+    else reduce_partials_body(l, p.partial, p.elems, p.chunks, p.out, p.n, p.ldo);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1343,6 +1473,131 @@ int ws_priv_gemm_xb_ex(const float* x, int64_t m, int32_t k, int64_t ldx, const 
                         b_row_stride, b_col_stride, gate);
 }
 
+// ---- grouped products (ws_common.h) ------------------------------------------------------------------------------------------
+// Each member keeps exactly the plan it gets alone from xb_plan / xty_plan -- kind, tile variant, splits, csplit, chunk,
+// chunks, reduction form, pitched output -- and its workgroups run the single kernels' bodies on that plan, so every sum
+// is added in the order of the single launch: a grouped result is bit-identical to the single one.  Only the number of
+// launches changes.
+static XbGate xb_problem_gate(const ws_xb_problem& q)
+{
+    XbGate g{};
+    g.y = q.gate_y; g.ld = q.ldg; g.slope = q.gate_slope;
+    g.mask = q.mask; g.ldm = q.ldm; g.mscale = q.mask_scale;
+    g.drop = ws_drop_args(q.drop_p, q.drop_seed);
+    g.dn = q.n;
+    g.rrows = q.res_rows; g.rld = q.res_rows_ld; g.rn = q.res_nrows;
+    return g;
+}
+static int xb_problem_alone(const ws_xb_problem& q, void* stream)
+{
+    return gemm_xb_impl(q.x, q.m, q.k, q.ldx, q.b, q.n, q.bias, q.residual, q.ldr, q.act, q.slope, q.y, q.ldy, q.scratch, q.scratch_bytes,
+                        stream, q.b_row_stride, q.b_col_stride, xb_problem_gate(q));
+}
+// one call plans at most GROUP_CALL_MAX members on the stack (no allocation on the launch path: the block calls pass 2 .. 4);
+// a longer list is handled as consecutive slices of that many, each grouped within itself
+constexpr int GROUP_CALL_MAX = 16;
+struct IdList {
+    int n = 0;
+    int v[GROUP_CALL_MAX];
+    void push_back(int i) { v[n++] = i; }
+    int size() const { return n; }
+    const int* data() const { return v; }
+    int operator[](int i) const { return v[i]; }
+};
+constexpr int64_t GROUP_MEMBER_BLOCKS = 1ll << 27;      // a member with more workgroups runs alone (the linear index stays 32-bit)
+
+static int xb2_group_launch(const ws_xb_problem* q, const XbPlan* plan, const int* ids, int cnt, hipStream_t st)
+{
+    Xb2Group g{};
+    SplitkGroup e{};
+    int ne = 0, last_e = -1;
+    unsigned total = 0, etotal = 0;
+    for (int j = 0; j < cnt; ++j) {
+        const ws_xb_problem& a = q[ids[j]];
+        const XbPlan& p = plan[ids[j]];
+        const XbGate gate = xb_problem_gate(a);
+        float* part = p.splits > 1 ? (float*)a.scratch : nullptr;
+        g.p[j] = Xb2Problem{a.x, a.m, a.ldx, a.b, a.y, a.ldy, a.bias, a.residual, a.ldr, part, gate, a.k, a.n,
+                            (int)(a.b_row_stride < 0 ? a.n : a.b_row_stride), (int)a.b_col_stride, a.act, p.csplit, p.staged, a.slope,
+                            p.grid.x, p.grid.y};
+        total += p.grid.x * p.grid.y * p.grid.z;
+        g.gi.end[j] = total;
+        if (p.splits > 1) {
+            const unsigned nb = (unsigned)ws_grid(a.m * (a.n / 4), 256);
+            e.p[ne] = SplitkProblem{part, a.m, a.y, a.ldy, a.bias, a.residual, a.ldr, gate, p.splits, a.n, a.act, a.slope, nb};
+            etotal += nb;
+            e.gi.end[ne++] = etotal;
+            last_e = ids[j];
+        }
+    }
+    for (int j = cnt; j < GROUP_MAX; ++j) g.gi.end[j] = total;
+    for (int j = ne; j < GROUP_MAX; ++j) e.gi.end[j] = etotal;
+    const XbPlan& p0 = plan[ids[0]];
+    if (p0.wn == 1) {
+        if (p0.nt == 1) gemm_xb2_group_kernel<1, 1><<<total, 256, 0, st>>>(g);
+        else if (p0.nt == 2) gemm_xb2_group_kernel<2, 1><<<total, 256, 0, st>>>(g);
+        else gemm_xb2_group_kernel<4, 1><<<total, 256, 0, st>>>(g);
+    } else {
+        if (p0.nt == 1) gemm_xb2_group_kernel<1, 2><<<total, 256, 0, st>>>(g);
+        else gemm_xb2_group_kernel<2, 2><<<total, 256, 0, st>>>(g);
+    }
+    WS_LAUNCH_CHECK();
+    if (ne == 1) {
+        const SplitkProblem& s1 = e.p[0];
+        splitk_epilogue_kernel<<<s1.nb, 256, 0, st>>>(s1.partial, s1.splits, s1.m, s1.n, s1.y, s1.ldy, s1.bias, s1.residual, s1.ldr, s1.act,
+                                                      s1.slope, xb_problem_gate(q[last_e]));
+        WS_HIP(hipGetLastError());      // (a single split epilogue counts with its product, as in gemm_xb_impl: ws_common.h)
+    } else if (ne > 1) {
+        splitk_epilogue_group_kernel<<<etotal, 256, 0, st>>>(e);
+        WS_LAUNCH_CHECK();
+    }
+    return WS_OK;
+}
+
+// private to the library (ws_common.h).  Members whose plan is not gemm_xb2 (the shallow and generic forms) run alone, as do
+// members alone in their instantiation; m == 0 does what the single entry does (nothing); more than GROUP_MAX members of one
+// instantiation spill into a second launch.
+int ws_priv_gemm_xb_group(const ws_xb_problem* q, int32_t count, void* stream)
+{
+    WS_REQUIRE(count >= 0 && (q || count == 0), "bad group");
+    for (; count > GROUP_CALL_MAX; q += GROUP_CALL_MAX, count -= GROUP_CALL_MAX) {
+        const int rc = ws_priv_gemm_xb_group(q, GROUP_CALL_MAX, stream);
+        if (rc != WS_OK) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    XbPlan plan[GROUP_CALL_MAX];
+    IdList bucket[5];
+    for (int i = 0; i < count; ++i) {
+        const ws_xb_problem& a = q[i];
+        WS_REQUIRE(a.m >= 0 && a.k >= 1 && a.n >= 1 && a.ldx >= a.k && a.ldy >= a.n, "member %d: bad sizes m=%lld k=%d n=%d", i, (long long)a.m, a.k, a.n);
+        WS_REQUIRE(!a.residual || a.ldr >= a.n, "member %d: residual leading dimension too small", i);
+        WS_REQUIRE(a.act == 0 || a.act == 1, "member %d: unknown activation %d", i, a.act);
+        WS_REQUIRE(a.drop_p >= 0.0f && a.drop_p < 1.0f, "member %d: bad drop probability %g", i, (double)a.drop_p);
+        WS_REQUIRE(!a.res_rows || (a.residual && a.res_rows_ld >= 1 && a.res_nrows >= 0), "member %d: gathered residual: NULL residual / bad sizes", i);
+        WS_REQUIRE(!a.gate_y || a.ldg >= a.n, "member %d: gate leading dimension too small", i);
+        WS_REQUIRE(!a.mask || a.ldm >= a.n, "member %d: mask leading dimension too small", i);
+        if (a.m == 0) continue;
+        WS_REQUIRE(a.x && a.b && a.y, "member %d: NULL argument", i);
+        const int rc = xb_plan(a.x, a.m, a.k, a.ldx, a.b, a.n, a.bias, a.residual, a.ldr, a.y, a.ldy, a.scratch, a.scratch_bytes,
+                               a.b_row_stride < 0 ? a.n : a.b_row_stride, a.b_col_stride, xb_problem_gate(a), plan[i]);
+        if (rc != WS_OK) return rc;
+        const XbPlan& p = plan[i];
+        if (p.kind != XB_XB2 || (int64_t)p.grid.x * p.grid.y * p.grid.z >= GROUP_MEMBER_BLOCKS) {
+            const int r1 = xb_problem_alone(a, stream);
+            if (r1 != WS_OK) return r1;
+            continue;
+        }
+        bucket[p.wn == 1 ? (p.nt == 1 ? 0 : p.nt == 2 ? 1 : 2) : (p.nt == 1 ? 3 : 4)].push_back(i);
+    }
+    for (const IdList& ids : bucket)
+        for (int off = 0; off < ids.size(); off += GROUP_MAX) {
+            const int cnt = ids.size() - off < GROUP_MAX ? ids.size() - off : GROUP_MAX;
+            const int rc = cnt == 1 ? xb_problem_alone(q[ids[off]], stream) : xb2_group_launch(q, plan, ids.data() + off, cnt, st);
+            if (rc != WS_OK) return rc;
+        }
+    return WS_OK;
+}
+
 int ws_gemm_xb(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n, float* y, int64_t ldy,
                void* stream)
 {
@@ -1414,6 +1669,9 @@ static int xty_plan(const void* x, int64_t m, int32_t k, int64_t ldx, const void
     return WS_OK;
 }
 
+static void xty_product_launch(const XtyPlan& p, const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy,
+                               hipStream_t st);
+
 static int gemm_xty_core(const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy,
                          float* out, void* scratch, void* stream, int64_t ldo)
 {
@@ -1432,6 +1690,20 @@ static int gemm_xty_core(const float* x, int64_t m, int32_t k, int64_t ldx, cons
     XtyPlan p;
     const int rc = xty_plan(x, m, k, ldx, y, n, ldy, out, scratch, ldo, false, p);
     if (rc != WS_OK) return rc;
+    xty_product_launch(p, x, m, k, ldx, y, n, ldy, st);
+    WS_LAUNCH_CHECK();
+    if (p.reduce) {
+        const int64_t elems = (int64_t)k * n;
+        launch_reduce_partials(p.partial, elems, p.chunks, out, st, n, pitched ? ldo : 0);
+        WS_LAUNCH_CHECK();
+    }
+    return WS_OK;
+}
+
+// the product launch of plan p (f32 rows)
+static void xty_product_launch(const XtyPlan& p, const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy,
+                               hipStream_t st)
+{
     if (!p.lds) {
 #define WS_XTY2(KTV, NTV, WKV, WNV) gemm_xty2_kernel<KTV, NTV, WKV, WNV><<<p.grid, 256, 0, st>>>(x, m, k, ldx, y, n, ldy, p.partial, p.chunk)
 #define WS_XTY2_W(KTV, NTV)                          \
@@ -1461,13 +1733,6 @@ static int gemm_xty_core(const float* x, int64_t m, int32_t k, int64_t ldx, cons
 #undef WS_XTY_K
 #undef WS_XTY
     }
-    WS_LAUNCH_CHECK();
-    if (p.reduce) {
-        const int64_t elems = (int64_t)k * n;
-        launch_reduce_partials(p.partial, elems, p.chunks, out, st, n, pitched ? ldo : 0);
-        WS_LAUNCH_CHECK();
-    }
-    return WS_OK;
 }
 
 // private to the library (ws_common.h): dW written as a column block of a wider matrix (row pitch ldo >= n)
@@ -1476,6 +1741,113 @@ int ws_priv_gemm_xty_pitched(const float* x, int64_t m, int32_t k, int64_t ldx, 
 {
     WS_REQUIRE(ldo >= n, "output pitch smaller than a row");
     return gemm_xty_core(x, m, k, ldx, y, n, ldy, out, scratch, stream, ldo);
+}
+
+static int xty2_group_launch(const ws_xty_problem* q, const XtyPlan* plan, const int* ids, int cnt, hipStream_t st)
+{
+    Xty2Group g{};
+    unsigned total = 0;
+    for (int j = 0; j < cnt; ++j) {
+        const ws_xty_problem& a = q[ids[j]];
+        const XtyPlan& p = plan[ids[j]];
+        g.p[j] = Xty2Problem{a.x, a.m, a.ldx, a.y, a.ldy, p.partial, p.chunk, a.k, a.n, p.grid.x, p.grid.y};
+        total += p.grid.x * p.grid.y * p.grid.z;
+        g.gi.end[j] = total;
+    }
+    for (int j = cnt; j < GROUP_MAX; ++j) g.gi.end[j] = total;
+    const XtyPlan& p0 = plan[ids[0]];
+#define WS_XTY2G(KTV, NTV, WKV, WNV) gemm_xty2_group_kernel<KTV, NTV, WKV, WNV><<<total, 256, 0, st>>>(g)
+#define WS_XTY2G_W(KTV, NTV)                             \
+    do {                                                 \
+        if (p0.wk == 2 && p0.wn == 2) WS_XTY2G(KTV, NTV, 2, 2); \
+        else if (p0.wk == 2) WS_XTY2G(KTV, NTV, 2, 1);     \
+        else if (p0.wn == 2) WS_XTY2G(KTV, NTV, 1, 2);     \
+        else WS_XTY2G(KTV, NTV, 1, 1);                   \
+    } while (0)
+    if (p0.kt == 2 && p0.nt == 2) WS_XTY2G_W(2, 2);
+    else if (p0.kt == 2) WS_XTY2G_W(2, 1);
+    else if (p0.nt == 2) WS_XTY2G_W(1, 2);
+    else WS_XTY2G_W(1, 1);
+#undef WS_XTY2G_W
+#undef WS_XTY2G
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+// private to the library (ws_common.h).  Members in the 32-bit-overflow form (gemm_xty_kernel) run alone, reduction
+// included; m == 0 clears the output like the single entry.  The others launch their products grouped by instantiation
+// (alone when nobody shares it; more than GROUP_MAX spill into a second launch), then the chunk sums of all of them are
+// added by grouped reduction launches of up to GROUP_MAX members.
+int ws_priv_gemm_xty_group(const ws_xty_problem* q, int32_t count, void* stream)
+{
+    WS_REQUIRE(count >= 0 && (q || count == 0), "bad group");
+    for (; count > GROUP_CALL_MAX; q += GROUP_CALL_MAX, count -= GROUP_CALL_MAX) {
+        const int rc = ws_priv_gemm_xty_group(q, GROUP_CALL_MAX, stream);
+        if (rc != WS_OK) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    XtyPlan plan[GROUP_CALL_MAX];
+    IdList bucket[16], red;
+    for (int i = 0; i < count; ++i) {
+        const ws_xty_problem& a = q[i];
+        WS_REQUIRE(a.m >= 0 && a.k >= 1 && a.n >= 1 && a.ldx >= a.k && a.ldy >= a.n, "member %d: bad sizes m=%lld k=%d n=%d", i, (long long)a.m, a.k, a.n);
+        WS_REQUIRE(a.out && (a.ldo == 0 || a.ldo >= a.n), "member %d: NULL output / pitch smaller than a row", i);
+        if (a.m == 0) {
+            const int rc = gemm_xty_core(a.x, 0, a.k, a.ldx, a.y, a.n, a.ldy, a.out, a.scratch, stream, a.ldo);
+            if (rc != WS_OK) return rc;
+            continue;
+        }
+        WS_REQUIRE(a.x && a.y && a.scratch, "member %d: NULL argument", i);
+        if (a.scratch_bytes < ws_gemm_xty_scratch_bytes(a.m, a.k, a.n))
+            return ws_fail(WS_ERR_CAPACITY, "member %d: scratch too small: %lld < %lld bytes", i, (long long)a.scratch_bytes,
+                           (long long)ws_gemm_xty_scratch_bytes(a.m, a.k, a.n));
+        const int rc = xty_plan(a.x, a.m, a.k, a.ldx, a.y, a.n, a.ldy, a.out, a.scratch, a.ldo, false, plan[i]);
+        if (rc != WS_OK) return rc;
+        const XtyPlan& p = plan[i];
+        if (p.lds || (int64_t)p.grid.x * p.grid.y * p.grid.z >= GROUP_MEMBER_BLOCKS) {
+            const int r1 = gemm_xty_core(a.x, a.m, a.k, a.ldx, a.y, a.n, a.ldy, a.out, a.scratch, stream, a.ldo);
+            if (r1 != WS_OK) return r1;
+            continue;
+        }
+        bucket[(((p.kt - 1) * 2 + (p.nt - 1)) * 2 + (p.wk - 1)) * 2 + (p.wn - 1)].push_back(i);
+        if (p.reduce) red.push_back(i);
+    }
+    for (const IdList& ids : bucket)
+        for (int off = 0; off < ids.size(); off += GROUP_MAX) {
+            const int cnt = ids.size() - off < GROUP_MAX ? ids.size() - off : GROUP_MAX;
+            if (cnt == 1) {
+                const ws_xty_problem& a = q[ids[off]];
+                xty_product_launch(plan[ids[off]], a.x, a.m, a.k, a.ldx, a.y, a.n, a.ldy, st);
+                WS_LAUNCH_CHECK();
+            } else {
+                const int rc = xty2_group_launch(q, plan, ids.data() + off, cnt, st);
+                if (rc != WS_OK) return rc;
+            }
+        }
+    for (int off = 0; off < red.size(); off += GROUP_MAX) {
+        const int cnt = red.size() - off < GROUP_MAX ? red.size() - off : GROUP_MAX;
+        if (cnt == 1) {
+            const ws_xty_problem& a = q[red[off]];
+            const XtyPlan& p = plan[red[off]];
+            launch_reduce_partials(p.partial, (int64_t)a.k * a.n, p.chunks, a.out, st, a.n, p.pitched ? a.ldo : 0);
+            WS_LAUNCH_CHECK();
+            continue;
+        }
+        ReduceGroup g{};
+        unsigned total = 0;
+        for (int j = 0; j < cnt; ++j) {
+            const ws_xty_problem& a = q[red[off + j]];
+            const XtyPlan& p = plan[red[off + j]];
+            const int64_t elems = (int64_t)a.k * a.n;
+            g.p[j] = ReduceProblem{p.partial, elems, a.out, p.pitched ? a.ldo : 0, p.chunks, a.n, p.reduce == 2 ? 1 : 0};
+            total += (unsigned)ws_ceil_div(elems, p.reduce == 2 ? 1024 : 32);
+            g.gi.end[j] = total;
+        }
+        for (int j = cnt; j < GROUP_MAX; ++j) g.gi.end[j] = total;
+        reduce_partials_group_kernel<<<total, 256, 0, st>>>(g);
+        WS_LAUNCH_CHECK();
+    }
+    return WS_OK;
 }
 
 

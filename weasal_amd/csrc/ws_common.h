@@ -33,6 +33,9 @@ inline int ws_fail(int code, const char* fmt, ...)
     } while (0)
 
 // every kernel launch of the library is followed by this check: it also counts them (ws_launch_count: bench.py's launches/step)
+// One rule has always held in gemm.hip and holds for the grouped entries too: a split-K product and its single
+// splitk_epilogue_kernel launch pass the check together and count as ONE; a grouped launch (product, split epilogue or
+// reduction) counts as one.
 extern "C" long long ws_launch_counter;
 #define WS_LAUNCH_CHECK()                         \
     do {                                          \
@@ -56,6 +59,32 @@ extern "C" int ws_priv_gemm_xb_ex(const float* x, int64_t m, int32_t k, int64_t 
 
 extern "C" int ws_priv_gemm_xty_pitched(const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy,
                                         float* out, int64_t ldo, void* scratch, void* stream);                        // gemm.hip for blocks.hip
+
+// Grouped launches (gemm.hip for blocks.hip): `count` products that are mutually independent -- no member reads what another
+// writes, every member has its own output and its own scratch -- behind one grid per kernel instantiation, and their
+// reductions behind one more.  A member keeps exactly the plan it gets alone; what the grouped kernels do not cover runs
+// alone through the single entry.  Fields as the arguments of ws_priv_gemm_xb_ex + ws_gemm_xb_gated_strided
+// (b_row_stride < 0: row-major [K, N]) and of ws_priv_gemm_xty_pitched (ldo = 0: flat output).
+struct ws_xb_problem {
+    const float* x; int64_t m; int32_t k; int64_t ldx;
+    const float* b; int64_t b_row_stride, b_col_stride; int32_t n;
+    const float* bias; const float* residual; int64_t ldr;
+    const int64_t* res_rows; int64_t res_rows_ld, res_nrows;
+    int32_t act; float slope;
+    const float* gate_y; int64_t ldg; float gate_slope;
+    const uint8_t* mask; int64_t ldm; float mask_scale;
+    float drop_p; uint64_t drop_seed;
+    float* y; int64_t ldy;
+    void* scratch; int64_t scratch_bytes;
+};
+struct ws_xty_problem {
+    const float* x; int64_t m; int32_t k; int64_t ldx;
+    const float* y; int32_t n; int64_t ldy;
+    float* out; int64_t ldo;
+    void* scratch; int64_t scratch_bytes;      // at least ws_gemm_xty_scratch_bytes(m, k, n)
+};
+extern "C" int ws_priv_gemm_xb_group(const ws_xb_problem* p, int32_t count, void* stream);
+extern "C" int ws_priv_gemm_xty_group(const ws_xty_problem* p, int32_t count, void* stream);
 
 // grid size for wave-per-item / grid-stride kernels: enough workgroups to fill 256 CUs a few
 // times over, never more than the work.

@@ -279,6 +279,20 @@ int ws_kpconv_gather_bwd_x_gated(const float* q_pts, int64_t nq, const float* s_
                                  const float* deformed_kp, const float* modulations, float extent,
                                  int32_t influence, int32_t aggregation, const int32_t* order, const float* gate_y,
                                  float gate_slope, float* dx, void* stream);
+/* ws_kpconv_gather_bwd_x_gated with four supports per wave (kpconv_gather_bwd_x_packed_kernel) where that form applies: f32
+ * rows with ci % 4 == 0 and 16-byte aligned dwf / dx, rigid kernel, linear influence, sum, nq < ns and at most PACK_MEAN_MAX
+ * (kpconv.hip) incoming pairs per support on average -- the strided layers of the pyramid.  Elsewhere it launches what
+ * ws_kpconv_gather_bwd_x_gated launches; dx is the same bit for bit either way.  The reporter names the packed kernel and
+ * its template arguments, or "none". */
+int ws_kpconv_gather_bwd_x_packed(const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
+                                  const int64_t* inds, int32_t h, const int32_t* t_offsets, const int32_t* t_pairs,
+                                  const float* dwf, int32_t ci, const float* kernel_points, int32_t k,
+                                  const float* deformed_kp, const float* modulations, float extent,
+                                  int32_t influence, int32_t aggregation, const int32_t* order, const float* gate_y,
+                                  float gate_slope, float* dx, void* stream);
+int ws_kpconv_gather_bwd_x_packed_variant(int64_t nq, int64_t ns, int32_t h, int32_t ci, const void* dwf, const void* dx, int32_t deformed,
+                                          int32_t modulated, int32_t influence, int32_t aggregation, int32_t rows_bf16, int32_t ordered,
+                                          char* out, int32_t cap);
 int ws_kpconv_gather_bwd_x_grid_gated(const float* s_pts, int64_t ns, const void* grid_blob, int32_t nb, int64_t cells,
                                       const uint64_t* key_last, float radius, const float* dwf, int32_t ci,
                                       const float* kernel_points, int32_t k, const float* deformed_kp, const float* modulations,

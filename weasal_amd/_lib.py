@@ -123,6 +123,10 @@ SIGNATURES = {
                                            _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp]),
     "ws_kpconv_gather_bwd_x_gated": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32,
                                               _vp, _vp, _f32, _i32, _i32, _vp, _vp, _f32, _vp, _vp]),
+    "ws_kpconv_gather_bwd_x_packed": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32,
+                                               _vp, _vp, _f32, _i32, _i32, _vp, _vp, _f32, _vp, _vp]),
+    "ws_kpconv_gather_bwd_x_packed_variant": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                                       C.c_char_p, _i32]),
     "ws_kpconv_gather_bwd_x_grid_gated": (C.c_int, [_vp, _i64, _vp, _i32, _i64, _vp, C.c_float, _vp, _i32, _vp, _i32, _vp, _vp,
                                                     C.c_float, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _vp]),
     "ws_vote_update": (C.c_int, [_vp, _i64, _i32, _vp, _f32, _vp, _vp, _i64, _f32, _vp]),

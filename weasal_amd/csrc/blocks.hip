@@ -26,6 +26,8 @@ extern "C" int64_t ws_block_group_rows = (int64_t)1 << 62;
 extern "C" int ws_block_fused_infer = 1;
 // A/B switch (WEASAL_POOL_ORDER=0): the strided blocks' max-pool walks its rows by index instead of in cell order
 extern "C" int ws_block_pool_order = 1;
+// A/B switch (WEASAL_BLOCK_PACKED_K4=0): the table-walk K4 of a block through ws_kpconv_gather_bwd_x_gated instead of the packed entry
+extern "C" int ws_block_packed_k4 = 1;
 
 namespace {
 
@@ -396,9 +398,10 @@ int kpblock_bwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
                                                  d->grid_overflow, st));
     } else {
         WS_REQUIRE(d->t_offsets && d->t_pairs, "KPConv backward needs the search grid or the transposed table");
-        WS_TRY(ws_kpconv_gather_bwd_x_gated(d->q_pts, nq, d->s_pts, ns, d->inds, d->h, d->t_offsets, d->t_pairs, dwf, d->conv_in,
-                                            d->kernel_points, d->k, nullptr, nullptr, d->extent, WS_INFLUENCE_LINEAR,
-                                            WS_AGGREGATION_SUM, d->order_s, gate1, d->slope, dx1_out, st));
+        // (the strided blocks: four supports per wave where the packed form applies, the same dx bit for bit)
+        WS_TRY((ws_block_packed_k4 ? ws_kpconv_gather_bwd_x_packed : ws_kpconv_gather_bwd_x_gated)(
+            d->q_pts, nq, d->s_pts, ns, d->inds, d->h, d->t_offsets, d->t_pairs, dwf, d->conv_in, d->kernel_points, d->k, nullptr, nullptr,
+            d->extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, d->order_s, gate1, d->slope, dx1_out, st));
     }
     if (d->w1) {
         if (!gate1)

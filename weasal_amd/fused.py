@@ -74,6 +74,7 @@ def _bind():
         C.c_int.in_dll(lib, "ws_block_fused_infer").value = 1 if FUSED_INFER else 0
         C.c_int.in_dll(lib, "ws_block_gather_residual").value = 0 if os.environ.get("WEASAL_BLOCK_GATHER_RESIDUAL", "1") == "0" else 1
         C.c_int.in_dll(lib, "ws_block_pool_order").value = 0 if os.environ.get("WEASAL_POOL_ORDER", "1") == "0" else 1
+        C.c_int.in_dll(lib, "ws_block_packed_k4").value = 0 if os.environ.get("WEASAL_BLOCK_PACKED_K4", "1") == "0" else 1
         if "WEASAL_BLOCK_GROUP_ROWS" in os.environ:     # row limit of the grouped product launches; 0 = single launches
             C.c_int64.in_dll(lib, "ws_block_group_rows").value = int(os.environ["WEASAL_BLOCK_GROUP_ROWS"])
         _GATES_SET = True

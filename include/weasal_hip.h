@@ -870,7 +870,8 @@ int ws_sgd_step(float* const* h_params, const float* const* h_grads, float* cons
  *   add), modulations [n,k] = 2 sigmoid(last k columns) (NULL / ignored when not modulated), and kp4 [n,k] float4 =
  *   (x, y, z, modulation or 1): the packed operand of the entries below (16-byte aligned).  deformed_kp may be NULL.
  *   kp_rmax (device float, may be NULL) receives max |deformed kernel point| of the call: ws_kpconv_gather_bwd_x_grid_wide
- *   drops the pairs farther apart than kp_rmax + extent (no kernel point reaches them).
+ *   drops the pairs farther apart than kp_rmax + extent (no kernel point reaches them); given kp4 without kp_rmax it takes
+ *   the same maximum over kp4 itself first, so its result does not depend on whether the caller kept the scalar.
  * rows_sorted != 0 (ws_kpconv_gather_fwd_def, _bwd_geom_def, ws_kpconv_gather_fwd_ex): the caller vouches that every index
  *   row is sorted by distance from its query (what the radius search delivers).  A neighbour beyond the reach of every
  *   kernel point (max |kp| + extent) has 15 zero influences and one beyond max_k (sqrt(min_d2[k]) + |kp_k|) cannot lower

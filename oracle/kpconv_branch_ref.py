@@ -34,6 +34,30 @@ Error model (u = 2^-24; first order in u)
   dot_abs = sum_c |dwf| |x|), the coefficient a few roundings (sqrt, product, division, modulation: c1 = 8), the sum
   over h another h:  |err| <= (ci + h + c1) u Mg  with Mg the same sum over absolute values.  d modulations[q,k] =
   sum_h w dot: (ci + h + c1) u sum_h |w| dot_abs + c2 u sum_{h live} dot_abs.
+
+Deformable fast path (MODE 2: ws_kpconv_gather_fwd_def / _bwd_x_def / _bwd_geom_def; kp4 = (x, y, z, modulation))
+  The same formulas with three differences in how a term is evaluated; none of them moves a constant above.
+  * forward and dx: the weight is  max(1 - v_sqrt(d2) * (1 / extent), 0) * mod  -- the modulation multiplies the influence
+    before the product instead of the finished row.  1 / extent is a correctly rounded division (u), v_sqrt 1 ulp (2 u), the
+    product u, 1 - s at most u: 5 u absolute on w <= 1, i.e. <= 5 u |mod| on the modulated weight, inside
+    c2 max(1, |mod|) = 8 max(1, |mod|).  The product with mod rounds once (u, relative) where the generic kernel rounds the
+    row once: c1 = 2 as before.  The number of additions per element is unchanged (h, or the incoming products).
+  * geometry: sd = d2 * v_rsq(d2) replaces v_sqrt: v_rsq 1 ulp (2 u) and one product (u), 3 u relative on sd; with
+    1 / extent (u), the product (u) and 1 - s (u): <= 6 u absolute on w <= c2 = 8 (d modulation = sum_h w dot, the
+    unmodulated influence).
+  * geometry: the coefficient of (n - kp) is  dot * (mod * (1 / extent)) * rs:  1 / extent u, the product with mod u, v_rsq
+    2 u, two more products 2 u: 6 u relative <= c1 = 8; the fmaf into the running sum is one of the h additions, n - kp
+    is exact on the lattice.  Where mod = 0 the coefficient is an exact 0, and so is the bound.
+  min_d2: on a row with a real column every candidate of the minimum is a lattice distance, exact in f32; the tests keep
+  the 4 u |ref| of the generic deformable rows.  On a row of shadow columns only the minimum is the shadow point's own
+  distance, evaluated in f32 as  a = fl(1e6 - q)  (u, relative),  d = fl(a - kp)  (u, and a's error relative to d: |a| / |d|
+  <= 1 + 4e-6 since |kp| < 2), so d is 2 u off; d * d 4 u + u; the sum of three non-negative squares two more additions:
+  7 u (a contraction into fma only removes roundings) -> `min_d2_bound` takes 8 u |ref| there.  The d_min_d2 term of
+  d kp, 2 g (kp - (s* - q)) at the arg-min column s*, is a, the subtraction and the rounding of the fmaf that adds it: 3 u
+  relative to |kp| + |s* - q|, within the (h + 8) u that `geom_bounds` already grants it (h >= 1).
+  Sorted-row cutoff (CUT): the columns it skips have 15 zero influences and cannot lower a minimum; the skipped terms are
+  fmaf / MFMA steps with an exact 0 factor, and the lanes keep their columns: same summation split, results equal bit for
+  bit to the walk without the cutoff.
 """
 import numpy as np
 import torch
@@ -300,6 +324,73 @@ def geom_bounds(x, dwf, q, s, inds, deformed, mod, extent, influence, aggregatio
             gmin = np.abs(np.asarray(dmin, np.float64)[a:b])[..., None]
             tol_k[a:b] += (h + 8.0) * U * 2 * gmin * (np.abs(kq[a:b]) + np.abs(nstar))
     return tol_k, tol_m
+
+
+def _offsets(q, s, inds, a, b):
+    """neighbour offsets [B,H,3] of queries a..b in float64 (shadow index -> the point (1e6, 1e6, 1e6))"""
+    s_pad = np.concatenate([np.asarray(s, np.float64), np.full((1, 3), 1e6)])
+    return s_pad[np.asarray(inds)[a:b]] - np.asarray(q, np.float64)[a:b, None, :]
+
+
+def min_d2_bound(ref_min, q, s, inds, deformed):
+    """per-element tolerance [nq,K] of min_d2 (module docstring): 4 u |ref| where the arg-min column is a real neighbour,
+    8 u |ref| where it is a shadow column"""
+    inds = np.asarray(inds)
+    ns = np.asarray(s).shape[0]
+    kq = np.asarray(deformed, np.float64)
+    shadow = np.zeros(kq.shape[:2], bool)
+    for a in range(0, inds.shape[0], 128):
+        b = min(inds.shape[0], a + 128)
+        sq = ((_offsets(q, s, inds, a, b)[:, :, None, :] - kq[a:b, None]) ** 2).sum(-1)        # [B,H,K]
+        arg = sq.argmin(1)                                                                     # [B,K]
+        shadow[a:b] = np.take_along_axis(inds[a:b], arg, 1) >= ns
+    return np.where(shadow, 8.0, 4.0) * U * np.abs(np.asarray(ref_min, np.float64))
+
+
+def cutoff_counts(q, s, inds, deformed, extent):
+    """what a sorted-row case holds (float64): (queries whose last column with a non-zero influence is >= 64,
+    (query, kernel point) pairs whose min_d2 arg-min column is >= 64, queries whose first column is a real neighbour
+    already beyond max |kp| + extent, queries whose walk ends inside the second 64-column chunk, ... inside the third).
+    The walk of a query: the first chunk in full, then up to the first column farther from the query than
+    R = 1.0001 max(max |kp| + extent, max_k (sqrt(min d2[k] over the first chunk) + |kp_k|)); it ends inside a chunk when
+    that column is a real neighbour and neither the first nor past the last column of the chunk (the cutoff, not the end of
+    the row or of a chunk, ends it)."""
+    inds = np.asarray(inds)
+    ns = np.asarray(s).shape[0]
+    ext = float(np.float32(extent))
+    kq = np.asarray(deformed, np.float64)
+    last_far = arg_far = first_beyond = second = third = 0
+    cols = np.arange(inds.shape[1])
+    for a in range(0, inds.shape[0], 128):
+        b = min(inds.shape[0], a + 128)
+        n = _offsets(q, s, inds, a, b)
+        sq = ((n[:, :, None, :] - kq[a:b, None]) ** 2).sum(-1)                                  # [B,H,K]
+        real = inds[a:b] < ns
+        infl = ((sq < ext * ext).any(-1)) & real                                               # [B,H]
+        last = np.where(infl, cols[None], -1).max(1)
+        last_far += int((last >= 64).sum())
+        arg_far += int((sq.argmin(1) >= 64).sum())
+        rk = np.sqrt((kq[a:b] ** 2).sum(-1))                                                    # [B,K]
+        reach = rk.max(1) + ext
+        dn = np.sqrt((n ** 2).sum(-1))                                                          # [B,H]
+        first_beyond += int((real[:, 0] & (dn[:, 0] > reach)).sum())
+        big = 1.0001 * np.maximum(reach, (np.sqrt(sq[:, :64].min(1)) + rk).max(1))
+        beyond = (cols[None] >= 64) & ((dn > big[:, None]) | ~real)
+        stop = np.where(beyond.any(1), beyond.argmax(1), inds.shape[1])
+        ended = (stop < inds.shape[1]) & np.take_along_axis(real, np.minimum(stop, inds.shape[1] - 1)[:, None], 1)[:, 0]
+        second += int((ended & (stop > 64) & (stop < 128)).sum())
+        third += int((ended & (stop > 128) & (stop < 192)).sum())
+    return last_far, arg_far, first_beyond, second, third
+
+
+def worst_ratio(got, ref, tol):
+    """(largest |got - ref| / tol over the elements, number of elements); an element with tol = 0 counts 0 when it is exact
+    and inf otherwise"""
+    err = np.abs(np.asarray(got, np.float64) - np.asarray(ref, np.float64))
+    tol = np.broadcast_to(np.asarray(tol, np.float64), err.shape)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(tol > 0, err / tol, np.where(err == 0, 0.0, np.inf))
+    return (float(ratio.max()) if ratio.size else 0.0), int(err.size)
 
 
 def violations(got, ref, tol):

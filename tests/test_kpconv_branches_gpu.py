@@ -23,9 +23,9 @@ with the real device pointers and has to name the row's kernel, every template a
                     (G = 16 only: <=64: 1, <=128: 2, else 4); ilv = GRID_INTERLEAVE when the supports have a point order.
 Unreachable through a public entry (so not in the table): kpconv_gather_fwd_mfma_kernel<..., VECROW=false> (never
 instantiated: the dispatch always passes VECROW = true and masks NT = 1 rows instead); bf16 rows that are not 8-byte
-aligned or have ci % 4 != 0 (the entries refuse them: rows_vec4_or_f32 in every plan).  Left to other modules: MODE 2 (the
-deformable fast path, ws_kpconv_gather_*_def: test_deform_fast_gpu.py, test_bf16_deform_chain_gpu.py) and FUSE (the fused
-forward layer: test_infer_gpu.py).
+aligned or have ci % 4 != 0 (the entries refuse them: rows_vec4_or_f32 in every plan).  MODE 2 (the deformable fast path,
+ws_kpconv_gather_*_def) has its own table on this harness: DEF_BRANCHES in test_kpconv_def_branches_gpu.py.  Left to another
+module: FUSE (the fused forward layer: test_infer_gpu.py).
 
 Inputs: points on a 2^-6 lattice, kernel points 2^-7 off it (oracle/kpconv_branch_ref.py: every squared distance exact
 in f32, no decision flips; the setup asserts the extent margin).  Reference: oracle.kpconv_ref.kpconv_gather_ref in

@@ -2529,6 +2529,21 @@ void dispatch(F&& f, Pick<Vs...> a, Rest... rest)
 template <int BF> using Row = std::conditional_t<BF != 0, bf16_t, float>;
 int launched() { WS_LAUNCH_CHECK(); return WS_OK; }      // the end of every launcher
 
+// max |kernel point| over kp4 [n] float4, the value ws_kpconv_deform_prepare hands out as kp_rmax, bit for bit (the same
+// expression without contraction, the same correctly rounded root; a maximum does not depend on the order): what
+// ws_kpconv_gather_bwd_x_grid_wide bounds its candidates with when the caller passes no kp_rmax.  rmax_bits is zeroed before.
+__global__ __launch_bounds__(256) void kp4_rmax_kernel(const float4* __restrict__ kp4, int64_t n, int* __restrict__ rmax_bits)
+{
+#pragma clang fp contract(off)
+    int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) e = n - 1;                                          // (tail lanes redo the last element: every lane reduces)
+    const float4 v = kp4[e];
+    float r = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) r = fmaxf(r, __shfl_xor(r, o, 64));
+    if ((threadIdx.x & 63) == 0 && __float_as_int(r) > *(volatile int*)rmax_bits) atomicMax(rmax_bits, __float_as_int(r));
+}
+
 // the grid blob of the search (ws_grid.h) as K4G reads it
 struct GridView {
     const CloudGrid* grids;
@@ -2758,6 +2773,27 @@ int ws_kpconv_gather_bwd_x_grid_wide(const float* s_pts, int64_t ns, const void*
     WS_REQUIRE(!rows || rows_h >= 1, "index rows given without their width");
     GatherPlan p;
     if (int rc = bwd_x_gridw_plan(rows_bf16 != 0, ns, ci, dwf, dx, kp4 != nullptr, order != nullptr, p)) return rc;
+    // no kp_rmax from the caller: the entry takes the maximum itself, so the candidates -- and with them the 64-pair batches and
+    // the association of the sums -- do not depend on whether the caller kept the scalar.  The word is stream-ordered memory of
+    // this call (freed on every way out); not under a stream capture, where the allocation would become a node of the graph:
+    // a captured caller passes kp_rmax.  (The helper launch is not counted: ws_launch_count counts the entry's one launch.)
+    struct OwnWord {
+        float* p = nullptr;
+        hipStream_t st;
+        ~OwnWord() { if (p) (void)hipFreeAsync(p, st); }
+    } own{nullptr, (hipStream_t)stream};
+    if (kp4 && !kp_rmax) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        WS_HIP(hipStreamIsCapturing(own.st, &cap));
+        if (cap != hipStreamCaptureStatusNone)
+            return ws_fail(WS_ERR_UNSUPPORTED, "deformable grid backward under a stream capture needs kp_rmax from the caller");
+        WS_HIP(hipMallocAsync((void**)&own.p, sizeof(float), own.st));
+        WS_HIP(hipMemsetAsync(own.p, 0, sizeof(float), own.st));
+        kp4_rmax_kernel<<<(unsigned)ws_ceil_div(ns * (int64_t)k, 256), 256, 0, own.st>>>(
+            reinterpret_cast<const float4*>(kp4), ns * (int64_t)k, reinterpret_cast<int*>(own.p));
+        WS_HIP(hipGetLastError());
+        kp_rmax = own.p;
+    }
     GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, kp4 ? 1 : 0, nullptr, 0.0f, rows, rows_h,
                  reinterpret_cast<const float4*>(kp4), kp4 ? kp_rmax : nullptr, 0, p.ilv};
     const GridView v = grid_view(grid_blob, nb, cells, key_last, radius);

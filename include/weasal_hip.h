@@ -788,6 +788,58 @@ int ws_anchor_overlap_fill(const float* points, int64_t n, const int64_t* anchor
                            int64_t nnz_sel, int64_t* out_ptr, int64_t* out_idx, uint32_t* out_bits, double* out_centres, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The per-sphere regions of the weak-label sampler and their means (csrc/regions.hip): datasets/DALES_WeakLabel.py:424-451
+ * (identical in Vaihingen3D_WeakLabel.py:418-445) and the averaging of models/architectures.py:752-768.
+ * A batch holds n_spheres <= 64 spheres; sphere s owns the rows row_off[s] .. row_off[s + 1] of the stacked batch, its slice
+ * of input_inds [n_rows] (ASCENDING tile point ids, the sampler's order) and its float64 centre.  The (sphere, anchor) pairs
+ * are numbered pair_off[s] + a, a < anchors of the sphere's tile: `pairs` in all, sphere by sphere, so that the pair order
+ * is (sphere, ascending anchor id).  row_off / pair_off: int64 [n_spheres + 1] on the device.  The tile-dependent entries
+ * take one tile and `group` [n_group] int32, the spheres of the batch that were cut from it: one call per tile.
+ * ws_region_cut_count: :433-449 -- for every pair of the group: candidate iff d2 = (dx*dx + dy*dy) + dz*dz <= radius*radius,
+ *   d = anchor centre - sphere centre, float64, every product and sum rounded (radius is the host's in_radius - sub_radius
+ *   - 0.01, :434); cnt[pair] = the members of the anchor (anchor_ptr / anchor_idx, the AnchorSet's CSR) found in the
+ *   sphere's slice by binary search (np.in1d, :445), or 0 when the pair is no candidate, when nothing is found, or when the
+ *   only one found is the slice's row 0 (`if idx.any()`, :449).  Every pair of the group is written.
+ * ws_region_cut_scan: slot / ptr32 [pairs + 1] = exclusive scans of (cnt > 0) and cnt; words[WS_REGION_TOTAL_ROWS] = kept
+ *   regions, [WS_REGION_TOTAL_NNZ] = their rows in all; cloud_lb [n_spheres, n_class] float32, column k = 1 iff a row of
+ *   the sphere has label k (:474-476; labels int64 [n_rows], already mapped); a label outside [0, n_class) sets nothing
+ *   and words[WS_REGION_BAD_LABEL] += 1.  words: WS_REGION_WORDS int64, rewritten here: the ONE thing the host reads.
+ *   pairs = 0 computes cloud_lb only.  scratch: ws_region_scratch_bytes(pairs).  n_class <= 32, pairs < 2^31.
+ * ws_region_cut_fill: :445-451 -- after the read, for the kept pairs of the group, region r = slot[pair]: out_ptr[r] =
+ *   ptr32[pair] (the caller sets out_ptr[n_regions] = nnz), out_idx = row_off[s] + position in the slice, ascending
+ *   (np.searchsorted, :447; ballot + prefix popcount, no atomics), out_reg [nnz] int32 = r at every row of the region,
+ *   out_sphere [R] int32, out_anchor [R] int64, out_lb [R, n_class] float32 unpacked from anchor_bits (:451), out_inv_len
+ *   [R] float32 = 1.0f / (float) length.
+ * ws_region_mean_fwd: architectures.py:752-768 -- out[r, :] = (sum over i in region_ptr[r] .. region_ptr[r + 1] of
+ *   x[region_idx[i], :]) * inv_len[r], x [n, w] float32 row-major, w <= 256 (else WS_ERR_UNSUPPORTED), float32 sums in an
+ *   order fixed by w and the region's length alone.  Every element of out [n_regions, w] is stored.
+ * ws_region_mean_bwd: grad_x[p, :] = sum over i in t_ptr[p] .. t_ptr[p + 1] of grad_out[t_reg[i], :] * inv_len[t_reg[i]],
+ *   in that order (t_ptr int64 [n + 1], t_reg int32 [nnz]: the transpose point -> regions).  No atomics; every row of
+ *   grad_x [n, w] is stored, a row in no region as zeros.
+ * All: queued on `stream`, nothing synchronises, nothing is read back; sizes are checked before the device is touched; an
+ *   offset or index outside its range is never dereferenced (the entry is skipped).  The same bytes on every run.
+ * ------------------------------------------------------------------------------------------ */
+enum { WS_REGION_TOTAL_ROWS = 0, WS_REGION_TOTAL_NNZ = 1, WS_REGION_BAD_LABEL = 2, WS_REGION_WORDS = 3 };
+enum { WS_REGION_MAX_SPHERES = 64, WS_REGION_MAX_WIDTH = 256 };
+int64_t ws_region_scratch_bytes(int64_t pairs);
+int ws_region_cut_count(const double* centres, const int64_t* anchor_ptr, const int64_t* anchor_idx, int64_t anchor_nnz,
+                        int64_t n_anchors, const int32_t* group, int32_t n_group, int32_t n_spheres, const double* sphere_centres,
+                        const int64_t* row_off, const int64_t* pair_off, const int64_t* input_inds, int64_t n_rows, int64_t pairs,
+                        double radius, int32_t* cnt, void* stream);
+int ws_region_cut_scan(int32_t* cnt, int64_t pairs, int32_t* slot, int32_t* ptr32, const int64_t* labels, const int64_t* row_off,
+                       int64_t n_rows, int32_t n_spheres, int32_t n_class, float* cloud_lb, int64_t* words, void* scratch, void* stream);
+int ws_region_cut_fill(const int64_t* anchor_ptr, const int64_t* anchor_idx, int64_t anchor_nnz, const uint32_t* anchor_bits,
+                       int64_t n_anchors, const int32_t* group, int32_t n_group, int32_t n_spheres, const int64_t* row_off,
+                       const int64_t* pair_off, const int64_t* input_inds, int64_t n_rows, int64_t pairs, const int32_t* cnt,
+                       const int32_t* slot, const int32_t* ptr32, int64_t n_regions, int64_t nnz, int32_t n_class, int64_t* out_ptr,
+                       int64_t* out_idx, int32_t* out_reg, int32_t* out_sphere, int64_t* out_anchor, float* out_lb, float* out_inv_len,
+                       void* stream);
+int ws_region_mean_fwd(const float* x, int64_t n, int32_t w, const int64_t* region_ptr, const int64_t* region_idx, int64_t nnz,
+                       const float* inv_len, int64_t n_regions, float* out, void* stream);
+int ws_region_mean_bwd(const float* grad_out, int64_t n_regions, int32_t w, const int64_t* t_ptr, const int32_t* t_reg, int64_t nnz,
+                       const float* inv_len, int64_t n, float* grad_x, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The sphere sampler on tiles resident in device memory: datasets/DALES_PseudoLabel.py:265-518 (`potential_item`) with
  * datasets/common.py:252-334 (`augmentation_transform`), a whole batch per call and no host round trip per sphere.
  *

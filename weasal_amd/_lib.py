@@ -150,6 +150,13 @@ SIGNATURES = {
     "ws_anchor_overlap_plan": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ws_anchor_overlap_fill": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                         _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ws_region_scratch_bytes": (_i64, [_i64]),
+    "ws_region_cut_count": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i64, C.c_double, _vp, _vp]),
+    "ws_region_cut_scan": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ws_region_cut_fill": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64,
+                                    _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ws_region_mean_fwd": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "ws_region_mean_bwd": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "ws_sampler_create": (C.c_int, [C.POINTER(_vp)]),
     "ws_sampler_destroy": (None, [_vp]),
     "ws_sampler_add_cloud": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),

@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from . import fused, ops
 from .blocks import KPConv, NearestUpsampleBlock, UnaryBlock, block_decider, closest_pool
+from .regions import SphereRegions
 
 _LAYER_CHANGE = ('pool', 'strided', 'upsample', 'global')
 REGULARIZER_KERNEL = os.environ.get("WEASAL_REG_KERNEL", "1") != "0"      # A/B switch: 0 = the torch-op form below
@@ -459,7 +460,16 @@ class KPFCNN_mprm(nn.Module):
 
     def region_mprm_loss(self, cam, regions_all, regions_lb, batch_lengths):
         """overlap-region loss (architectures.py:735-784): the four class-activation maps are averaged over every
-        labelled sub-region of every sphere and compared with the sub-region's weak labels"""
+        labelled sub-region of every sphere and compared with the sub-region's weak labels.  regions_all: the reference's
+        per-sphere lists, or a regions.SphereRegions (device CSR): then the maps go side by side through ops.region_mean, no
+        host array is built, nothing is uploaded, and regions_lb / batch_lengths are not looked at"""
+        if isinstance(regions_all, SphereRegions):
+            c = int(cam[0].shape[1])
+            averaged = ops.region_mean(torch.cat(list(cam), dim=1), regions_all)      # [R, K * C]
+            self.output_loss = 0
+            for ii in range(len(cam)):
+                self.output_loss = self.output_loss + self.criterion_multi(averaged[:, ii * c:(ii + 1) * c], regions_all.lb)
+            return self.output_loss
         dev = cam[0].device
         cam_all = torch.stack(cam, dim=0)                              # [4, N, C]
         # The reference averages region by region (one index upload and one gather per region, :752-768).  Same means as ONE

@@ -1314,6 +1314,76 @@ def contrast_rows(on, xs, slc_idx, certain, lbl, temperature, eps):
 
 
 # ------------------------------------------------------------------------------------------------
+# region means of the overlap-region loss (models/architectures.py:752-768) over a regions.SphereRegions
+# ------------------------------------------------------------------------------------------------
+REGION_MAX_WIDTH = 256           # WS_REGION_MAX_WIDTH
+
+
+def _region_width(w):
+    if not 1 <= int(w) <= REGION_MAX_WIDTH:
+        raise ValueError("region_mean takes 1 to %d columns (got %d)" % (REGION_MAX_WIDTH, int(w)))
+
+
+def region_mean_fwd(x, regions, out=None):
+    """out [R, W] float32 = the mean of the rows x[idx] of every region (ws_region_mean_fwd); x [N, W] float32 on the device,
+    W <= 256 (ValueError beyond).  out: a contiguous float32 [R, W] buffer to fill instead of a new one."""
+    _need_cuda(x, regions.ptr, regions.idx, regions.inv_len)
+    if x.dim() != 2:
+        raise ValueError("region_mean: x must be [N, W]")
+    _region_width(x.shape[1])
+    if x.shape[0] != regions.n_rows:
+        raise ValueError("region_mean: x holds %d rows, the regions were cut from %d" % (x.shape[0], regions.n_rows))
+    xc = _f32c(x)
+    r, w = len(regions), int(x.shape[1])
+    if out is None:
+        out = torch.empty((r, w), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (r, w) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("region_mean: out must be a contiguous float32 [%d, %d] device tensor" % (r, w))
+    check(_lib.lib().ws_region_mean_fwd(ptr(xc), xc.shape[0], w, ptr(regions.ptr), ptr(regions.idx), regions.nnz, ptr(regions.inv_len),
+                                        r, ptr(out), current_stream()))
+    return out
+
+
+def region_mean_bwd(grad_out, regions, out=None):
+    """grad_x [N, W] float32 of region_mean_fwd for grad_out [R, W]: a gather through the transpose (ws_region_mean_bwd),
+    every row written, rows in no region exact zeros"""
+    _need_cuda(grad_out, regions.t_ptr, regions.t_reg, regions.inv_len)
+    if grad_out.dim() != 2 or grad_out.shape[0] != len(regions):
+        raise ValueError("region_mean: grad_out must be [R, W]")
+    _region_width(grad_out.shape[1])
+    g = _f32c(grad_out)
+    n, w = regions.n_rows, int(g.shape[1])
+    if out is None:
+        out = torch.empty((n, w), dtype=torch.float32, device=g.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, w) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("region_mean: out must be a contiguous float32 [%d, %d] device tensor" % (n, w))
+    check(_lib.lib().ws_region_mean_bwd(ptr(g), len(regions), w, ptr(regions.t_ptr), ptr(regions.t_reg), regions.nnz,
+                                        ptr(regions.inv_len), n, ptr(out), current_stream()))
+    return out
+
+
+class _RegionMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, regions):
+        ctx.regions = regions
+        return region_mean_fwd(x, regions)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return region_mean_bwd(grad_out, ctx.regions), None
+
+
+def region_mean(x, regions):
+    """[R, W] = mean over every region of the rows of x [N, W] (float32, W <= 256), differentiable in x; both directions are
+    run-to-run bit-identical (no float atomics)"""
+    _need_cuda(x)
+    if x.dim() != 2:
+        raise ValueError("region_mean: x must be [N, W]")
+    _region_width(x.shape[1])
+    return _RegionMean.apply(x, regions)
+
+
+# ------------------------------------------------------------------------------------------------
 # sphere sampler (datasets/DALES_PseudoLabel.py:265-518): thin binding of ws_sampler_*; the policy lives in sampler.py
 # ------------------------------------------------------------------------------------------------
 class SamplerHandle:

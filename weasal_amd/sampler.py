@@ -13,7 +13,10 @@ Differences from the reference, all deliberate:
   * `input_inds` of a sphere are in ascending index order (the KD-tree returns its traversal order; same set);
   * the per-point augmentation noise comes from a counter-based generator on the device, keyed by (seed, sphere sequence
     number, row, column), not from the host's stream;
-  * a batch is cut from at most `max_spheres` attempts (a dropped sphere, n < 2, uses one).
+  * a batch is cut from at most `max_spheres` attempts (a dropped sphere, n < 2, uses one);
+  * the sub-regions of the weak-label sampler (cut_regions, DALES_WeakLabel.py:424-451) are ordered by ascending anchor id,
+    and `if idx.any()` (:449) drops a region that holds local row 0 alone: here row 0 is the sphere's point with the
+    smallest tile index, in the reference whatever its KD-tree returned first.
 """
 import numpy as np
 import torch
@@ -111,6 +114,9 @@ class SphereSampler:
         self.failed = 0                   # dropped spheres so far
         self.lengths_dev = None
         self._sync_count = 0              # blocking device-to-host reads made by sample()
+        self._region_sync_count = 0       # blocking device-to-host reads made by cut_regions()
+        self.anchor_sets = None           # set_anchors
+        self._last_batch = None
         self._max_n = 0
         self._h_draws = torch.empty(MAX_SPHERES * DRAW_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
 
@@ -229,6 +235,7 @@ class SphereSampler:
         self.last_failed = head['n_fail']
         self.failed += head['n_fail']
         self.last_state = (head, slots)
+        self._last_batch = None
         if B == 0:
             return None
         kept = slots[:head['attempts']]
@@ -238,8 +245,37 @@ class SphereSampler:
         self.lengths_dev = per_sphere[0][:B]
         self.last_centres = kept[:, 5:8].copy().view(np.float64)
         points, features, labels, input_inds = (t[:total] for t in rows)
+        self._last_batch = (kept[:, 1].copy(), labels, input_inds, lengths)     # what cut_regions() works on
         return (points, features, labels, lengths, per_sphere[1][:B], per_sphere[2][:B], per_sphere[3][:B], per_sphere[4][:B],
                 input_inds)
+
+    # -----------------------------------------------------------------------------------------------------------
+    def set_anchors(self, anchor_sets):
+        """the anchors of every tile (anchors.AnchorSet, an empty one where a tile has none), in the order of `clouds`: what
+        cut_regions() cuts the sub-regions of a batch from (datasets/DALES_WeakLabel.py:201-269 builds them per tile).  Their
+        float64 centres go to the device once, here."""
+        from . import regions
+        anchor_sets = list(anchor_sets)
+        if len(anchor_sets) != len(self.sub_points):
+            raise ValueError("set_anchors needs one AnchorSet per cloud (%d clouds, %d sets)" % (len(self.sub_points), len(anchor_sets)))
+        for a in anchor_sets:
+            regions.prepare(a)
+        self.anchor_sets = anchor_sets
+
+    def cut_regions(self, n_class=None):
+        """-> regions.SphereRegions of the batch the last sample() returned (DALES_WeakLabel.py:424-451 and the per-sphere
+        class rows of :474-476): the kept spheres' tiles and centres come from that batch's state block, the rows from its
+        `input_inds`, `labels` and `lengths`.  One blocking read of its own, counted in `_region_sync_count`; sample() and
+        its single read are untouched.  n_class: config.num_classes unless given."""
+        from . import regions
+        if self.anchor_sets is None:
+            raise ValueError("cut_regions needs set_anchors first")
+        if self._last_batch is None:
+            raise ValueError("cut_regions needs a batch: call sample() first")
+        tiles, labels, input_inds, lengths = self._last_batch
+        self._region_sync_count += 1
+        return regions.cut_regions(self.anchor_sets, tiles, self.last_centres, input_inds, lengths, labels, self.config.in_radius,
+                                   self.config.sub_radius, self.config.num_classes if n_class is None else n_class)
 
     def __iter__(self):
         while True:

@@ -10,6 +10,8 @@ and are deliberately not reproduced.
 """
 import torch
 
+from .regions import SphereRegions
+
 
 class FusedSGD(torch.optim.SGD):
     """torch.optim.SGD (same constructor, param_groups, state / state_dict: `momentum_buffer` per parameter) whose step on
@@ -112,8 +114,13 @@ def train_step_weak(net, optimizer, batch, config, grad_sync=None):
       region_mprm_loss(cam, batch.region, batch.region_lb, batch.lengths[0]) or class_logits_loss(class_logits,
       batch.cloud_lb) by config.loss_type (:203-207) -> backward -> [all-reduce] -> clip_grad_NORM_(grad_clip_norm) (:216;
       the pseudo-label trainer clips by value) -> SGD step.
-    -> (loss, (logits, class_logits, cam)), or (None, None) for a skipped batch."""
-    if not any(len(r) > 0 for r in batch.region):
+    -> (loss, (logits, class_logits, cam)), or (None, None) for a skipped batch.
+    batch.region: the reference's per-sphere lists, or a regions.SphereRegions (the device CSR of sampler.cut_regions; none
+    kept = the skipped batch)."""
+    if isinstance(batch.region, SphereRegions):
+        if len(batch.region) == 0:
+            return None, None
+    elif not any(len(r) > 0 for r in batch.region):
         return None, None
     optimizer.zero_grad(set_to_none=grad_sync is None)
     logits, class_logits, cam = net(batch, config)

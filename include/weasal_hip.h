@@ -1019,6 +1019,42 @@ int ws_p2p_regularizer_fwd(const float* deformed_kp, const float* kp4, const flo
 int ws_p2p_regularizer_bwd(const float* deformed_kp, const float* kp4, const float* min_d2, int64_t n, int32_t k, float extent,
                            float repulse_extent, const float* g2, float* d_min_d2, float* d_deformed_kp, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-sphere dense attention of KPFCNN_mprm (models/blocks.py:758-1011), weasal_amd/csrc/attention.hip.
+ * `lengths` is a HOST vector of `nspheres` sphere sizes (rows are stacked sphere after sphere); every entry validates on the
+ * host before anything is queued: widths, lengths >= 0, sum(lengths) == n, NULL pointers.  The offsets travel in the kernel
+ * arguments: more than WS_ATT_MAX_SPHERES spheres is WS_ERR_UNSUPPORTED.  Zero-length spheres are legal and write nothing.
+ * No float atomics: every entry is run-to-run bit-identical.
+ *
+ * ws_sphere_attention_fwd (spatial_att, blocks.py:788-821: the loop over spheres with torch.matmul / nn.Softmax):
+ *   att [n, dv] = softmax(Q_s K_s^T) V_s per sphere s (no 1/sqrt(d) scale), xn = att / n_s; q, k [n, dq], v [n, dv] contiguous.
+ *   Streaming: no [n_s, n_s] tensor reaches memory.  lse: NULL, or [n] for the row log-sum-exp the backward entry needs;
+ *   att does not depend on whether it is given.  dq % 8 == 0, dq <= 64, dv % 64 == 0, dv <= 512, else WS_ERR_UNSUPPORTED.
+ * ws_sphere_attention_bwd: d_q, d_k [n, dq], d_v [n, dv] for the incoming d_att, d_xn [n, dv] (either may be NULL = zeros,
+ *   not both); att, lse as the forward wrote them; scratch >= ws_sphere_attention_bwd_scratch_bytes(n, dv).
+ *
+ * ws_channel_attention_fwd (channel_att, blocks.py:853-882, max_minus = 1; ele_att, blocks.py:984-1011, max_minus = 0):
+ *   per sphere E = X1_s^T X2_s [c, c], A_s = softmax_rows(max_minus ? rowmax(E) - E : E), out_s = Val_s A_s;
+ *   x1, x2, value, out [n, c] contiguous; a [nspheres, c, c] receives the A_s (kept for the backward entry).
+ *   c % 4 == 0, c <= 512, else WS_ERR_UNSUPPORTED.  scratch >= ws_channel_attention_scratch_bytes(lengths, nspheres, c, 0).
+ * ws_channel_attention_bwd: d_x1, d_x2, d_value [n, c] for d_out [n, c]; scratch >= ..._scratch_bytes(lengths, nspheres, c, 1).
+ *   In the max-minus form the gradient torch sends through the row maximum is sum_j dT_ij of a softmax backward, zero up
+ *   to rounding: it is not replayed. */
+#define WS_ATT_MAX_SPHERES 64
+int ws_sphere_attention_fwd(const float* q, const float* k, const float* v, int64_t n, int32_t dq, int32_t dv, const int64_t* lengths,
+                            int32_t nspheres, float* att, float* xn, float* lse, void* stream);
+int64_t ws_sphere_attention_bwd_scratch_bytes(int64_t n, int32_t dv);
+int ws_sphere_attention_bwd(const float* q, const float* k, const float* v, const float* att, const float* lse, const float* d_att,
+                            const float* d_xn, int64_t n, int32_t dq, int32_t dv, const int64_t* lengths, int32_t nspheres,
+                            float* d_q, float* d_k, float* d_v, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t ws_channel_attention_scratch_bytes(const int64_t* lengths, int32_t nspheres, int32_t c, int32_t backward);
+int ws_channel_attention_fwd(const float* x1, const float* x2, const float* value, int64_t n, int32_t c, const int64_t* lengths,
+                             int32_t nspheres, int32_t max_minus, float* a, float* out, void* scratch, int64_t scratch_bytes,
+                             void* stream);
+int ws_channel_attention_bwd(const float* x1, const float* x2, const float* value, const float* a, const float* d_out, int64_t n,
+                             int32_t c, const int64_t* lengths, int32_t nspheres, int32_t max_minus, float* d_x1, float* d_x2,
+                             float* d_value, void* scratch, int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

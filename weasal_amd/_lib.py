@@ -191,6 +191,12 @@ SIGNATURES = {
     "ws_p2p_regularizer_scratch_bytes": (_i64, [_i64]),
     "ws_p2p_regularizer_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp]),
     "ws_p2p_regularizer_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "ws_sphere_attention_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "ws_sphere_attention_bwd_scratch_bytes": (_i64, [_i64, _i32]),
+    "ws_sphere_attention_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ws_channel_attention_scratch_bytes": (_i64, [_vp, _i32, _i32, _i32]),
+    "ws_channel_attention_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "ws_channel_attention_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ws_timer_reset": (C.c_int, []),
     "ws_timer_count": (C.c_int, []),
     "ws_timer_read": (C.c_int, [_i32, _vp, _vp, _vp, _vp]),

@@ -28,6 +28,7 @@ from . import fused, ops
 from .kernel_points import load_kernels
 
 DEFORM_FAST_PATH = os.environ.get("WEASAL_DEFORM_FAST", "1") != "0"      # A/B switch (diagnostics, tests): 0 = generic kernels
+ATT_KERNELS = os.environ.get("WEASAL_ATT_KERNELS", "1") != "0"           # A/B switch: 0 = the attention blocks loop over spheres with torch.matmul
 
 
 # ---------------------------------------------------------------------------------------------
@@ -422,7 +423,15 @@ class MaxPoolBlock(nn.Module):
 # projections; same module names / state_dict keys as the reference.  Device agnostic: the reference's `.cuda()`
 # calls on fresh tensors (blocks.py:796,863,989) are replaced by "same device as the features", and its repeated
 # torch.cat inside the per-sphere loop by one cat at the end (same values).
+# On the GPU the loops are replaced by ops.sphere_attention / ops.channel_attention (weasal_amd/csrc/attention.hip: one
+# streaming launch for all spheres, no [n, n] tensor) when the features are float32 device tensors of a supported width and
+# WEASAL_ATT_KERNELS is not 0; everything else -- CPU tensors (oracle.kpconv_ref.cpu_reference_mode), other dtypes or
+# widths -- takes the loop.
 # ----------------------------------------------------------------------------------------------------------------------
+def _att_kernels(nspheres, *tensors):
+    return ATT_KERNELS and nspheres <= ops.ATT_MAX_SPHERES and all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
 def _per_cloud(lengths):
     """[(start, end)] of the stacked spheres; `lengths` is the host or device length vector of the layer"""
     ls = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
@@ -456,8 +465,12 @@ class spatial_att(nn.Module):
     def forward(self, features, batch):
         features = self.simple1(features, batch)
         q, k, v = self.unary1(features), self.unary2(features), self.unary3(features)
+        spans = _per_cloud(_layer_lengths(batch, self.layer_ind))
+        if _att_kernels(len(spans), q, k, v) and ops.sphere_attention_supported(q.shape[1], v.shape[1], len(spans), q.shape[0], v):
+            x, xn = ops.sphere_attention(q, k, v, [b - a for a, b in spans])
+            return self.simple2(self.gamma * x + features, batch), xn
         outs, outs_n = [], []
-        for a, b in _per_cloud(_layer_lengths(batch, self.layer_ind)):
+        for a, b in spans:
             att = torch.matmul(self.softmax(torch.matmul(q[a:b], k[a:b].T)), v[a:b])
             outs.append(att)
             outs_n.append(att / float(b - a))
@@ -488,8 +501,12 @@ class channel_att(nn.Module):
     def forward(self, features, batch):
         features = self.simple1(features, batch)
         x1, x2 = self.unary1(features), self.unary2(features)
+        spans = _per_cloud(_layer_lengths(batch, self.layer_ind))
+        if _att_kernels(len(spans), x1, x2, features) and ops.channel_attention_supported(features.shape[1]):
+            x = ops.channel_attention(x1, x2, features, [b - a for a, b in spans], True)
+            return self.simple2(self.gamma * x + features, batch)
         outs = []
-        for a, b in _per_cloud(_layer_lengths(batch, self.layer_ind)):
+        for a, b in spans:
             energy = torch.matmul(x1[a:b].T, x2[a:b])
             energy_new = torch.max(energy, -1, keepdim=True)[0].expand_as(energy) - energy
             outs.append(torch.matmul(features[a:b], self.softmax(energy_new)))
@@ -568,6 +585,10 @@ class ele_att(nn.Module):
             centre_z = h
         ele_f = torch.cat((h, h + centre_z), dim=1)
         query, key = self.unary1(ele_f), self.unary2(ele_f)
+        if _att_kernels(len(spans), query, key, features) and ops.channel_attention_supported(features.shape[1]) \
+                and query.shape == features.shape:
+            x = ops.channel_attention(query, key, features, [b - a for a, b in spans], False)
+            return self.simple2(self.gamma * x + features, batch)
         outs = []
         for a, b in spans:
             att = self.softmax(torch.matmul(query[a:b].T, key[a:b]))

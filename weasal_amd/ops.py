@@ -1431,3 +1431,121 @@ class SamplerHandle:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------------------------------------
+# per-sphere dense attention of KPFCNN_mprm (models/blocks.py:758-1011): ws_sphere_attention_* / ws_channel_attention_*
+# ------------------------------------------------------------------------------------------------
+ATT_MAX_SPHERES = 64             # WS_ATT_MAX_SPHERES
+
+
+def sphere_attention_supported(dq, dv, nspheres=1, rows=0, v=None):
+    """what ws_sphere_attention_* take: the widths, the sphere count, fewer than 2^22 stacked rows and, for a `v` that is
+    passed as it is (float32, contiguous), 16-byte aligned rows; anything else is refused by the library"""
+    if v is not None and v.dtype == torch.float32 and v.is_contiguous() and v.data_ptr() % 16 != 0:
+        return False
+    return (dq >= 8 and dq % 8 == 0 and dq <= 64 and dv >= 64 and dv % 64 == 0 and dv <= 512 and nspheres <= ATT_MAX_SPHERES
+            and rows < (1 << 22))
+
+
+def channel_attention_supported(c, nspheres=1):
+    """the widths ws_channel_attention_* take"""
+    return c >= 4 and c % 4 == 0 and c <= 512 and nspheres <= ATT_MAX_SPHERES
+
+
+def _att_lengths(lengths, n):
+    import ctypes as C
+    ls = [int(v) for v in lengths]
+    return (C.c_int64 * max(len(ls), 1))(*ls), len(ls)
+
+
+def _scratch(nbytes, device):
+    return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
+
+
+class _SphereAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, lengths):
+        qc, kc, vc = _f32c(q), _f32c(k), _f32c(v)
+        n, dq, dv = int(qc.shape[0]), int(qc.shape[1]), int(vc.shape[1])
+        lens, ns = _att_lengths(lengths, n)
+        att = torch.empty((n, dv), dtype=torch.float32, device=q.device)
+        xn = torch.empty((n, dv), dtype=torch.float32, device=q.device)
+        need = any(ctx.needs_input_grad[:3])
+        lse = torch.empty((n,), dtype=torch.float32, device=q.device) if need else None
+        check(_lib.lib().ws_sphere_attention_fwd(ptr(qc), ptr(kc), ptr(vc), n, dq, dv, lens, ns, ptr(att), ptr(xn), ptr(lse),
+                                                 current_stream()))
+        if need:
+            ctx.save_for_backward(qc, kc, vc, att, lse)
+            ctx.lengths = lengths
+        return att, xn
+
+    @staticmethod
+    def backward(ctx, d_att, d_xn):
+        qc, kc, vc, att, lse = ctx.saved_tensors
+        n, dq, dv = int(qc.shape[0]), int(qc.shape[1]), int(vc.shape[1])
+        lens, ns = _att_lengths(ctx.lengths, n)
+        d_q, d_k, d_v = torch.empty_like(qc), torch.empty_like(kc), torch.empty_like(vc)
+        if d_att is None and d_xn is None:
+            return d_q.zero_(), d_k.zero_(), d_v.zero_(), None
+        lib = _lib.lib()
+        nbytes = lib.ws_sphere_attention_bwd_scratch_bytes(n, dv)
+        scratch = _scratch(nbytes, qc.device)
+        da, dx = _f32c(d_att), _f32c(d_xn)         # (contiguous copies of strided gradients: alive until the call is queued)
+        check(lib.ws_sphere_attention_bwd(ptr(qc), ptr(kc), ptr(vc), ptr(att), ptr(lse), ptr(da), ptr(dx), n, dq, dv,
+                                          lens, ns, ptr(d_q), ptr(d_k), ptr(d_v), ptr(scratch), nbytes, current_stream()))
+        return d_q, d_k, d_v, None
+
+
+def sphere_attention(q, k, v, lengths):
+    """(att, xn): per sphere att = softmax(Q K^T) V (no scale) and xn = att / n_sphere (models/blocks.py:788-821), streaming
+    -- no [n, n] tensor exists, forward or backward; q, k [N, dq], v [N, dv] float32 on the device, `lengths` a HOST sequence
+    of sphere sizes summing to N.  dq % 8 == 0, dq <= 64, dv % 64 == 0, dv <= 512 and at most 64 spheres, else the library's
+    unsupported error.  Differentiable in q, k, v; both directions are run-to-run bit-identical."""
+    _need_cuda(q, k, v)
+    if q.dim() != 2 or k.shape != q.shape or v.dim() != 2 or v.shape[0] != q.shape[0]:
+        raise ValueError("sphere_attention: q, k must be [N, dq] and v [N, dv]")
+    return _SphereAttention.apply(q, k, v, lengths)
+
+
+class _ChannelAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x1, x2, value, lengths, max_minus):
+        x1c, x2c, vc = _f32c(x1), _f32c(x2), _f32c(value)
+        n, c = int(x1c.shape[0]), int(x1c.shape[1])
+        lens, ns = _att_lengths(lengths, n)
+        lib = _lib.lib()
+        a = torch.empty((ns, c, c), dtype=torch.float32, device=x1.device)
+        out = torch.empty((n, c), dtype=torch.float32, device=x1.device)
+        nbytes = lib.ws_channel_attention_scratch_bytes(lens, ns, c, 0)
+        scratch = _scratch(nbytes, x1.device)
+        check(lib.ws_channel_attention_fwd(ptr(x1c), ptr(x2c), ptr(vc), n, c, lens, ns, int(bool(max_minus)), ptr(a), ptr(out),
+                                           ptr(scratch), nbytes, current_stream()))
+        if any(ctx.needs_input_grad[:3]):
+            ctx.save_for_backward(x1c, x2c, vc, a)
+            ctx.lengths, ctx.max_minus = lengths, bool(max_minus)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        x1c, x2c, vc, a = ctx.saved_tensors
+        n, c = int(x1c.shape[0]), int(x1c.shape[1])
+        lens, ns = _att_lengths(ctx.lengths, n)
+        lib = _lib.lib()
+        d_x1, d_x2, d_v = torch.empty_like(x1c), torch.empty_like(x2c), torch.empty_like(vc)
+        nbytes = lib.ws_channel_attention_scratch_bytes(lens, ns, c, 1)
+        scratch = _scratch(nbytes, x1c.device)
+        do = _f32c(d_out)                          # (a contiguous copy of a strided gradient: alive until the call is queued)
+        check(lib.ws_channel_attention_bwd(ptr(x1c), ptr(x2c), ptr(vc), ptr(a), ptr(do), n, c, lens, ns, int(ctx.max_minus),
+                                           ptr(d_x1), ptr(d_x2), ptr(d_v), ptr(scratch), nbytes, current_stream()))
+        return d_x1, d_x2, d_v, None, None
+
+
+def channel_attention(x1, x2, value, lengths, max_minus):
+    """out [N, c]: per sphere E = X1^T X2 [c, c], A = softmax_rows(rowmax(E) - E if max_minus else E), out = value A
+    (channel_att, models/blocks.py:853-882: max_minus; ele_att, blocks.py:984-1011: plain); x1, x2, value [N, c] float32 on
+    the device, `lengths` a HOST sequence.  c % 4 == 0, c <= 512, at most 64 spheres.  Differentiable in x1, x2, value."""
+    _need_cuda(x1, x2, value)
+    if x1.dim() != 2 or x2.shape != x1.shape or value.shape != x1.shape:
+        raise ValueError("channel_attention: x1, x2 and value must share one [N, c] shape")
+    return _ChannelAttention.apply(x1, x2, value, lengths, max_minus)

@@ -401,7 +401,12 @@ int64_t ws_pyramid_desc_bytes(void);   /* sizeof(ws_pyramid_desc): lets a bindin
  * lbl[slc_idx[j]] == lbl[i].  on [n,c] = L2-normalised logits (:475), xs [s,c] = on[slc_idx] (:476),
  * certain [n] uint8 (:433-435), lbl [n] int64 pseudo labels (:438-439).  rowmax / den / npos [n] are saved
  * for the backward, which returns d loss / d on (d_on [n,c], the slice rows' own contribution excluded) and
- * d loss / d xs (d_xs [s,c]; per-chunk partials in `scratch`, added in a fixed order).  c <= 16, s <= 1024.
+ * d loss / d xs (d_xs [s,c]; per-chunk partials in `scratch`, added in a fixed order).  c <= 16, s <= 1024
+ * (WS_ERR_UNSUPPORTED beyond).  Preconditions, the caller's to keep:
+ *   - the rows of on / xs have norm <= 1 (unit rows, or all-zero ones): the sums are taken against the bound |logit| <= 1/T;
+ *   - 0.023 <= temperature <= 1e26 (WS_ERR_INVALID outside): exp(-2/T) must be a normal float, -T / 1e-12 finite;
+ *   - lbl >= 0 wherever certain == 0 (a negative label of an uncertain point would collide with the kernels' markers for
+ *     padding columns and rows beyond n; ws_contrast_head_fwd cannot produce one: a given label, -1 included, is certain).
  * ------------------------------------------------------------------------------------------ */
 int ws_contrast_rows_fwd(const float* on, int64_t n, int32_t c, const float* xs, int32_t s, const int64_t* slc_idx,
                          const uint8_t* certain, const int64_t* lbl, float temperature, float eps, float* loss,
@@ -425,7 +430,9 @@ int ws_contrast_rows_bwd(const float* on, int64_t n, int32_t c, const float* xs,
  *   loss [1] = mean of the per_class entries > 0 (:498-504), w_cls [n_cls] = d loss / d pts_loss of a kept point of the class.
  * tail_bwd: g [1] -> g_row [n] (the `g` operand of ws_contrast_rows_bwd).
  * head_bwd: d_on [n,c] (modified in place: the slice rows' gradients d_xs [s,c] are added onto their points, duplicates in
- *   slot order) -> d_x [n, c] (row stride ldd) through the backward of the normalisation.   c <= 16, s <= 2048, n_cls <= 16. */
+ *   slot order) -> d_x [n, c] (row stride ldd) through the backward of the normalisation.
+ * c <= 16, n_cls <= 16 (WS_ERR_INVALID beyond); s <= 1024, the limit of the rows entries (WS_ERR_UNSUPPORTED beyond, before
+ * any launch). */
 int64_t ws_contrast_head_scratch_bytes(int64_t n);
 int ws_contrast_head_fwd(const float* x, int64_t n, int32_t c, int64_t ldx, const int64_t* labels, float threshold,
                          const float* u, const int64_t* r_given, int32_t s, float* on, float* inv_norm, uint8_t* certain,

@@ -183,6 +183,20 @@ def test_contrast_small_and_wide_inputs(n, c):
     assert slc.shape == (1000,) and int(slc.max()) < n
     assert abs(lk - lt) <= 5e-6 * max(1.0, abs(lt)), (lk, lt)
     assert float((gk - gt).abs().max()) <= 5e-5 * max(float(gt.abs().max()), 1e-12)
+    # and against the independent restatement (both forms above share the rows kernel): the device draw, expressed as the
+    # positions in the list of valid points that the oracle takes; the module's bar, 1e-4
+    with torch.no_grad():
+        lst = torch.where((torch.softmax(outputs, 1).max(1)[0] > 0.3) | (labels < 10))[0]
+    pos = torch.searchsorted(lst, slc)
+    assert torch.equal(lst[pos.clamp(max=lst.numel() - 1)], slc)
+    valid = lst.numel()
+    if valid < 1000:
+        assert torch.equal(slc[:valid], lst)
+    o_ref = outputs.clone().requires_grad_(True)
+    ref = contrast_loss_ref(o_ref, labels, 30, pos if valid >= 1000 else pos[valid:])
+    ref.backward()
+    assert abs(lk - float(ref.detach())) <= 1e-4 * max(1.0, abs(float(ref.detach()))), (lk, float(ref.detach()))
+    assert float((gk - o_ref.grad).abs().max()) <= 1e-4 * max(float(o_ref.grad.abs().max()), 1e-12)
 
 
 @pytest.mark.gpu

@@ -18,6 +18,7 @@ namespace {
 
 constexpr int CH_CMAX = 16;         // classes (columns of the logits) supported, = the [N, slc_con] kernels' limit
 constexpr int CH_BINS = 16;         // label bins of the tail (max(C, 10) in the reference's setting)
+constexpr int CH_SMAX = 1024;       // slice rows supported, = the [N, slc_con] kernels' limit (contrast_mfma.hip: CM_SMAX)
 constexpr int CH_MAXBLK = 8192;     // per-block counts the selection kernel keeps in LDS
 
 __global__ __launch_bounds__(256) void contrast_prepare_kernel(const float* __restrict__ x, int64_t n, int c, int64_t ldx,
@@ -337,7 +338,8 @@ int ws_contrast_head_fwd(const float* x, int64_t n, int32_t c, int64_t ldx, cons
     WS_REQUIRE((u != nullptr) != (r_given != nullptr), "exactly one of u / r_given must be given");
     WS_REQUIRE(n >= 1 && n < (int64_t)2147483647, "n out of range");
     WS_REQUIRE(c >= 1 && c <= CH_CMAX, "1 <= c <= 16 classes supported");
-    WS_REQUIRE(s >= 1 && s <= 2048, "1 <= s <= 2048 slice rows supported");
+    WS_REQUIRE(s >= 1, "s < 1");
+    if (s > CH_SMAX) return ws_fail(WS_ERR_UNSUPPORTED, "contrast head: s=%d (<= %d)", s, CH_SMAX);
     WS_REQUIRE(ldx >= c, "ldx < c");
     hipStream_t st = (hipStream_t)stream;
     const int rpb = rows_per_block(n);
@@ -382,7 +384,8 @@ int ws_contrast_head_bwd(float* d_on, const float* d_xs, const int64_t* slc_idx,
                          const float* inv_norm, int64_t n, int32_t c, float* d_x, int64_t ldd, void* stream)
 {
     WS_REQUIRE(d_on && d_xs && slc_idx && on && inv_norm && d_x, "NULL argument");
-    WS_REQUIRE(n >= 1 && c >= 1 && c <= CH_CMAX && s >= 1 && s <= 2048 && ldd >= c, "size out of range");
+    WS_REQUIRE(n >= 1 && c >= 1 && c <= CH_CMAX && s >= 1 && ldd >= c, "size out of range");
+    if (s > CH_SMAX) return ws_fail(WS_ERR_UNSUPPORTED, "contrast head: s=%d (<= %d)", s, CH_SMAX);
     hipStream_t st = (hipStream_t)stream;
     contrast_slice_add_kernel<<<(unsigned)ws_ceil_div(s, 4), 256, 0, st>>>(d_xs, slc_idx, s, c, d_on);
     WS_LAUNCH_CHECK();

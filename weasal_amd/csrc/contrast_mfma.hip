@@ -32,6 +32,9 @@ namespace {
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 constexpr int CM_SMAX = 1024;          // slice columns supported (the reference uses 1000)
+// temperatures the entries take.  The one-pass sums hold only while exp(-2 / T) is a normal float (-log(FLT_MIN) = 87.34; unit
+// rows in f32 reach |<o, s>| = 1 + a few ulps, so 2 / T stays below 87), and the backward's -T / (P + 1e-12) must stay finite at P = 0
+constexpr float CM_TMIN = 0.023f, CM_TMAX = 1.0e26f;
 constexpr int CM_CP = 17;              // channel pitch of the staged rows (C <= 16; odd: row- and column-wise operand reads both spread over the banks)
 
 __device__ __forceinline__ void lds_order()
@@ -264,6 +267,7 @@ int ws_contrast_rows_fwd(const float* on, int64_t n, int32_t c, const float* xs,
 {
     WS_REQUIRE(n >= 0 && c >= 1 && s >= 1, "bad sizes n=%lld c=%d s=%d", (long long)n, c, s);
     if (c > 16 || s > CM_SMAX) return ws_fail(WS_ERR_UNSUPPORTED, "contrast rows: c=%d (<= 16) s=%d (<= %d)", c, s, CM_SMAX);
+    WS_REQUIRE(temperature >= CM_TMIN && temperature <= CM_TMAX, "contrast rows: temperature %g outside [%g, %g]", (double)temperature, (double)CM_TMIN, (double)CM_TMAX);
     WS_REQUIRE(n < (1ll << 31), "n exceeds int32");
     if (n == 0) return WS_OK;
     WS_REQUIRE(on && xs && slc_idx && certain && lbl && loss && rowmax && den && npos, "NULL argument");
@@ -289,6 +293,7 @@ int ws_contrast_rows_bwd(const float* on, int64_t n, int32_t c, const float* xs,
 {
     WS_REQUIRE(n >= 0 && c >= 1 && s >= 1, "bad sizes n=%lld c=%d s=%d", (long long)n, c, s);
     if (c > 16 || s > CM_SMAX) return ws_fail(WS_ERR_UNSUPPORTED, "contrast rows: c=%d (<= 16) s=%d (<= %d)", c, s, CM_SMAX);
+    WS_REQUIRE(temperature >= CM_TMIN && temperature <= CM_TMAX, "contrast rows: temperature %g outside [%g, %g]", (double)temperature, (double)CM_TMIN, (double)CM_TMAX);
     WS_REQUIRE(d_xs, "NULL argument");
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {

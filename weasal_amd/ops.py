@@ -1293,6 +1293,19 @@ class _ContrastLoss(torch.autograd.Function):
         return d_x, None, None, None, None, None, None
 
 
+CONTRAST_MAX_SLICE = 1024                            # CM_SMAX / CH_SMAX: every contrast entry takes s <= 1024
+CONTRAST_TEMPERATURE = (0.023, 1.0e26)               # CM_TMIN, CM_TMAX (contrast_mfma.hip: where the one-pass sums hold)
+
+
+def _contrast_limits(s, temperature):
+    """refuse, before the first launch, what the rows kernels refuse"""
+    if not 1 <= int(s) <= CONTRAST_MAX_SLICE:
+        raise _lib.WeasalHipError("contrast: 1 <= slice rows <= %d supported (got %d)" % (CONTRAST_MAX_SLICE, int(s)))
+    lo, hi = CONTRAST_TEMPERATURE
+    if not lo <= float(temperature) <= hi:
+        raise _lib.WeasalHipError("contrast: temperature %r outside [%g, %g]" % (temperature, lo, hi))
+
+
 def contrast_loss(x, labels, draw, threshold, temperature=0.1, eps=1e-8, n_cls=None):
     """KPFCNN.contrast_loss (architectures.py:405-504) on logits x [N, C] (C <= 16) and labels [N] (>= 10 = unlabelled).
     `draw`: float32 [s] uniforms in [0, 1) (slot j takes valid point floor(u_j * num_valid)) or int64 [s] positions in the list
@@ -1302,14 +1315,19 @@ def contrast_loss(x, labels, draw, threshold, temperature=0.1, eps=1e-8, n_cls=N
         raise _lib.WeasalHipError("contrast_loss takes float32 logits [N, C <= 16] (got %s %s)" % (x.dtype, tuple(x.shape)))
     if draw.dtype not in (torch.float32, torch.int64) or draw.dim() != 1:
         raise _lib.WeasalHipError("contrast_loss: draw must be float32 uniforms or int64 positions [s]")
+    _contrast_limits(draw.shape[0], temperature)
     n_cls = max(int(x.shape[1]), 10) if n_cls is None else int(n_cls)
     return _ContrastLoss.apply(x, labels, draw.contiguous(), threshold, temperature, eps, n_cls)
 
 
 def contrast_rows(on, xs, slc_idx, certain, lbl, temperature, eps):
     """per-point supervised contrastive loss [N] (ws_contrast_rows_fwd / _bwd); on [N,C] normalised logits,
-    xs [S,C] = on[slc_idx], certain [N] bool, lbl [N] pseudo labels"""
+    xs [S,C] = on[slc_idx], certain [N] bool, lbl [N] pseudo labels.  C <= 16, S <= 1024, 0.023 <= temperature <= 1e26.
+    Preconditions the caller keeps (not checked): the rows of on have norm <= 1 (F.normalize output; the kernels sum against
+    |logit| <= 1 / temperature), and lbl >= 0 wherever certain is False (a negative label of an uncertain point collides with
+    the kernels' padding markers; given labels, which are always certain, may be negative)."""
     _need_cuda(on, xs)
+    _contrast_limits(xs.shape[0], temperature)
     return _ContrastRows.apply(on, xs, slc_idx, certain, lbl, temperature, eps)
 
 

@@ -36,6 +36,7 @@
 //             The transposed operands come from the b_row_stride / b_col_stride of ws_xb_problem where the MFMA product
 //             takes them (c % 32 == 0); for other widths the softmax backward writes A^T and dE^T beside dE.
 #include "ws_common.h"
+#include "ws_dispatch.h"
 #include <math.h>
 
 namespace {
@@ -439,31 +440,33 @@ int att_widths(int32_t dq, int32_t dv)
 
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// both launchers: the launch and its check
 template <int TR>
-void launch_pv(const AttSpheres& sp, int64_t tiles, const float* x, const float* y, const float* z, int dq, int dv, float* out, float* xn,
-               float* lse_out, const float* lse_in, hipStream_t st)
+int launch_pv(const AttSpheres& sp, int64_t tiles, const float* x, const float* y, const float* z, int dq, int dv, float* out, float* xn,
+              float* lse_out, const float* lse_in, hipStream_t st)
 {
     const int nst = dq <= 8 ? 2 : dq <= 32 ? 8 : 16;
     const bool wide = dv % 128 == 0;
     const dim3 grid((unsigned)tiles, (unsigned)(dv / (wide ? 128 : 64)));
-#define WS_ATT_PV(NSTV, CTV) sphere_att_pv_kernel<TR, NSTV, CTV><<<grid, 256, 0, st>>>(sp, x, y, z, dq, dv, out, xn, lse_out, lse_in)
-#define WS_ATT_PV_W(NSTV) do { if (wide) WS_ATT_PV(NSTV, 8); else WS_ATT_PV(NSTV, 4); } while (0)
-    if (nst == 2) WS_ATT_PV_W(2);
-    else if (nst == 8) WS_ATT_PV_W(8);
-    else WS_ATT_PV_W(16);
-#undef WS_ATT_PV_W
-#undef WS_ATT_PV
+    const bool called = dispatch([&](auto ns, auto ct) {
+        sphere_att_pv_kernel<TR, ns.value, ct.value><<<grid, 256, 0, st>>>(sp, x, y, z, dq, dv, out, xn, lse_out, lse_in);
+    }, Pick<2, 8, 16>{nst}, Pick<4, 8>{wide ? 8 : 4});
+    if (!called) return ws_no_instantiation("sphere_att_pv_kernel<TR=%d, NST=%d, CT=%d>", TR, nst, wide ? 8 : 4);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
 }
 
 template <int TR>
-void launch_dqk(const AttSpheres& sp, int64_t tiles, const float* x1, const float* y1, const float* x2, const float* y2, int dq, int dv,
-                const float* lse, const float* dsum, float* out, hipStream_t st)
+int launch_dqk(const AttSpheres& sp, int64_t tiles, const float* x1, const float* y1, const float* x2, const float* y2, int dq, int dv,
+               const float* lse, const float* dsum, float* out, hipStream_t st)
 {
     const int nst = dq <= 8 ? 2 : dq <= 32 ? 8 : 16;
-    const dim3 grid((unsigned)tiles);
-    if (nst == 2) sphere_att_dqk_kernel<TR, 2><<<grid, 256, 0, st>>>(sp, x1, y1, x2, y2, dq, dv, lse, dsum, out);
-    else if (nst == 8) sphere_att_dqk_kernel<TR, 8><<<grid, 256, 0, st>>>(sp, x1, y1, x2, y2, dq, dv, lse, dsum, out);
-    else sphere_att_dqk_kernel<TR, 16><<<grid, 256, 0, st>>>(sp, x1, y1, x2, y2, dq, dv, lse, dsum, out);
+    const bool called = dispatch([&](auto ns) {
+        sphere_att_dqk_kernel<TR, ns.value><<<dim3((unsigned)tiles), 256, 0, st>>>(sp, x1, y1, x2, y2, dq, dv, lse, dsum, out);
+    }, Pick<2, 8, 16>{nst});
+    if (!called) return ws_no_instantiation("sphere_att_dqk_kernel<TR=%d, NST=%d>", TR, nst);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
 }
 
 int channel_args(int64_t n, int32_t c, const int64_t* lengths, int32_t nspheres)
@@ -503,9 +506,7 @@ int ws_sphere_attention_fwd(const float* q, const float* k, const float* v, int6
     if (n == 0) return WS_OK;
     WS_REQUIRE(q && k && v && att && xn, "NULL argument");
     WS_REQUIRE(al16(v), "v must be 16-byte aligned");
-    launch_pv<0>(sp, tiles, q, k, v, dq, dv, att, xn, lse, nullptr, (hipStream_t)stream);
-    WS_LAUNCH_CHECK();
-    return WS_OK;
+    return launch_pv<0>(sp, tiles, q, k, v, dq, dv, att, xn, lse, nullptr, (hipStream_t)stream);
 }
 
 int64_t ws_sphere_attention_bwd_scratch_bytes(int64_t n, int32_t dv)
@@ -537,13 +538,10 @@ int ws_sphere_attention_bwd(const float* q, const float* k, const float* v, cons
     hipStream_t st = (hipStream_t)stream;
     sphere_att_pre_kernel<<<(unsigned)ws_ceil_div(n, 4), 256, 0, st>>>(sp, n, dv, d_att, d_xn, att, d_o, dsum);
     WS_LAUNCH_CHECK();
-    launch_dqk<0>(sp, tiles, q, k, d_o, v, dq, dv, lse, dsum, d_q, st);
-    WS_LAUNCH_CHECK();
-    launch_pv<1>(sp, tiles, k, q, d_o, dq, dv, d_v, nullptr, nullptr, lse, st);
-    WS_LAUNCH_CHECK();
-    launch_dqk<1>(sp, tiles, k, q, v, d_o, dq, dv, lse, dsum, d_k, st);
-    WS_LAUNCH_CHECK();
-    return WS_OK;
+    rc = launch_dqk<0>(sp, tiles, q, k, d_o, v, dq, dv, lse, dsum, d_q, st);
+    if (rc == WS_OK) rc = launch_pv<1>(sp, tiles, k, q, d_o, dq, dv, d_v, nullptr, nullptr, lse, st);
+    if (rc == WS_OK) rc = launch_dqk<1>(sp, tiles, k, q, v, d_o, dq, dv, lse, dsum, d_k, st);
+    return rc;
 }
 
 int64_t ws_channel_attention_scratch_bytes(const int64_t* lengths, int32_t nspheres, int32_t c, int32_t backward)

@@ -27,6 +27,7 @@
 //              inner; d O accumulates in registers across the outer loop, d S per slice tile is summed over the four
 //              waves through LDS and written as the workgroup's partial (fixed-order reduction afterwards: deterministic).
 #include "ws_common.h"
+#include "ws_dispatch.h"
 
 namespace {
 
@@ -273,10 +274,12 @@ int ws_contrast_rows_fwd(const float* on, int64_t n, int32_t c, const float* xs,
     WS_REQUIRE(on && xs && slc_idx && certain && lbl && loss && rowmax && den && npos, "NULL argument");
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)ws_ceil_div(n, CF_WAVES * CF_TILES * 16);
-    if (c <= 4) contrast_fwd_mfma_kernel<1><<<grid, 64 * CF_WAVES, 0, st>>>(on, n, c, xs, s, slc_idx, certain, lbl, temperature, eps, loss, rowmax, den, npos);
-    else if (c <= 8) contrast_fwd_mfma_kernel<2><<<grid, 64 * CF_WAVES, 0, st>>>(on, n, c, xs, s, slc_idx, certain, lbl, temperature, eps, loss, rowmax, den, npos);
-    else if (c <= 12) contrast_fwd_mfma_kernel<3><<<grid, 64 * CF_WAVES, 0, st>>>(on, n, c, xs, s, slc_idx, certain, lbl, temperature, eps, loss, rowmax, den, npos);
-    else contrast_fwd_mfma_kernel<4><<<grid, 64 * CF_WAVES, 0, st>>>(on, n, c, xs, s, slc_idx, certain, lbl, temperature, eps, loss, rowmax, den, npos);
+    const int ns = (c + 3) / 4;       // MFMA steps per tile: c <= 4 / 8 / 12 / 16
+    const bool called = dispatch([&](auto nsv) {
+        contrast_fwd_mfma_kernel<nsv.value><<<grid, 64 * CF_WAVES, 0, st>>>(on, n, c, xs, s, slc_idx, certain, lbl, temperature, eps, loss, rowmax,
+                                                                           den, npos);
+    }, Pick<1, 2, 3, 4>{ns});
+    if (!called) return ws_no_instantiation("contrast_fwd_mfma_kernel<NS=%d> c=%d", ns, c);
     WS_LAUNCH_CHECK();
     return WS_OK;
 }
@@ -303,12 +306,12 @@ int ws_contrast_rows_bwd(const float* on, int64_t n, int32_t c, const float* xs,
     WS_REQUIRE(on && xs && slc_idx && certain && lbl && rowmax && den && npos && g && d_on && scratch, "NULL argument");
     const int chunks = (int)ws_ceil_div(n, 4 * CB_TILES * 16);
     float* partial = chunks == 1 ? d_xs : (float*)scratch;
-#define WS_CBM(NSV) contrast_bwd_mfma_kernel<NSV><<<chunks, 256, 0, st>>>(on, n, c, xs, s, slc_idx, certain, lbl, temperature, rowmax, den, npos, g, d_on, partial)
-    if (c <= 4) WS_CBM(1);
-    else if (c <= 8) WS_CBM(2);
-    else if (c <= 12) WS_CBM(3);
-    else WS_CBM(4);
-#undef WS_CBM
+    const int ns = (c + 3) / 4;       // MFMA steps per tile: c <= 4 / 8 / 12 / 16
+    const bool called = dispatch([&](auto nsv) {
+        contrast_bwd_mfma_kernel<nsv.value><<<chunks, 256, 0, st>>>(on, n, c, xs, s, slc_idx, certain, lbl, temperature, rowmax, den, npos, g, d_on,
+                                                                   partial);
+    }, Pick<1, 2, 3, 4>{ns});
+    if (!called) return ws_no_instantiation("contrast_bwd_mfma_kernel<NS=%d> c=%d", ns, c);
     WS_LAUNCH_CHECK();
     if (chunks > 1) {
         const int64_t elems = (int64_t)s * c;

@@ -16,7 +16,7 @@
 // order.  A operand lane map: A[i = lane&31][k = lane>>5]; B: B[k = lane>>5][j = lane&31];
 // C/D: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)  (cdna_hip_programming.md section 3).
 #include "ws_common.h"
-#include "ws_bf16.h"
+#include "ws_dispatch.h"
 
 namespace {
 
@@ -1195,19 +1195,60 @@ constexpr int THIN_K = 64;    // products with k <= this take 64-column tiles (m
 }  // namespace
 
 extern "C" {
-
 // diagnostic switches (not part of the drop-in surface of include/weasal_hip.h)
 int ws_gemm_shallow = 1;     // products with k <= 64 that the MFMA tiles do not take (k % 32 != 0), n % 4 == 0, many rows: 1 = gemm_xb_shallow_kernel, 0 = gemm_xb_kernel
 int ws_gemm_staged = 1;     // gemm_xb2 epilogue: 1 = the tile turned through LDS (whole 128-byte row segments per store), 0 = per-lane rows
-
-int64_t ws_gemm_xb_scratch_bytes(int64_t m, int32_t k, int32_t n)
-{
-    // room for up to 16 split-K partial outputs; only short, deep products use it
-    if (m <= 0 || m >= 32768 || k < 512) return 0;
-    return 16 * m * (int64_t)n * (int64_t)sizeof(float);
 }
 
-// The launch a product takes: every selection rule of gemm_xb_impl, shared with the reporter ws_gemm_xb_variant (which
+// ---------------------------------------------------------------------------------------------
+// Host side.  A product travels as a record -- ws_xb_problem / ws_xty_problem (ws_common.h) -- that every entry, single or
+// grouped, fills.  Per family: one validator (its messages carry "member <i>: " in a group), one plan shared with the reporter,
+// one launcher per kernel that dispatches the plan onto the template arguments (ws_dispatch.h), one run.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// a failed requirement of a product: the message of the single entries (member < 0), behind "member <i>: " for a group's member i
+int product_fail(int member, int code, const char* fmt, ...)
+{
+    char* buf = ws_errbuf();
+    const int off = member >= 0 ? snprintf(buf, 512, "member %d: ", member) : 0;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf + off, 512 - (size_t)off, fmt, ap);
+    va_end(ap);
+    return code;
+}
+#define PRODUCT_REQUIRE(member, cond, ...) do { if (!(cond)) return product_fail(member, WS_ERR_INVALID, __VA_ARGS__); } while (0)
+
+// ---- gemm_xb ----------------------------------------------------------------------------------------------------------------
+int xb_validate(const ws_xb_problem& q, int member)
+{
+    PRODUCT_REQUIRE(member, q.m >= 0 && q.k >= 1 && q.n >= 1 && q.ldx >= q.k && q.ldy >= q.n, "bad sizes m=%lld k=%d n=%d", (long long)q.m, q.k, q.n);
+    PRODUCT_REQUIRE(member, !q.residual || q.ldr >= q.n, "residual leading dimension too small");
+    PRODUCT_REQUIRE(member, q.act == 0 || q.act == 1, "unknown activation %d", q.act);
+    PRODUCT_REQUIRE(member, q.drop_p >= 0.0f && q.drop_p < 1.0f, "bad drop probability %g", (double)q.drop_p);
+    PRODUCT_REQUIRE(member, !q.res_rows || (q.residual && q.res_rows_ld >= 1 && q.res_nrows >= 0), "gathered residual: NULL residual / bad sizes");
+    PRODUCT_REQUIRE(member, !q.gate_y || q.ldg >= q.n, "gate leading dimension too small");
+    PRODUCT_REQUIRE(member, !q.mask || q.ldm >= q.n, "mask leading dimension too small");
+    PRODUCT_REQUIRE(member, q.m == 0 || (q.x && q.b && q.y), "NULL argument");
+    return WS_OK;
+}
+
+XbGate xb_problem_gate(const ws_xb_problem& q)
+{
+    XbGate g{};
+    g.y = q.gate_y; g.ld = q.ldg; g.slope = q.gate_slope;
+    g.mask = q.mask; g.ldm = q.ldm; g.mscale = q.mask_scale;
+    g.drop = ws_drop_args(q.drop_p, q.drop_seed);
+    g.dn = q.n;
+    g.rrows = q.res_rows; g.rld = q.res_rows_ld; g.rn = q.res_nrows;
+    return g;
+}
+
+// row stride of the small matrix (b_row_stride < 0: row-major [K, N])
+int64_t xb_brs(const ws_xb_problem& q) { return q.b_row_stride < 0 ? q.n : q.b_row_stride; }
+
+// The launch a product takes: every selection rule of the xb entries, shared with the reporter ws_gemm_xb_variant (which
 // only reads the pointers' alignment).
 enum { XB_NONE = 0, XB_XB2 = 1, XB_SHALLOW = 2, XB_GENERIC = 3 };
 struct XbPlan {
@@ -1221,21 +1262,22 @@ struct XbPlan {
     size_t lds;             // XB_SHALLOW: dynamic LDS bytes
 };
 
-static int xb_plan(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n, const float* bias,
-                   const float* residual, int64_t ldr, const float* y, int64_t ldy, const void* scratch, int64_t scratch_bytes,
-                   int64_t brs, int64_t bcs, const XbGate& gate, XbPlan& p)
+int xb_plan(const ws_xb_problem& q, XbPlan& p)
 {
     p = XbPlan{};
-    if (m == 0) return WS_OK;
-    const int vecx = al16(x) && (ldx % 4 == 0);
-    const int vecb = al16(b) && (n % 4 == 0);
+    if (q.m == 0) return WS_OK;
+    const int64_t m = q.m, brs = xb_brs(q), bcs = q.b_col_stride;
+    const int k = q.k, n = q.n;
+    const int vecx = al16(q.x) && (q.ldx % 4 == 0);
+    const int vecb = al16(q.b) && (n % 4 == 0);
     const int64_t gx = ws_ceil_div(m, BM);
     WS_REQUIRE(gx < (1ll << 31), "m too large");
-    if (vecx && k % 32 == 0 && n % 4 == 0 && al16(y) && ldy % 4 == 0 &&
-        (!residual || (al16(residual) && ldr % 4 == 0)) && (!bias || al16(bias)) &&
-        (int64_t)(k - 1) * brs + (int64_t)(n - 1) * bcs < (1ll << 29) && 128 * ldx < (1ll << 29) && al16(b) &&
-        (bcs == 1 ? true : (brs == 1 && bcs % 4 == 0)) &&
-        (!gate.y || (al16(gate.y) && gate.ld % 4 == 0)) && (!gate.mask || ((reinterpret_cast<uintptr_t>(gate.mask) & 3u) == 0 && gate.ldm % 4 == 0))) {
+    // what the float4 epilogues ask of everything they touch
+    const bool epi4 = n % 4 == 0 && al16(q.y) && q.ldy % 4 == 0 && (!q.residual || (al16(q.residual) && q.ldr % 4 == 0)) &&
+                      (!q.bias || al16(q.bias)) && (!q.gate_y || (al16(q.gate_y) && q.ldg % 4 == 0)) &&
+                      (!q.mask || ((reinterpret_cast<uintptr_t>(q.mask) & 3u) == 0 && q.ldm % 4 == 0));
+    if (vecx && k % 32 == 0 && epi4 && (int64_t)(k - 1) * brs + (int64_t)(n - 1) * bcs < (1ll << 29) && 128 * q.ldx < (1ll << 29) &&
+        al16(q.b) && (bcs == 1 ? true : (brs == 1 && bcs % 4 == 0))) {
         const int64_t tiles = ws_ceil_div(m, 32);
         int wn = tiles >= 2048 ? 1 : 2;
         if (n <= 32) wn = 1;
@@ -1243,11 +1285,11 @@ static int xb_plan(const float* x, int64_t m, int32_t k, int64_t ldx, const floa
         const unsigned gx2 = (unsigned)ws_ceil_div(m, 32 * (4 / wn)), gy2 = (unsigned)ws_ceil_div(n, 32 * nt * wn);
         const int nch = k / 32;
         int splits = 1;
-        if (scratch && (int64_t)gx2 * gy2 < 256 && nch >= 16) {
+        if (q.scratch && (int64_t)gx2 * gy2 < 256 && nch >= 16) {
             splits = (int)ws_ceil_div(768, (int64_t)gx2 * gy2);
             if (splits > nch / 8) splits = nch / 8;
             if (splits > 16) splits = 16;
-            if ((int64_t)splits * m * n * 4 > scratch_bytes) splits = (int)(scratch_bytes / (m * n * 4));
+            if ((int64_t)splits * m * n * 4 > q.scratch_bytes) splits = (int)(q.scratch_bytes / (m * n * 4));
             if (splits < 2) splits = 1;
         }
         const int csplit = (int)ws_ceil_div(nch, splits);
@@ -1258,9 +1300,7 @@ static int xb_plan(const float* x, int64_t m, int32_t k, int64_t ldx, const floa
     }
     WS_REQUIRE(bcs == 1 && brs == n, "a strided small matrix needs k %% 32 == 0, n %% 4 == 0 and 16-byte aligned rows "
                                      "(k=%d n=%d): pass a row-major [K,N] copy for this shape", k, n);
-    if (ws_gemm_shallow && k <= 64 && n % 4 == 0 && n <= 1024 && (int64_t)k * n <= 8192 && m >= 4096 && al16(b) && al16(y) && ldy % 4 == 0 &&
-        (!residual || (al16(residual) && ldr % 4 == 0)) && (!bias || al16(bias)) && (!gate.y || (al16(gate.y) && gate.ld % 4 == 0)) &&
-        (!gate.mask || ((reinterpret_cast<uintptr_t>(gate.mask) & 3u) == 0 && gate.ldm % 4 == 0))) {
+    if (ws_gemm_shallow && k <= 64 && n <= 1024 && (int64_t)k * n <= 8192 && m >= 4096 && al16(q.b) && epi4) {
         // shallow, ragged contraction over many rows: the streaming VALU form (gemm_xb_shallow_kernel)
         const int per = 256 / (n / 4);
         const int kp = (k + 3) & ~3;
@@ -1278,49 +1318,462 @@ static int xb_plan(const float* x, int64_t m, int32_t k, int64_t ldx, const floa
     return WS_OK;
 }
 
-static int gemm_xb_impl(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n,
-                        const float* bias, const float* residual, int64_t ldr, int32_t act, float slope,
-                        float* y, int64_t ldy, void* scratch, int64_t scratch_bytes, void* stream,
-                        int64_t brs = -1, int64_t bcs = 1, XbGate gate = XbGate{})
+// the (NT, WN) of gemm_xb2_kernel / gemm_xb2_group_kernel that exist; the index is the bucket of the grouped entry
+constexpr int XB2_PAIRS[][2] = {{1, 1}, {2, 1}, {4, 1}, {1, 2}, {2, 2}};
+constexpr int XB2_NPAIRS = 5;
+constexpr int xb2_pair(int nt, int wn)
 {
-    if (brs < 0) brs = n;                       // row-major [K,N]
-    WS_REQUIRE(m >= 0 && k >= 1 && n >= 1 && ldx >= k && ldy >= n, "bad sizes m=%lld k=%d n=%d", (long long)m, k, n);
-    WS_REQUIRE(!residual || ldr >= n, "residual leading dimension too small");
-    WS_REQUIRE(act == 0 || act == 1, "unknown activation %d", act);
-    if (m == 0) return WS_OK;
-    WS_REQUIRE(x && b && y, "NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    XbPlan p;
-    const int rc = xb_plan(x, m, k, ldx, b, n, bias, residual, ldr, y, ldy, scratch, scratch_bytes, brs, bcs, gate, p);
-    if (rc != WS_OK) return rc;
+    for (int i = 0; i < XB2_NPAIRS; ++i)
+        if (XB2_PAIRS[i][0] == nt && XB2_PAIRS[i][1] == wn) return i;
+    return -1;
+}
+int xb2_no_instantiation(const XbPlan& p) { return ws_no_instantiation("gemm_xb2_kernel<NT=%d, WN=%d>", p.nt, p.wn); }
+
+int launch_xb2(const ws_xb_problem& q, const XbPlan& p, const XbGate& gate, hipStream_t st)
+{
+    float* part = p.splits > 1 ? (float*)q.scratch : nullptr;
+    bool pruned = false;
+    const bool called = dispatch([&](auto nt, auto wn) {
+        if constexpr (xb2_pair(nt.value, wn.value) >= 0)
+            gemm_xb2_kernel<nt.value, wn.value><<<p.grid, 256, 0, st>>>(q.x, q.m, q.k, q.ldx, q.b, q.n, (int)xb_brs(q), (int)q.b_col_stride, q.y,
+                                                                        q.ldy, q.bias, q.residual, q.ldr, q.act, q.slope, p.csplit, part, gate,
+                                                                        p.staged);
+        else pruned = true;
+    }, Pick<1, 2, 4>{p.nt}, Pick<1, 2>{p.wn});
+    return called && !pruned ? WS_OK : xb2_no_instantiation(p);
+}
+
+// the epilogue of ONE split product (p.splits > 1): it counts with its product's launch (ws_common.h)
+void launch_splitk_epilogue(const ws_xb_problem& q, const XbPlan& p, const XbGate& gate, hipStream_t st)
+{
+    splitk_epilogue_kernel<<<ws_grid(q.m * (q.n / 4), 256), 256, 0, st>>>((const float*)q.scratch, p.splits, q.m, q.n, q.y, q.ldy, q.bias,
+                                                                          q.residual, q.ldr, q.act, q.slope, gate);
+}
+
+int launch_xb_generic(const ws_xb_problem& q, const XbPlan& p, const XbGate& gate, hipStream_t st)
+{
+    const bool called = dispatch([&](auto nt) {
+        gemm_xb_kernel<nt.value, 32><<<p.grid, 256, 0, st>>>(q.x, q.m, q.k, q.ldx, q.b, q.n, q.n, q.y, q.ldy, p.vecx, p.vecb, q.bias, q.residual,
+                                                             q.ldr, q.act, q.slope, gate);
+    }, Pick<1, 2, 4>{p.nt});
+    return called ? WS_OK : ws_no_instantiation("gemm_xb_kernel<NT=%d, BKX=32>", p.nt);
+}
+
+// product q (m > 0) by its plan: ONE counted launch
+int xb_launch(const ws_xb_problem& q, const XbPlan& p, hipStream_t st)
+{
+    const XbGate gate = xb_problem_gate(q);
+    int rc = WS_OK;
     if (p.kind == XB_XB2) {
-        float* part = p.splits > 1 ? (float*)scratch : nullptr;
-#define WS_XB2(NTV, WNV)                                                                                                   \
-    gemm_xb2_kernel<NTV, WNV><<<p.grid, 256, 0, st>>>(x, m, k, ldx, b, n, (int)brs, (int)bcs, y, ldy, bias, residual, ldr, act, \
-                                                      slope, p.csplit, part, gate, p.staged)
-        if (p.wn == 1) {
-            if (p.nt == 1) WS_XB2(1, 1);
-            else if (p.nt == 2) WS_XB2(2, 1);
-            else WS_XB2(4, 1);
-        } else {
-            if (p.nt == 1) WS_XB2(1, 2);
-            else WS_XB2(2, 2);
-        }
-#undef WS_XB2
-        if (p.splits > 1)
-            splitk_epilogue_kernel<<<ws_grid(m * (n / 4), 256), 256, 0, st>>>(part, p.splits, m, n, y, ldy, bias, residual, ldr,
-                                                                              act, slope, gate);
+        rc = launch_xb2(q, p, gate, st);
+        if (rc == WS_OK && p.splits > 1) launch_splitk_epilogue(q, p, gate, st);
     } else if (p.kind == XB_SHALLOW) {
-        gemm_xb_shallow_kernel<<<p.grid, 256, p.lds, st>>>(x, m, k, ldx, b, n, y, ldy, bias, residual, ldr, act, slope, gate, p.rows);
+        gemm_xb_shallow_kernel<<<p.grid, 256, p.lds, st>>>(q.x, q.m, q.k, q.ldx, q.b, q.n, q.y, q.ldy, q.bias, q.residual, q.ldr, q.act, q.slope,
+                                                           gate, p.rows);
     } else {
-#define WS_XB(NTV)                                                                                                         \
-    gemm_xb_kernel<NTV, 32><<<p.grid, 256, 0, st>>>(x, m, k, ldx, b, n, n, y, ldy, p.vecx, p.vecb, bias, residual, ldr, act, slope, gate)
-        if (p.nt == 1) WS_XB(1);
-        else if (p.nt == 2) WS_XB(2);
-        else WS_XB(4);
-#undef WS_XB
+        rc = launch_xb_generic(q, p, gate, st);
     }
+    if (rc != WS_OK) return rc;
     WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+int xb_run(const ws_xb_problem& q, void* stream)
+{
+    int rc = xb_validate(q, -1);
+    if (rc != WS_OK || q.m == 0) return rc;
+    XbPlan p;
+    rc = xb_plan(q, p);
+    return rc != WS_OK ? rc : xb_launch(q, p, (hipStream_t)stream);
+}
+
+// the record of the plain product y = x b, b row-major [K, N]: the entries add their strides, epilogue and gates
+ws_xb_problem xb_problem(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n, float* y, int64_t ldy,
+                         void* scratch = nullptr, int64_t scratch_bytes = 0)
+{
+    ws_xb_problem q{};
+    q.x = x; q.m = m; q.k = k; q.ldx = ldx;
+    q.b = b; q.b_row_stride = -1; q.b_col_stride = 1; q.n = n;
+    q.y = y; q.ldy = ldy;
+    q.scratch = scratch; q.scratch_bytes = scratch_bytes;
+    return q;
+}
+void xb_epilogue(ws_xb_problem& q, const float* bias, const float* residual, int64_t ldr, int32_t act, float slope)
+{
+    q.bias = bias; q.residual = residual; q.ldr = ldr; q.act = act; q.slope = slope;
+}
+void xb_strides(ws_xb_problem& q, int64_t b_row_stride, int64_t b_col_stride)
+{
+    q.b_row_stride = b_row_stride; q.b_col_stride = b_col_stride;
+}
+
+// ---- grouped products (ws_common.h) ------------------------------------------------------------------------------------------
+// Each member keeps exactly the plan it gets alone from xb_plan / xty_plan -- kind, tile variant, splits, csplit, chunk,
+// chunks, reduction form, pitched output -- and its workgroups run the single kernels' bodies on that plan, so every sum
+// is added in the order of the single launch: a grouped result is bit-identical to the single one.  Only the number of
+// launches changes.
+// one call plans at most GROUP_CALL_MAX members on the stack (no allocation on the launch path: the block calls pass 2 .. 4);
+// a longer list is handled as consecutive slices of that many, each grouped within itself
+constexpr int GROUP_CALL_MAX = 16;
+struct IdList {
+    int n = 0;
+    int v[GROUP_CALL_MAX];
+    void push_back(int i) { v[n++] = i; }
+    int size() const { return n; }
+};
+constexpr int64_t GROUP_MEMBER_BLOCKS = 1ll << 27;      // a member with more workgroups runs alone (the linear index stays 32-bit)
+
+// the members of one instantiation, GROUP_MAX at a time (more spill into further launches): f(ids, cnt) -> WS_OK or the error
+template <typename F>
+int for_each_launch(const IdList& ids, F&& f)
+{
+    for (int off = 0; off < ids.size(); off += GROUP_MAX) {
+        const int rc = f(ids.v + off, ids.size() - off < GROUP_MAX ? ids.size() - off : GROUP_MAX);
+        if (rc != WS_OK) return rc;
+    }
+    return WS_OK;
+}
+// running workgroup totals of a group: member j ends at end[j], entries past the last member repeat the total
+struct GroupFill {
+    GroupIndex& gi;
+    int n = 0;
+    unsigned total = 0;
+    void add(unsigned blocks)
+    {
+        total += blocks;
+        for (int j = n++; j < GROUP_MAX; ++j) gi.end[j] = total;
+    }
+};
+
+int launch_xb2_group(const ws_xb_problem* q, const XbPlan* plan, const int* ids, int cnt, hipStream_t st)
+{
+    Xb2Group g{};
+    SplitkGroup e{};
+    GroupFill gf{g.gi}, ef{e.gi};
+    int last_e = -1;
+    for (int j = 0; j < cnt; ++j) {
+        const ws_xb_problem& a = q[ids[j]];
+        const XbPlan& p = plan[ids[j]];
+        const XbGate gate = xb_problem_gate(a);
+        float* part = p.splits > 1 ? (float*)a.scratch : nullptr;
+        g.p[j] = Xb2Problem{a.x, a.m, a.ldx, a.b, a.y, a.ldy, a.bias, a.residual, a.ldr, part, gate, a.k, a.n,
+                            (int)xb_brs(a), (int)a.b_col_stride, a.act, p.csplit, p.staged, a.slope, p.grid.x, p.grid.y};
+        gf.add(p.grid.x * p.grid.y * p.grid.z);
+        if (p.splits > 1) {
+            const unsigned nb = (unsigned)ws_grid(a.m * (a.n / 4), 256);
+            e.p[ef.n] = SplitkProblem{part, a.m, a.y, a.ldy, a.bias, a.residual, a.ldr, gate, p.splits, a.n, a.act, a.slope, nb};
+            ef.add(nb);
+            last_e = ids[j];
+        }
+    }
+    const XbPlan& p0 = plan[ids[0]];        // (the bucket's instantiation: xb2_pair)
+    bool pruned = false;
+    const bool called = dispatch([&](auto nt, auto wn) {
+        if constexpr (xb2_pair(nt.value, wn.value) >= 0) gemm_xb2_group_kernel<nt.value, wn.value><<<gf.total, 256, 0, st>>>(g);
+        else pruned = true;
+    }, Pick<1, 2, 4>{p0.nt}, Pick<1, 2>{p0.wn});
+    if (!called || pruned) return xb2_no_instantiation(p0);
+    WS_LAUNCH_CHECK();
+    if (ef.n == 1) {
+        launch_splitk_epilogue(q[last_e], plan[last_e], xb_problem_gate(q[last_e]), st);
+        WS_HIP(hipGetLastError());      // (a single split epilogue counts with its product, as in xb_launch: ws_common.h)
+    } else if (ef.n > 1) {
+        splitk_epilogue_group_kernel<<<ef.total, 256, 0, st>>>(e);
+        WS_LAUNCH_CHECK();
+    }
+    return WS_OK;
+}
+
+// ---- gemm_xty -----------------------------------------------------------------------------------------------------------------
+// bf16 rows (ws_gemm_xty_bf16) travel in the same record, x and y pointing at 2-byte elements: the row type is the `bf16` beside it
+int xty_validate(const ws_xty_problem& q, int member)
+{
+    PRODUCT_REQUIRE(member, q.m >= 0 && q.k >= 1 && q.n >= 1 && q.ldx >= q.k && q.ldy >= q.n, "bad sizes m=%lld k=%d n=%d", (long long)q.m, q.k, q.n);
+    PRODUCT_REQUIRE(member, q.out, "NULL argument");
+    PRODUCT_REQUIRE(member, q.ldo == 0 || q.ldo >= q.n, "output pitch smaller than a row");
+    PRODUCT_REQUIRE(member, q.m == 0 || (q.x && q.y && q.scratch), "NULL argument");
+    return WS_OK;
+}
+
+// The launches of a dW reduction: every selection rule of the xty entries, shared with the reporter ws_gemm_xty_variant
+// (which only reads the pointers' alignment).  bf16: 2-byte operands (no gemm_xty_kernel fallback).
+struct XtyPlan {
+    int bf16;
+    int lds;                // 0: gemm_xty2_kernel<kt, nt, wk, wn>; 1: gemm_xty_kernel<nt, kt> (32-bit buffer offsets overflow)
+    int kt, nt, wk, wn;
+    int vecx, vecy;         // gemm_xty_kernel: float4 loads
+    int64_t chunk;
+    int chunks;
+    float* partial;         // out itself (one chunk, flat) or the scratch
+    int reduce;             // 0: none, 1: reduce_partials_kernel, 2: reduce_partials_wide_kernel
+    bool pitched;           // ldo > n: `out` is a column block of a wider matrix (row pitch ldo): the chunk sums go through the scratch
+    dim3 grid;              //   and the reduction writes the pitched rows (also for one chunk, where it is the copy a caller would make)
+};
+
+int xty_plan(const ws_xty_problem& q, bool bf16, XtyPlan& p)
+{
+    p = XtyPlan{};
+    p.bf16 = bf16;
+    p.pitched = q.ldo > q.n;
+    if (q.m == 0) return WS_OK;
+    const int k = q.k, n = q.n;
+    p.chunk = xty_chunk(q.m, k, n);
+    p.chunks = (int)ws_ceil_div(q.m, p.chunk);
+    const int64_t span = p.chunk * (q.ldx > q.ldy ? q.ldx : q.ldy);
+    if (bf16) WS_REQUIRE(span * 2 < (1ll << 31), "operand exceeds the 32-bit buffer offsets");
+    p.partial = (p.chunks == 1 && !p.pitched) ? q.out : (float*)q.scratch;
+    p.lds = !bf16 && span * 4 >= (1ll << 31);
+    if (!p.lds) {
+        // per-wave tile (32 KT) x (32 NT); waves WK x WN over the output, the rest split the rows
+        const bool a2x = bf16 ? (reinterpret_cast<uintptr_t>(q.x) & 3u) == 0 && q.ldx % 2 == 0 && k % 2 == 0
+                              : (reinterpret_cast<uintptr_t>(q.x) & 7u) == 0 && q.ldx % 2 == 0;
+        const bool a2y = bf16 ? (reinterpret_cast<uintptr_t>(q.y) & 3u) == 0 && q.ldy % 2 == 0 && n % 2 == 0
+                              : (reinterpret_cast<uintptr_t>(q.y) & 7u) == 0 && q.ldy % 2 == 0;
+        p.kt = (k > 32 && a2x) ? 2 : 1;
+        p.nt = (n > 32 && a2y) ? 2 : 1;
+        p.wk = k > 32 * p.kt ? 2 : 1;
+        p.wn = (n > 32 * p.nt && p.wk == 1) || (n > 32 * p.nt && k > 32 * p.kt) ? 2 : 1;
+        p.grid = dim3(p.chunks, (unsigned)ws_ceil_div(k, 32 * p.kt * p.wk), (unsigned)ws_ceil_div(n, 32 * p.nt * p.wn));
+    } else {
+        p.vecx = al16(q.x) && (q.ldx % 4 == 0);
+        p.vecy = al16(q.y) && (q.ldy % 4 == 0);
+        p.kt = k <= 32 ? 1 : (k <= 64 ? 2 : 4);
+        p.nt = n <= 32 ? 1 : (n <= 64 ? 2 : 4);
+        p.grid = dim3(p.chunks, (unsigned)ws_ceil_div(k, 32 * p.kt), (unsigned)ws_ceil_div(n, 32 * p.nt));
+    }
+    if (p.chunks > 1 || p.pitched)
+        p.reduce = reduce_partials_wide(p.partial, (int64_t)k * n, p.chunks, q.out, n, p.pitched ? q.ldo : 0) ? 2 : 1;
+    return WS_OK;
+}
+
+int xty2_no_instantiation(const XtyPlan& p)
+{
+    return ws_no_instantiation("gemm_xty2_kernel<KT=%d, NT=%d, WK=%d, WN=%d> bf16=%d", p.kt, p.nt, p.wk, p.wn, p.bf16);
+}
+
+// gemm_xty2_kernel: a product alone (f32 or bf16 rows), and a grouped member nobody shares an instantiation with
+int launch_xty2(const ws_xty_problem& q, const XtyPlan& p, hipStream_t st)
+{
+    const bool called = dispatch([&](auto bf, auto kt, auto nt, auto wk, auto wn) {
+        using T = Row<bf.value>;
+        gemm_xty2_kernel<kt.value, nt.value, wk.value, wn.value, T><<<p.grid, 256, 0, st>>>((const T*)q.x, q.m, q.k, q.ldx, (const T*)q.y, q.n,
+                                                                                           q.ldy, p.partial, p.chunk);
+    }, Flag{p.bf16}, Pick<1, 2>{p.kt}, Pick<1, 2>{p.nt}, Pick<1, 2>{p.wk}, Pick<1, 2>{p.wn});
+    return called ? WS_OK : xty2_no_instantiation(p);
+}
+
+int launch_xty_lds(const ws_xty_problem& q, const XtyPlan& p, hipStream_t st)
+{
+    const bool called = dispatch([&](auto nt, auto kt) {
+        gemm_xty_kernel<nt.value, kt.value><<<p.grid, 256, 0, st>>>(q.x, q.m, q.k, q.ldx, q.y, q.n, q.ldy, p.partial, p.chunk, p.vecx, p.vecy);
+    }, Pick<1, 2, 4>{p.nt}, Pick<1, 2, 4>{p.kt});
+    return called ? WS_OK : ws_no_instantiation("gemm_xty_kernel<NT=%d, KT=%d>", p.nt, p.kt);
+}
+
+// the product launch of plan p: counted
+int xty_product_launch(const ws_xty_problem& q, const XtyPlan& p, hipStream_t st)
+{
+    const int rc = p.lds ? launch_xty_lds(q, p, st) : launch_xty2(q, p, st);
+    if (rc != WS_OK) return rc;
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+// the chunk sums of plan p (p.reduce != 0): counted
+int xty_reduce_launch(const ws_xty_problem& q, const XtyPlan& p, hipStream_t st)
+{
+    launch_reduce_partials(p.partial, (int64_t)q.k * q.n, p.chunks, q.out, st, q.n, p.pitched ? q.ldo : 0);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+int xty_run(const ws_xty_problem& q, bool bf16, void* stream)
+{
+    int rc = xty_validate(q, -1);
+    if (rc != WS_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (q.m == 0) {
+        if (q.ldo > q.n) WS_HIP(hipMemset2DAsync(q.out, sizeof(float) * (size_t)q.ldo, 0, sizeof(float) * (size_t)q.n, (size_t)q.k, st));
+        else WS_HIP(hipMemsetAsync(q.out, 0, sizeof(float) * (size_t)q.k * q.n, st));
+        return WS_OK;
+    }
+    XtyPlan p;
+    rc = xty_plan(q, bf16, p);
+    if (rc == WS_OK) rc = xty_product_launch(q, p, st);
+    if (rc == WS_OK && p.reduce) rc = xty_reduce_launch(q, p, st);
+    return rc;
+}
+
+int launch_xty2_group(const ws_xty_problem* q, const XtyPlan* plan, const int* ids, int cnt, hipStream_t st)
+{
+    Xty2Group g{};
+    GroupFill gf{g.gi};
+    for (int j = 0; j < cnt; ++j) {
+        const ws_xty_problem& a = q[ids[j]];
+        const XtyPlan& p = plan[ids[j]];
+        g.p[j] = Xty2Problem{a.x, a.m, a.ldx, a.y, a.ldy, p.partial, p.chunk, a.k, a.n, p.grid.x, p.grid.y};
+        gf.add(p.grid.x * p.grid.y * p.grid.z);
+    }
+    const XtyPlan& p0 = plan[ids[0]];
+    const bool called = dispatch([&](auto kt, auto nt, auto wk, auto wn) {
+        gemm_xty2_group_kernel<kt.value, nt.value, wk.value, wn.value><<<gf.total, 256, 0, st>>>(g);
+    }, Pick<1, 2>{p0.kt}, Pick<1, 2>{p0.nt}, Pick<1, 2>{p0.wk}, Pick<1, 2>{p0.wn});
+    if (!called) return xty2_no_instantiation(p0);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+int launch_reduce_group(const ws_xty_problem* q, const XtyPlan* plan, const int* ids, int cnt, hipStream_t st)
+{
+    ReduceGroup g{};
+    GroupFill gf{g.gi};
+    for (int j = 0; j < cnt; ++j) {
+        const ws_xty_problem& a = q[ids[j]];
+        const XtyPlan& p = plan[ids[j]];
+        const int64_t elems = (int64_t)a.k * a.n;
+        g.p[j] = ReduceProblem{p.partial, elems, a.out, p.pitched ? a.ldo : 0, p.chunks, a.n, p.reduce == 2 ? 1 : 0};
+        gf.add((unsigned)ws_ceil_div(elems, p.reduce == 2 ? 1024 : 32));
+    }
+    reduce_partials_group_kernel<<<gf.total, 256, 0, st>>>(g);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+const char* reduce_name(int r)
+{
+    return r == 2 ? "reduce_partials_wide_kernel" : (r == 1 ? "reduce_partials_kernel" : "none");
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ws_gemm_xb_scratch_bytes(int64_t m, int32_t k, int32_t n)
+{
+    // room for up to 16 split-K partial outputs; only short, deep products use it
+    if (m <= 0 || m >= 32768 || k < 512) return 0;
+    return 16 * m * (int64_t)n * (int64_t)sizeof(float);
+}
+
+int ws_gemm_xb(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n, float* y, int64_t ldy,
+               void* stream)
+{
+    return xb_run(xb_problem(x, m, k, ldx, b, n, y, ldy), stream);
+}
+
+int ws_gemm_xb_epilogue(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n,
+                        const float* bias, const float* residual, int64_t ldr, int32_t act, float slope,
+                        float* y, int64_t ldy, void* stream)
+{
+    ws_xb_problem q = xb_problem(x, m, k, ldx, b, n, y, ldy);
+    xb_epilogue(q, bias, residual, ldr, act, slope);
+    return xb_run(q, stream);
+}
+
+int ws_gemm_xb_epilogue_splitk(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n,
+                               const float* bias, const float* residual, int64_t ldr, int32_t act, float slope,
+                               float* y, int64_t ldy, void* scratch, int64_t scratch_bytes, void* stream)
+{
+    ws_xb_problem q = xb_problem(x, m, k, ldx, b, n, y, ldy, scratch, scratch_bytes);
+    xb_epilogue(q, bias, residual, ldr, act, slope);
+    return xb_run(q, stream);
+}
+
+int ws_gemm_xb_epilogue_strided(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int64_t b_row_stride,
+                                int64_t b_col_stride, int32_t n, const float* bias, const float* residual, int64_t ldr,
+                                int32_t act, float slope, float* y, int64_t ldy, void* scratch, int64_t scratch_bytes,
+                                void* stream)
+{
+    ws_xb_problem q = xb_problem(x, m, k, ldx, b, n, y, ldy, scratch, scratch_bytes);
+    xb_strides(q, b_row_stride, b_col_stride);
+    xb_epilogue(q, bias, residual, ldr, act, slope);
+    return xb_run(q, stream);
+}
+
+int ws_gemm_xb_gated_strided(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int64_t b_row_stride,
+                             int64_t b_col_stride, int32_t n, const float* bias, const float* residual, int64_t ldr,
+                             int32_t act, float slope, const float* gate_y, int64_t ldg, float gate_slope, const uint8_t* mask,
+                             int64_t ldm, float mask_scale, float* y, int64_t ldy, void* scratch, int64_t scratch_bytes,
+                             void* stream)
+{
+    ws_xb_problem q = xb_problem(x, m, k, ldx, b, n, y, ldy, scratch, scratch_bytes);
+    xb_strides(q, b_row_stride, b_col_stride);
+    xb_epilogue(q, bias, residual, ldr, act, slope);
+    q.gate_y = gate_y; q.ldg = ldg; q.gate_slope = gate_slope;
+    q.mask = mask; q.ldm = ldm; q.mask_scale = mask_scale;
+    return xb_run(q, stream);
+}
+
+int ws_gemm_xb_dropout_strided(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int64_t b_row_stride,
+                               int64_t b_col_stride, int32_t n, const float* bias, const float* residual, int64_t ldr,
+                               int32_t act, float slope, float drop_p, uint64_t drop_seed, float* y, int64_t ldy, void* scratch,
+                               int64_t scratch_bytes, void* stream)
+{
+    ws_xb_problem q = xb_problem(x, m, k, ldx, b, n, y, ldy, scratch, scratch_bytes);
+    xb_strides(q, b_row_stride, b_col_stride);
+    xb_epilogue(q, bias, residual, ldr, act, slope);
+    q.drop_p = drop_p; q.drop_seed = drop_seed;
+    return xb_run(q, stream);
+}
+
+int ws_gemm_xb_gate_dropout(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n, const float* gate_y,
+                            int64_t ldg, float gate_slope, float drop_p, uint64_t drop_seed, float* y, int64_t ldy, void* scratch,
+                            int64_t scratch_bytes, void* stream)
+{
+    ws_xb_problem q = xb_problem(x, m, k, ldx, b, n, y, ldy, scratch, scratch_bytes);
+    q.gate_y = gate_y; q.ldg = ldg; q.gate_slope = gate_slope;
+    q.drop_p = drop_p; q.drop_seed = drop_seed;
+    return xb_run(q, stream);
+}
+
+// private to the library (ws_common.h): the strided product with the whole epilogue menu -- dropout (drop_p > 0) and / or a
+// gathered residual (res_rows != NULL: row r adds residual[res_rows[r * res_rows_ld]], indices outside [0, res_nrows) add nothing)
+int ws_priv_gemm_xb_ex(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int64_t b_row_stride, int64_t b_col_stride,
+                       int32_t n, const float* bias, const float* residual, int64_t ldr, const int64_t* res_rows, int64_t res_rows_ld,
+                       int64_t res_nrows, int32_t act, float slope, float drop_p, uint64_t drop_seed, float* y, int64_t ldy,
+                       void* scratch, int64_t scratch_bytes, void* stream)
+{
+    ws_xb_problem q = xb_problem(x, m, k, ldx, b, n, y, ldy, scratch, scratch_bytes);
+    xb_strides(q, b_row_stride, b_col_stride);
+    xb_epilogue(q, bias, residual, ldr, act, slope);
+    q.res_rows = res_rows; q.res_rows_ld = res_rows_ld; q.res_nrows = res_nrows;
+    q.drop_p = drop_p; q.drop_seed = drop_seed;
+    return xb_run(q, stream);
+}
+
+// private to the library (ws_common.h).  Members whose plan is not gemm_xb2 (the shallow and generic forms) run alone, as do
+// members alone in their instantiation; m == 0 does what the single entry does (nothing); more than GROUP_MAX members of one
+// instantiation spill into a second launch.
+int ws_priv_gemm_xb_group(const ws_xb_problem* q, int32_t count, void* stream)
+{
+    WS_REQUIRE(count >= 0 && (q || count == 0), "bad group");
+    for (; count > GROUP_CALL_MAX; q += GROUP_CALL_MAX, count -= GROUP_CALL_MAX) {
+        const int rc = ws_priv_gemm_xb_group(q, GROUP_CALL_MAX, stream);
+        if (rc != WS_OK) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    XbPlan plan[GROUP_CALL_MAX];
+    IdList bucket[XB2_NPAIRS];
+    for (int i = 0; i < count; ++i) {
+        int rc = xb_validate(q[i], i);
+        if (rc != WS_OK) return rc;
+        if (q[i].m == 0) continue;
+        const XbPlan& p = plan[i];
+        rc = xb_plan(q[i], plan[i]);
+        if (rc != WS_OK) return rc;
+        if (p.kind != XB_XB2 || (int64_t)p.grid.x * p.grid.y * p.grid.z >= GROUP_MEMBER_BLOCKS) {
+            rc = xb_launch(q[i], p, st);
+            if (rc != WS_OK) return rc;
+            continue;
+        }
+        if (xb2_pair(p.nt, p.wn) < 0) return xb2_no_instantiation(p);
+        bucket[xb2_pair(p.nt, p.wn)].push_back(i);
+    }
+    for (const IdList& ids : bucket) {
+        const int rc = for_each_launch(ids, [&](const int* id, int cnt) {
+            return cnt == 1 ? xb_launch(q[id[0]], plan[id[0]], st) : launch_xb2_group(q, plan, id, cnt, st);
+        });
+        if (rc != WS_OK) return rc;
+    }
     return WS_OK;
 }
 
@@ -1354,7 +1807,29 @@ static ColsumPlan colsum_plan(const void* dy, int64_t m, int32_t n, int64_t lddy
 }
 
 static int act_bwd_colsum_impl(const float* dy, int64_t m, int32_t n, int64_t lddy, const float* y, int64_t ldy, float slope,
-                               float* dz, int64_t lddz, float* colsum, void* scratch, void* stream, WsDrop drop);
+                               float* dz, int64_t lddz, float* colsum, void* scratch, void* stream, WsDrop drop)
+{
+    WS_REQUIRE(m >= 0 && n >= 1 && lddy >= n, "bad sizes m=%lld n=%d", (long long)m, n);
+    WS_REQUIRE(!y || (dz && ldy >= n && lddz >= n), "activation backward needs y and dz");
+    WS_REQUIRE(!colsum || scratch, "column sums need scratch");
+    hipStream_t st = (hipStream_t)stream;
+    if (m == 0) {
+        if (colsum) WS_HIP(hipMemsetAsync(colsum, 0, sizeof(float) * (size_t)n, st));
+        return WS_OK;
+    }
+    WS_REQUIRE(dy && (y || colsum), "NULL argument");
+    const ColsumPlan p = colsum_plan(dy, m, n, lddy, y, ldy, dz, lddz, colsum, scratch);
+    const bool called = dispatch([&](auto v) {
+        act_bwd_colsum_kernel<v.value><<<p.grid, 256, 0, st>>>(dy, y, m, n, lddy, ldy, slope, dz, lddz, p.partial, p.chunk, drop);
+    }, Pick<1, 4>{p.v});
+    if (!called) return ws_no_instantiation("act_bwd_colsum_kernel<V=%d>", p.v);
+    WS_LAUNCH_CHECK();
+    if (p.reduce) {
+        reduce_partials_kernel<<<(unsigned)ws_ceil_div(n, 32), 256, 0, st>>>(p.partial, n, p.chunks, colsum);
+        WS_LAUNCH_CHECK();
+    }
+    return WS_OK;
+}
 
 int ws_act_bwd_colsum(const float* dy, int64_t m, int32_t n, int64_t lddy, const float* y, int64_t ldy, float slope,
                       float* dz, int64_t lddz, float* colsum, void* scratch, void* stream)
@@ -1370,240 +1845,6 @@ int ws_act_bwd_colsum_dropout(const float* dy, int64_t m, int32_t n, int64_t ldd
     return act_bwd_colsum_impl(dy, m, n, lddy, y, ldy, slope, dz, lddz, colsum, scratch, stream, ws_drop_args(drop_p, drop_seed));
 }
 
-static int act_bwd_colsum_impl(const float* dy, int64_t m, int32_t n, int64_t lddy, const float* y, int64_t ldy, float slope,
-                               float* dz, int64_t lddz, float* colsum, void* scratch, void* stream, WsDrop drop)
-{
-    WS_REQUIRE(m >= 0 && n >= 1 && lddy >= n, "bad sizes m=%lld n=%d", (long long)m, n);
-    WS_REQUIRE(!y || (dz && ldy >= n && lddz >= n), "activation backward needs y and dz");
-    WS_REQUIRE(!colsum || scratch, "column sums need scratch");
-    hipStream_t st = (hipStream_t)stream;
-    if (m == 0) {
-        if (colsum) WS_HIP(hipMemsetAsync(colsum, 0, sizeof(float) * (size_t)n, st));
-        return WS_OK;
-    }
-    WS_REQUIRE(dy && (y || colsum), "NULL argument");
-    const ColsumPlan p = colsum_plan(dy, m, n, lddy, y, ldy, dz, lddz, colsum, scratch);
-    if (p.v == 4)
-        act_bwd_colsum_kernel<4><<<p.grid, 256, 0, st>>>(dy, y, m, n, lddy, ldy, slope, dz, lddz, p.partial, p.chunk, drop);
-    else
-        act_bwd_colsum_kernel<1><<<p.grid, 256, 0, st>>>(dy, y, m, n, lddy, ldy, slope, dz, lddz, p.partial, p.chunk, drop);
-    WS_LAUNCH_CHECK();
-    if (p.reduce) {
-        reduce_partials_kernel<<<(unsigned)ws_ceil_div(n, 32), 256, 0, st>>>(p.partial, n, p.chunks, colsum);
-        WS_LAUNCH_CHECK();
-    }
-    return WS_OK;
-}
-
-int ws_gemm_xb_epilogue(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n,
-                        const float* bias, const float* residual, int64_t ldr, int32_t act, float slope,
-                        float* y, int64_t ldy, void* stream)
-{
-    return gemm_xb_impl(x, m, k, ldx, b, n, bias, residual, ldr, act, slope, y, ldy, nullptr, 0, stream);
-}
-
-int ws_gemm_xb_epilogue_splitk(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n,
-                               const float* bias, const float* residual, int64_t ldr, int32_t act, float slope,
-                               float* y, int64_t ldy, void* scratch, int64_t scratch_bytes, void* stream)
-{
-    return gemm_xb_impl(x, m, k, ldx, b, n, bias, residual, ldr, act, slope, y, ldy, scratch, scratch_bytes, stream);
-}
-
-int ws_gemm_xb_epilogue_strided(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int64_t b_row_stride,
-                                int64_t b_col_stride, int32_t n, const float* bias, const float* residual, int64_t ldr,
-                                int32_t act, float slope, float* y, int64_t ldy, void* scratch, int64_t scratch_bytes,
-                                void* stream)
-{
-    return gemm_xb_impl(x, m, k, ldx, b, n, bias, residual, ldr, act, slope, y, ldy, scratch, scratch_bytes, stream,
-                        b_row_stride, b_col_stride);
-}
-
-int ws_gemm_xb_gated_strided(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int64_t b_row_stride,
-                             int64_t b_col_stride, int32_t n, const float* bias, const float* residual, int64_t ldr,
-                             int32_t act, float slope, const float* gate_y, int64_t ldg, float gate_slope, const uint8_t* mask,
-                             int64_t ldm, float mask_scale, float* y, int64_t ldy, void* scratch, int64_t scratch_bytes,
-                             void* stream)
-{
-    WS_REQUIRE(!gate_y || ldg >= n, "gate leading dimension too small");
-    WS_REQUIRE(!mask || ldm >= n, "mask leading dimension too small");
-    return gemm_xb_impl(x, m, k, ldx, b, n, bias, residual, ldr, act, slope, y, ldy, scratch, scratch_bytes, stream,
-                        b_row_stride, b_col_stride, XbGate{gate_y, ldg, gate_slope, mask, ldm, mask_scale, WsDrop{}, 0, nullptr, 0, 0});
-}
-
-int ws_gemm_xb_dropout_strided(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int64_t b_row_stride,
-                               int64_t b_col_stride, int32_t n, const float* bias, const float* residual, int64_t ldr,
-                               int32_t act, float slope, float drop_p, uint64_t drop_seed, float* y, int64_t ldy, void* scratch,
-                               int64_t scratch_bytes, void* stream)
-{
-    WS_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f, "bad drop probability %g", (double)drop_p);
-    XbGate gate{};
-    gate.drop = ws_drop_args(drop_p, drop_seed);
-    gate.dn = n;
-    return gemm_xb_impl(x, m, k, ldx, b, n, bias, residual, ldr, act, slope, y, ldy, scratch, scratch_bytes, stream,
-                        b_row_stride, b_col_stride, gate);
-}
-
-int ws_gemm_xb_gate_dropout(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n, const float* gate_y,
-                            int64_t ldg, float gate_slope, float drop_p, uint64_t drop_seed, float* y, int64_t ldy, void* scratch,
-                            int64_t scratch_bytes, void* stream)
-{
-    WS_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f, "bad drop probability %g", (double)drop_p);
-    WS_REQUIRE(!gate_y || ldg >= n, "gate leading dimension too small");
-    XbGate gate{};
-    gate.y = gate_y; gate.ld = ldg; gate.slope = gate_slope;
-    gate.drop = ws_drop_args(drop_p, drop_seed);
-    gate.dn = n;
-    return gemm_xb_impl(x, m, k, ldx, b, n, nullptr, nullptr, 0, 0, 0.0f, y, ldy, scratch, scratch_bytes, stream, -1, 1, gate);
-}
-
-// private to the library (ws_common.h): the strided product with the whole epilogue menu -- dropout (drop_p > 0) and / or a
-// gathered residual (res_rows != NULL: row r adds residual[res_rows[r * res_rows_ld]], indices outside [0, res_nrows) add nothing)
-int ws_priv_gemm_xb_ex(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int64_t b_row_stride, int64_t b_col_stride,
-                       int32_t n, const float* bias, const float* residual, int64_t ldr, const int64_t* res_rows, int64_t res_rows_ld,
-                       int64_t res_nrows, int32_t act, float slope, float drop_p, uint64_t drop_seed, float* y, int64_t ldy,
-                       void* scratch, int64_t scratch_bytes, void* stream)
-{
-    WS_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f, "bad drop probability %g", (double)drop_p);
-    WS_REQUIRE(!res_rows || (residual && res_rows_ld >= 1 && res_nrows >= 0), "gathered residual: NULL residual / bad sizes");
-    XbGate gate{};
-    gate.drop = ws_drop_args(drop_p, drop_seed);
-    gate.dn = n;
-    gate.rrows = res_rows; gate.rld = res_rows_ld; gate.rn = res_nrows;
-    return gemm_xb_impl(x, m, k, ldx, b, n, bias, residual, ldr, act, slope, y, ldy, scratch, scratch_bytes, stream,
-                        b_row_stride, b_col_stride, gate);
-}
-
-// ---- grouped products (ws_common.h) ------------------------------------------------------------------------------------------
-// Each member keeps exactly the plan it gets alone from xb_plan / xty_plan -- kind, tile variant, splits, csplit, chunk,
-// chunks, reduction form, pitched output -- and its workgroups run the single kernels' bodies on that plan, so every sum
-// is added in the order of the single launch: a grouped result is bit-identical to the single one.  Only the number of
-// launches changes.
-static XbGate xb_problem_gate(const ws_xb_problem& q)
-{
-    XbGate g{};
-    g.y = q.gate_y; g.ld = q.ldg; g.slope = q.gate_slope;
-    g.mask = q.mask; g.ldm = q.ldm; g.mscale = q.mask_scale;
-    g.drop = ws_drop_args(q.drop_p, q.drop_seed);
-    g.dn = q.n;
-    g.rrows = q.res_rows; g.rld = q.res_rows_ld; g.rn = q.res_nrows;
-    return g;
-}
-static int xb_problem_alone(const ws_xb_problem& q, void* stream)
-{
-    return gemm_xb_impl(q.x, q.m, q.k, q.ldx, q.b, q.n, q.bias, q.residual, q.ldr, q.act, q.slope, q.y, q.ldy, q.scratch, q.scratch_bytes,
-                        stream, q.b_row_stride, q.b_col_stride, xb_problem_gate(q));
-}
-// one call plans at most GROUP_CALL_MAX members on the stack (no allocation on the launch path: the block calls pass 2 .. 4);
-// a longer list is handled as consecutive slices of that many, each grouped within itself
-constexpr int GROUP_CALL_MAX = 16;
-struct IdList {
-    int n = 0;
-    int v[GROUP_CALL_MAX];
-    void push_back(int i) { v[n++] = i; }
-    int size() const { return n; }
-    const int* data() const { return v; }
-    int operator[](int i) const { return v[i]; }
-};
-constexpr int64_t GROUP_MEMBER_BLOCKS = 1ll << 27;      // a member with more workgroups runs alone (the linear index stays 32-bit)
-
-static int xb2_group_launch(const ws_xb_problem* q, const XbPlan* plan, const int* ids, int cnt, hipStream_t st)
-{
-    Xb2Group g{};
-    SplitkGroup e{};
-    int ne = 0, last_e = -1;
-    unsigned total = 0, etotal = 0;
-    for (int j = 0; j < cnt; ++j) {
-        const ws_xb_problem& a = q[ids[j]];
-        const XbPlan& p = plan[ids[j]];
-        const XbGate gate = xb_problem_gate(a);
-        float* part = p.splits > 1 ? (float*)a.scratch : nullptr;
-        g.p[j] = Xb2Problem{a.x, a.m, a.ldx, a.b, a.y, a.ldy, a.bias, a.residual, a.ldr, part, gate, a.k, a.n,
-                            (int)(a.b_row_stride < 0 ? a.n : a.b_row_stride), (int)a.b_col_stride, a.act, p.csplit, p.staged, a.slope,
-                            p.grid.x, p.grid.y};
-        total += p.grid.x * p.grid.y * p.grid.z;
-        g.gi.end[j] = total;
-        if (p.splits > 1) {
-            const unsigned nb = (unsigned)ws_grid(a.m * (a.n / 4), 256);
-            e.p[ne] = SplitkProblem{part, a.m, a.y, a.ldy, a.bias, a.residual, a.ldr, gate, p.splits, a.n, a.act, a.slope, nb};
-            etotal += nb;
-            e.gi.end[ne++] = etotal;
-            last_e = ids[j];
-        }
-    }
-    for (int j = cnt; j < GROUP_MAX; ++j) g.gi.end[j] = total;
-    for (int j = ne; j < GROUP_MAX; ++j) e.gi.end[j] = etotal;
-    const XbPlan& p0 = plan[ids[0]];
-    if (p0.wn == 1) {
-        if (p0.nt == 1) gemm_xb2_group_kernel<1, 1><<<total, 256, 0, st>>>(g);
-        else if (p0.nt == 2) gemm_xb2_group_kernel<2, 1><<<total, 256, 0, st>>>(g);
-        else gemm_xb2_group_kernel<4, 1><<<total, 256, 0, st>>>(g);
-    } else {
-        if (p0.nt == 1) gemm_xb2_group_kernel<1, 2><<<total, 256, 0, st>>>(g);
-        else gemm_xb2_group_kernel<2, 2><<<total, 256, 0, st>>>(g);
-    }
-    WS_LAUNCH_CHECK();
-    if (ne == 1) {
-        const SplitkProblem& s1 = e.p[0];
-        splitk_epilogue_kernel<<<s1.nb, 256, 0, st>>>(s1.partial, s1.splits, s1.m, s1.n, s1.y, s1.ldy, s1.bias, s1.residual, s1.ldr, s1.act,
-                                                      s1.slope, xb_problem_gate(q[last_e]));
-        WS_HIP(hipGetLastError());      // (a single split epilogue counts with its product, as in gemm_xb_impl: ws_common.h)
-    } else if (ne > 1) {
-        splitk_epilogue_group_kernel<<<etotal, 256, 0, st>>>(e);
-        WS_LAUNCH_CHECK();
-    }
-    return WS_OK;
-}
-
-// private to the library (ws_common.h).  Members whose plan is not gemm_xb2 (the shallow and generic forms) run alone, as do
-// members alone in their instantiation; m == 0 does what the single entry does (nothing); more than GROUP_MAX members of one
-// instantiation spill into a second launch.
-int ws_priv_gemm_xb_group(const ws_xb_problem* q, int32_t count, void* stream)
-{
-    WS_REQUIRE(count >= 0 && (q || count == 0), "bad group");
-    for (; count > GROUP_CALL_MAX; q += GROUP_CALL_MAX, count -= GROUP_CALL_MAX) {
-        const int rc = ws_priv_gemm_xb_group(q, GROUP_CALL_MAX, stream);
-        if (rc != WS_OK) return rc;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    XbPlan plan[GROUP_CALL_MAX];
-    IdList bucket[5];
-    for (int i = 0; i < count; ++i) {
-        const ws_xb_problem& a = q[i];
-        WS_REQUIRE(a.m >= 0 && a.k >= 1 && a.n >= 1 && a.ldx >= a.k && a.ldy >= a.n, "member %d: bad sizes m=%lld k=%d n=%d", i, (long long)a.m, a.k, a.n);
-        WS_REQUIRE(!a.residual || a.ldr >= a.n, "member %d: residual leading dimension too small", i);
-        WS_REQUIRE(a.act == 0 || a.act == 1, "member %d: unknown activation %d", i, a.act);
-        WS_REQUIRE(a.drop_p >= 0.0f && a.drop_p < 1.0f, "member %d: bad drop probability %g", i, (double)a.drop_p);
-        WS_REQUIRE(!a.res_rows || (a.residual && a.res_rows_ld >= 1 && a.res_nrows >= 0), "member %d: gathered residual: NULL residual / bad sizes", i);
-        WS_REQUIRE(!a.gate_y || a.ldg >= a.n, "member %d: gate leading dimension too small", i);
-        WS_REQUIRE(!a.mask || a.ldm >= a.n, "member %d: mask leading dimension too small", i);
-        if (a.m == 0) continue;
-        WS_REQUIRE(a.x && a.b && a.y, "member %d: NULL argument", i);
-        const int rc = xb_plan(a.x, a.m, a.k, a.ldx, a.b, a.n, a.bias, a.residual, a.ldr, a.y, a.ldy, a.scratch, a.scratch_bytes,
-                               a.b_row_stride < 0 ? a.n : a.b_row_stride, a.b_col_stride, xb_problem_gate(a), plan[i]);
-        if (rc != WS_OK) return rc;
-        const XbPlan& p = plan[i];
-        if (p.kind != XB_XB2 || (int64_t)p.grid.x * p.grid.y * p.grid.z >= GROUP_MEMBER_BLOCKS) {
-            const int r1 = xb_problem_alone(a, stream);
-            if (r1 != WS_OK) return r1;
-            continue;
-        }
-        bucket[p.wn == 1 ? (p.nt == 1 ? 0 : p.nt == 2 ? 1 : 2) : (p.nt == 1 ? 3 : 4)].push_back(i);
-    }
-    for (const IdList& ids : bucket)
-        for (int off = 0; off < ids.size(); off += GROUP_MAX) {
-            const int cnt = ids.size() - off < GROUP_MAX ? ids.size() - off : GROUP_MAX;
-            const int rc = cnt == 1 ? xb_problem_alone(q[ids[off]], stream) : xb2_group_launch(q, plan, ids.data() + off, cnt, st);
-            if (rc != WS_OK) return rc;
-        }
-    return WS_OK;
-}
-
-int ws_gemm_xb(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int32_t n, float* y, int64_t ldy,
-               void* stream)
-{
-    return gemm_xb_impl(x, m, k, ldx, b, n, nullptr, nullptr, 0, 0, 0.0f, y, ldy, nullptr, 0, stream);
-}
-
 int64_t ws_gemm_xty_scratch_bytes(int64_t m, int32_t k, int32_t n)
 {
     // (xty_chunk(0, ..) is 0: size an empty operand as one row, like ws_act_bwd_colsum_scratch_bytes)
@@ -1611,167 +1852,26 @@ int64_t ws_gemm_xty_scratch_bytes(int64_t m, int32_t k, int32_t n)
     return ws_ceil_div(rows, xty_chunk(rows, k, n)) * (int64_t)k * n * (int64_t)sizeof(float);
 }
 
-static int gemm_xty_core(const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy,
-                         float* out, void* scratch, void* stream, int64_t ldo = 0);
-
 int ws_gemm_xty(const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy,
                 float* out, void* scratch, void* stream)
 {
-    return gemm_xty_core(x, m, k, ldx, y, n, ldy, out, scratch, stream);
+    return xty_run(ws_xty_problem{x, m, k, ldx, y, n, ldy, out, 0, scratch, 0}, false, stream);
 }
 
-// The launches of a dW reduction: every selection rule of gemm_xty_core / ws_gemm_xty_bf16, shared with the reporter
-// ws_gemm_xty_variant (which only reads the pointers' alignment).  bf16: 2-byte operands (no gemm_xty_kernel fallback).
-struct XtyPlan {
-    int lds;                // 0: gemm_xty2_kernel<kt, nt, wk, wn>; 1: gemm_xty_kernel<nt, kt> (32-bit buffer offsets overflow)
-    int kt, nt, wk, wn;
-    int vecx, vecy;         // gemm_xty_kernel: float4 loads
-    int64_t chunk;
-    int chunks;
-    float* partial;         // out itself (one chunk, flat) or the scratch
-    int reduce;             // 0: none, 1: reduce_partials_kernel, 2: reduce_partials_wide_kernel
-    bool pitched;
-    dim3 grid;
-};
-
-static int xty_plan(const void* x, int64_t m, int32_t k, int64_t ldx, const void* y, int32_t n, int64_t ldy, float* out, void* scratch,
-                    int64_t ldo, bool bf16, XtyPlan& p)
+// dW = X^T dY with bf16 rows (BASELINE config 5): the LDS-free reduction with 2-byte operand loads; no pitched form.
+// Requirements: k, n even or <= 32 handled by the one-column form; every shape of the bf16 path qualifies.
+int ws_gemm_xty_bf16(const uint16_t* x, int64_t m, int32_t k, int64_t ldx, const uint16_t* y, int32_t n, int64_t ldy,
+                     float* out, void* scratch, void* stream)
 {
-    p = XtyPlan{};
-    p.pitched = ldo > n;
-    if (m == 0) return WS_OK;
-    p.chunk = xty_chunk(m, k, n);
-    p.chunks = (int)ws_ceil_div(m, p.chunk);
-    const int64_t span = p.chunk * (ldx > ldy ? ldx : ldy);
-    if (bf16) WS_REQUIRE(span * 2 < (1ll << 31), "operand exceeds the 32-bit buffer offsets");
-    p.partial = (p.chunks == 1 && !p.pitched) ? out : (float*)scratch;
-    p.lds = !bf16 && span * 4 >= (1ll << 31);
-    if (!p.lds) {
-        // per-wave tile (32 KT) x (32 NT); waves WK x WN over the output, the rest split the rows
-        const bool a2x = bf16 ? (reinterpret_cast<uintptr_t>(x) & 3u) == 0 && ldx % 2 == 0 && k % 2 == 0
-                              : (reinterpret_cast<uintptr_t>(x) & 7u) == 0 && ldx % 2 == 0;
-        const bool a2y = bf16 ? (reinterpret_cast<uintptr_t>(y) & 3u) == 0 && ldy % 2 == 0 && n % 2 == 0
-                              : (reinterpret_cast<uintptr_t>(y) & 7u) == 0 && ldy % 2 == 0;
-        p.kt = (k > 32 && a2x) ? 2 : 1;
-        p.nt = (n > 32 && a2y) ? 2 : 1;
-        p.wk = k > 32 * p.kt ? 2 : 1;
-        p.wn = (n > 32 * p.nt && p.wk == 1) || (n > 32 * p.nt && k > 32 * p.kt) ? 2 : 1;
-        p.grid = dim3(p.chunks, (unsigned)ws_ceil_div(k, 32 * p.kt * p.wk), (unsigned)ws_ceil_div(n, 32 * p.nt * p.wn));
-    } else {
-        p.vecx = al16(x) && (ldx % 4 == 0);
-        p.vecy = al16(y) && (ldy % 4 == 0);
-        p.kt = k <= 32 ? 1 : (k <= 64 ? 2 : 4);
-        p.nt = n <= 32 ? 1 : (n <= 64 ? 2 : 4);
-        p.grid = dim3(p.chunks, (unsigned)ws_ceil_div(k, 32 * p.kt), (unsigned)ws_ceil_div(n, 32 * p.nt));
-    }
-    if (p.chunks > 1 || p.pitched)
-        p.reduce = reduce_partials_wide(p.partial, (int64_t)k * n, p.chunks, out, n, p.pitched ? ldo : 0) ? 2 : 1;
-    return WS_OK;
-}
-
-static void xty_product_launch(const XtyPlan& p, const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy,
-                               hipStream_t st);
-
-static int gemm_xty_core(const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy,
-                         float* out, void* scratch, void* stream, int64_t ldo)
-{
-    // ldo > n: `out` is a column block of a wider matrix (row pitch ldo): the chunk sums go through the scratch buffer and the
-    // reduction writes the pitched rows (also for a single chunk, where it is the copy a caller would otherwise make)
-    const bool pitched = ldo > n;
-    WS_REQUIRE(m >= 0 && k >= 1 && n >= 1 && ldx >= k && ldy >= n, "bad sizes m=%lld k=%d n=%d", (long long)m, k, n);
-    WS_REQUIRE(out, "NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (m == 0) {
-        if (pitched) WS_HIP(hipMemset2DAsync(out, sizeof(float) * (size_t)ldo, 0, sizeof(float) * (size_t)n, (size_t)k, st));
-        else WS_HIP(hipMemsetAsync(out, 0, sizeof(float) * (size_t)k * n, st));
-        return WS_OK;
-    }
-    WS_REQUIRE(x && y && scratch, "NULL argument");
-    XtyPlan p;
-    const int rc = xty_plan(x, m, k, ldx, y, n, ldy, out, scratch, ldo, false, p);
-    if (rc != WS_OK) return rc;
-    xty_product_launch(p, x, m, k, ldx, y, n, ldy, st);
-    WS_LAUNCH_CHECK();
-    if (p.reduce) {
-        const int64_t elems = (int64_t)k * n;
-        launch_reduce_partials(p.partial, elems, p.chunks, out, st, n, pitched ? ldo : 0);
-        WS_LAUNCH_CHECK();
-    }
-    return WS_OK;
-}
-
-// the product launch of plan p (f32 rows)
-static void xty_product_launch(const XtyPlan& p, const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy,
-                               hipStream_t st)
-{
-    if (!p.lds) {
-#define WS_XTY2(KTV, NTV, WKV, WNV) gemm_xty2_kernel<KTV, NTV, WKV, WNV><<<p.grid, 256, 0, st>>>(x, m, k, ldx, y, n, ldy, p.partial, p.chunk)
-#define WS_XTY2_W(KTV, NTV)                          \
-    do {                                             \
-        if (p.wk == 2 && p.wn == 2) WS_XTY2(KTV, NTV, 2, 2); \
-        else if (p.wk == 2) WS_XTY2(KTV, NTV, 2, 1);   \
-        else if (p.wn == 2) WS_XTY2(KTV, NTV, 1, 2);   \
-        else WS_XTY2(KTV, NTV, 1, 1);                \
-    } while (0)
-        if (p.kt == 2 && p.nt == 2) WS_XTY2_W(2, 2);
-        else if (p.kt == 2) WS_XTY2_W(2, 1);
-        else if (p.nt == 2) WS_XTY2_W(1, 2);
-        else WS_XTY2_W(1, 1);
-#undef WS_XTY2_W
-#undef WS_XTY2
-    } else {
-#define WS_XTY(NTV, KTV) gemm_xty_kernel<NTV, KTV><<<p.grid, 256, 0, st>>>(x, m, k, ldx, y, n, ldy, p.partial, p.chunk, p.vecx, p.vecy)
-#define WS_XTY_K(NTV)                    \
-    do {                                 \
-        if (p.kt == 1) WS_XTY(NTV, 1);     \
-        else if (p.kt == 2) WS_XTY(NTV, 2); \
-        else WS_XTY(NTV, 4);             \
-    } while (0)
-        if (p.nt == 1) WS_XTY_K(1);
-        else if (p.nt == 2) WS_XTY_K(2);
-        else WS_XTY_K(4);
-#undef WS_XTY_K
-#undef WS_XTY
-    }
+    return xty_run(ws_xty_problem{(const float*)x, m, k, ldx, (const float*)y, n, ldy, out, 0, scratch, 0}, true, stream);
 }
 
 // private to the library (ws_common.h): dW written as a column block of a wider matrix (row pitch ldo >= n)
 int ws_priv_gemm_xty_pitched(const float* x, int64_t m, int32_t k, int64_t ldx, const float* y, int32_t n, int64_t ldy, float* out,
                              int64_t ldo, void* scratch, void* stream)
 {
-    WS_REQUIRE(ldo >= n, "output pitch smaller than a row");
-    return gemm_xty_core(x, m, k, ldx, y, n, ldy, out, scratch, stream, ldo);
-}
-
-static int xty2_group_launch(const ws_xty_problem* q, const XtyPlan* plan, const int* ids, int cnt, hipStream_t st)
-{
-    Xty2Group g{};
-    unsigned total = 0;
-    for (int j = 0; j < cnt; ++j) {
-        const ws_xty_problem& a = q[ids[j]];
-        const XtyPlan& p = plan[ids[j]];
-        g.p[j] = Xty2Problem{a.x, a.m, a.ldx, a.y, a.ldy, p.partial, p.chunk, a.k, a.n, p.grid.x, p.grid.y};
-        total += p.grid.x * p.grid.y * p.grid.z;
-        g.gi.end[j] = total;
-    }
-    for (int j = cnt; j < GROUP_MAX; ++j) g.gi.end[j] = total;
-    const XtyPlan& p0 = plan[ids[0]];
-#define WS_XTY2G(KTV, NTV, WKV, WNV) gemm_xty2_group_kernel<KTV, NTV, WKV, WNV><<<total, 256, 0, st>>>(g)
-#define WS_XTY2G_W(KTV, NTV)                             \
-    do {                                                 \
-        if (p0.wk == 2 && p0.wn == 2) WS_XTY2G(KTV, NTV, 2, 2); \
-        else if (p0.wk == 2) WS_XTY2G(KTV, NTV, 2, 1);     \
-        else if (p0.wn == 2) WS_XTY2G(KTV, NTV, 1, 2);     \
-        else WS_XTY2G(KTV, NTV, 1, 1);                   \
-    } while (0)
-    if (p0.kt == 2 && p0.nt == 2) WS_XTY2G_W(2, 2);
-    else if (p0.kt == 2) WS_XTY2G_W(2, 1);
-    else if (p0.nt == 2) WS_XTY2G_W(1, 2);
-    else WS_XTY2G_W(1, 1);
-#undef WS_XTY2G_W
-#undef WS_XTY2G
-    WS_LAUNCH_CHECK();
-    return WS_OK;
+    WS_REQUIRE(ldo >= n, "output pitch smaller than a row");      // (this entry has no ldo = 0: the record's flat form)
+    return xty_run(ws_xty_problem{x, m, k, ldx, y, n, ldy, out, ldo, scratch, 0}, false, stream);
 }
 
 // private to the library (ws_common.h).  Members in the 32-bit-overflow form (gemm_xty_kernel) run alone, reduction
@@ -1790,117 +1890,37 @@ int ws_priv_gemm_xty_group(const ws_xty_problem* q, int32_t count, void* stream)
     IdList bucket[16], red;
     for (int i = 0; i < count; ++i) {
         const ws_xty_problem& a = q[i];
-        WS_REQUIRE(a.m >= 0 && a.k >= 1 && a.n >= 1 && a.ldx >= a.k && a.ldy >= a.n, "member %d: bad sizes m=%lld k=%d n=%d", i, (long long)a.m, a.k, a.n);
-        WS_REQUIRE(a.out && (a.ldo == 0 || a.ldo >= a.n), "member %d: NULL output / pitch smaller than a row", i);
-        if (a.m == 0) {
-            const int rc = gemm_xty_core(a.x, 0, a.k, a.ldx, a.y, a.n, a.ldy, a.out, a.scratch, stream, a.ldo);
-            if (rc != WS_OK) return rc;
-            continue;
-        }
-        WS_REQUIRE(a.x && a.y && a.scratch, "member %d: NULL argument", i);
-        if (a.scratch_bytes < ws_gemm_xty_scratch_bytes(a.m, a.k, a.n))
-            return ws_fail(WS_ERR_CAPACITY, "member %d: scratch too small: %lld < %lld bytes", i, (long long)a.scratch_bytes,
-                           (long long)ws_gemm_xty_scratch_bytes(a.m, a.k, a.n));
-        const int rc = xty_plan(a.x, a.m, a.k, a.ldx, a.y, a.n, a.ldy, a.out, a.scratch, a.ldo, false, plan[i]);
+        int rc = xty_validate(a, i);
         if (rc != WS_OK) return rc;
+        if (a.m > 0 && a.scratch_bytes < ws_gemm_xty_scratch_bytes(a.m, a.k, a.n))
+            return product_fail(i, WS_ERR_CAPACITY, "scratch too small: %lld < %lld bytes", (long long)a.scratch_bytes,
+                                (long long)ws_gemm_xty_scratch_bytes(a.m, a.k, a.n));
         const XtyPlan& p = plan[i];
-        if (p.lds || (int64_t)p.grid.x * p.grid.y * p.grid.z >= GROUP_MEMBER_BLOCKS) {
-            const int r1 = gemm_xty_core(a.x, a.m, a.k, a.ldx, a.y, a.n, a.ldy, a.out, a.scratch, stream, a.ldo);
-            if (r1 != WS_OK) return r1;
+        rc = xty_plan(a, false, plan[i]);
+        if (rc != WS_OK) return rc;
+        if (a.m == 0 || p.lds || (int64_t)p.grid.x * p.grid.y * p.grid.z >= GROUP_MEMBER_BLOCKS) {
+            rc = xty_run(a, false, stream);
+            if (rc != WS_OK) return rc;
             continue;
         }
         bucket[(((p.kt - 1) * 2 + (p.nt - 1)) * 2 + (p.wk - 1)) * 2 + (p.wn - 1)].push_back(i);
         if (p.reduce) red.push_back(i);
     }
-    for (const IdList& ids : bucket)
-        for (int off = 0; off < ids.size(); off += GROUP_MAX) {
-            const int cnt = ids.size() - off < GROUP_MAX ? ids.size() - off : GROUP_MAX;
-            if (cnt == 1) {
-                const ws_xty_problem& a = q[ids[off]];
-                xty_product_launch(plan[ids[off]], a.x, a.m, a.k, a.ldx, a.y, a.n, a.ldy, st);
-                WS_LAUNCH_CHECK();
-            } else {
-                const int rc = xty2_group_launch(q, plan, ids.data() + off, cnt, st);
-                if (rc != WS_OK) return rc;
-            }
-        }
-    for (int off = 0; off < red.size(); off += GROUP_MAX) {
-        const int cnt = red.size() - off < GROUP_MAX ? red.size() - off : GROUP_MAX;
-        if (cnt == 1) {
-            const ws_xty_problem& a = q[red[off]];
-            const XtyPlan& p = plan[red[off]];
-            launch_reduce_partials(p.partial, (int64_t)a.k * a.n, p.chunks, a.out, st, a.n, p.pitched ? a.ldo : 0);
-            WS_LAUNCH_CHECK();
-            continue;
-        }
-        ReduceGroup g{};
-        unsigned total = 0;
-        for (int j = 0; j < cnt; ++j) {
-            const ws_xty_problem& a = q[red[off + j]];
-            const XtyPlan& p = plan[red[off + j]];
-            const int64_t elems = (int64_t)a.k * a.n;
-            g.p[j] = ReduceProblem{p.partial, elems, a.out, p.pitched ? a.ldo : 0, p.chunks, a.n, p.reduce == 2 ? 1 : 0};
-            total += (unsigned)ws_ceil_div(elems, p.reduce == 2 ? 1024 : 32);
-            g.gi.end[j] = total;
-        }
-        for (int j = cnt; j < GROUP_MAX; ++j) g.gi.end[j] = total;
-        reduce_partials_group_kernel<<<total, 256, 0, st>>>(g);
-        WS_LAUNCH_CHECK();
+    for (const IdList& ids : bucket) {
+        const int rc = for_each_launch(ids, [&](const int* id, int cnt) {
+            return cnt == 1 ? xty_product_launch(q[id[0]], plan[id[0]], st) : launch_xty2_group(q, plan, id, cnt, st);
+        });
+        if (rc != WS_OK) return rc;
     }
-    return WS_OK;
-}
-
-
-// dW = X^T dY with bf16 rows (BASELINE config 5): the LDS-free reduction above with 2-byte operand loads.
-// Requirements: k, n even or <= 32 handled by the one-column form; every shape of the bf16 path qualifies.
-int ws_gemm_xty_bf16(const uint16_t* x, int64_t m, int32_t k, int64_t ldx, const uint16_t* y, int32_t n, int64_t ldy,
-                     float* out, void* scratch, void* stream)
-{
-    WS_REQUIRE(m >= 0 && k >= 1 && n >= 1 && ldx >= k && ldy >= n, "bad sizes m=%lld k=%d n=%d", (long long)m, k, n);
-    WS_REQUIRE(out, "NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (m == 0) {
-        WS_HIP(hipMemsetAsync(out, 0, sizeof(float) * (size_t)k * n, st));
-        return WS_OK;
-    }
-    WS_REQUIRE(x && y && scratch, "NULL argument");
-    XtyPlan p;
-    const int rc = xty_plan(x, m, k, ldx, y, n, ldy, out, scratch, 0, true, p);
-    if (rc != WS_OK) return rc;
-    const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
-    const bf16_t* yb = reinterpret_cast<const bf16_t*>(y);
-#define WS_XTY2B(KTV, NTV, WKV, WNV) gemm_xty2_kernel<KTV, NTV, WKV, WNV, bf16_t><<<p.grid, 256, 0, st>>>(xb, m, k, ldx, yb, n, ldy, p.partial, p.chunk)
-#define WS_XTY2B_W(KTV, NTV)                          \
-    do {                                              \
-        if (p.wk == 2 && p.wn == 2) WS_XTY2B(KTV, NTV, 2, 2); \
-        else if (p.wk == 2) WS_XTY2B(KTV, NTV, 2, 1);   \
-        else if (p.wn == 2) WS_XTY2B(KTV, NTV, 1, 2);   \
-        else WS_XTY2B(KTV, NTV, 1, 1);                \
-    } while (0)
-    if (p.kt == 2 && p.nt == 2) WS_XTY2B_W(2, 2);
-    else if (p.kt == 2) WS_XTY2B_W(2, 1);
-    else if (p.nt == 2) WS_XTY2B_W(1, 2);
-    else WS_XTY2B_W(1, 1);
-#undef WS_XTY2B_W
-#undef WS_XTY2B
-    WS_LAUNCH_CHECK();
-    if (p.reduce) {
-        const int64_t elems = (int64_t)k * n;
-        launch_reduce_partials(p.partial, elems, p.chunks, out, st);
-        WS_LAUNCH_CHECK();
-    }
-    return WS_OK;
+    return for_each_launch(red, [&](const int* id, int cnt) {
+        return cnt == 1 ? xty_reduce_launch(q[id[0]], plan[id[0]], st) : launch_reduce_group(q, plan, id, cnt, st);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
-// Reporters: the launches the entries above make for these arguments (the same plan functions; pointers are only
-// tested for alignment, nothing is read or launched).  Form: "kernel<template arguments> key=value ...".
+// Reporters: the launches the entries above make for these arguments (the same validators and plan functions; pointers are
+// only tested for NULL and alignment, nothing is read or launched).  Form: "kernel<template arguments> key=value ...".
 // ---------------------------------------------------------------------------------------------
-static const char* reduce_name(int r)
-{
-    return r == 2 ? "reduce_partials_wide_kernel" : (r == 1 ? "reduce_partials_kernel" : "none");
-}
-
 // ws_gemm_xb* / ws_priv_gemm_xb_ex: b_row_stride < 0 = row-major [K, N] (the non-strided entries); gate_y / mask as in
 // ws_gemm_xb_gated_strided (dropout and the gathered residual do not change the launch)
 int ws_gemm_xb_variant(const float* x, int64_t m, int32_t k, int64_t ldx, const float* b, int64_t b_row_stride, int64_t b_col_stride,
@@ -1909,18 +1929,19 @@ int ws_gemm_xb_variant(const float* x, int64_t m, int32_t k, int64_t ldx, const 
                        char* out, int32_t cap)
 {
     WS_REQUIRE(out && cap > 0, "bad argument");
-    WS_REQUIRE(m >= 0 && k >= 1 && n >= 1 && ldx >= k && ldy >= n, "bad sizes m=%lld k=%d n=%d", (long long)m, k, n);
-    const int64_t brs = b_row_stride < 0 ? n : b_row_stride;
-    XbGate gate{};
-    gate.y = gate_y; gate.ld = ldg; gate.mask = mask; gate.ldm = ldm;
+    ws_xb_problem q = xb_problem(x, m, k, ldx, b, n, const_cast<float*>(y), ldy, const_cast<void*>(scratch), scratch_bytes);
+    xb_strides(q, b_row_stride, b_col_stride);
+    q.bias = bias; q.residual = residual; q.ldr = ldr;
+    q.gate_y = gate_y; q.ldg = ldg; q.mask = mask; q.ldm = ldm;
     XbPlan p;
-    const int rc = xb_plan(x, m, k, ldx, b, n, bias, residual, ldr, y, ldy, scratch, scratch_bytes, brs, b_col_stride, gate, p);
+    int rc = xb_validate(q, -1);
+    if (rc == WS_OK) rc = xb_plan(q, p);
     if (rc != WS_OK) return rc;
     if (p.kind == XB_NONE)
         snprintf(out, (size_t)cap, "none (m == 0)");
     else if (p.kind == XB_XB2)
         snprintf(out, (size_t)cap, "gemm_xb2_kernel<NT=%d, WN=%d> b=%s epilogue=%s splits=%d csplit=%d%s", p.nt, p.wn,
-                 brs == 1 ? "transposed" : "rows", p.staged ? "staged" : "lanes", p.splits, p.csplit,
+                 xb_brs(q) == 1 ? "transposed" : "rows", p.staged ? "staged" : "lanes", p.splits, p.csplit,
                  p.splits > 1 ? " + splitk_epilogue_kernel" : "");
     else if (p.kind == XB_SHALLOW)
         snprintf(out, (size_t)cap, "gemm_xb_shallow_kernel rows=%d", p.rows);
@@ -1934,10 +1955,11 @@ int ws_gemm_xty_variant(const void* x, int64_t m, int32_t k, int64_t ldx, const 
                         int64_t ldo, void* scratch, int32_t rows_bf16, char* out, int32_t cap)
 {
     WS_REQUIRE(out && cap > 0, "bad argument");
-    WS_REQUIRE(m >= 0 && k >= 1 && n >= 1 && ldx >= k && ldy >= n, "bad sizes m=%lld k=%d n=%d", (long long)m, k, n);
     WS_REQUIRE(!rows_bf16 || ldo == 0, "the bf16 reduction has no pitched form");
+    const ws_xty_problem q{(const float*)x, m, k, ldx, (const float*)y, n, ldy, out_m, ldo, scratch, 0};
     XtyPlan p;
-    const int rc = xty_plan(x, m, k, ldx, y, n, ldy, out_m, scratch, ldo, rows_bf16 != 0, p);
+    int rc = xty_validate(q, -1);
+    if (rc == WS_OK) rc = xty_plan(q, rows_bf16 != 0, p);
     if (rc != WS_OK) return rc;
     const char* form = p.pitched ? "pitched" : "flat";
     if (m == 0)
@@ -1968,4 +1990,3 @@ int ws_act_bwd_colsum_variant(const float* dy, int64_t m, int32_t n, int64_t ldd
 }
 
 }  // extern "C"
-

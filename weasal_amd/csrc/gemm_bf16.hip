@@ -18,7 +18,7 @@
 // dW = X^T dY stays on the exact-f32 MFMA (gemm.hip: gemm_xty2 with 2-byte operand loads; bf16 -> f32 is exact, the
 // products and the running sums are fp32, the result is the fp32 master gradient).
 #include "ws_common.h"
-#include "ws_bf16.h"
+#include "ws_dispatch.h"
 
 extern "C" int ws_gemm_staged;      // gemm.hip: 1 = epilogues turned through LDS
 
@@ -312,15 +312,11 @@ int ws_gemm_xbt_bf16(const uint16_t* x, int64_t m, int32_t k, int64_t ldx, const
     const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
     const bf16_t* bb = reinterpret_cast<const bf16_t*>(bt);
     const bf16_t* rb = reinterpret_cast<const bf16_t*>(residual);
-#define WS_XBT(NTV)                                                                                                        \
-    do {                                                                                                                   \
-        if (out_f32) gemm_xbt_bf16_kernel<NTV, true><<<p.grid, 256, 0, st>>>(xb, m, k, ldx, bb, n, ldbt, y, ldy, bias, rb, ldr, act, slope, p.vecout, p.staged); \
-        else gemm_xbt_bf16_kernel<NTV, false><<<p.grid, 256, 0, st>>>(xb, m, k, ldx, bb, n, ldbt, y, ldy, bias, rb, ldr, act, slope, p.vecout, p.staged);       \
-    } while (0)
-    if (p.nt == 1) WS_XBT(1);
-    else if (p.nt == 2) WS_XBT(2);
-    else WS_XBT(4);
-#undef WS_XBT
+    const bool called = dispatch([&](auto nt, auto f32) {
+        gemm_xbt_bf16_kernel<nt.value, f32.value != 0><<<p.grid, 256, 0, st>>>(xb, m, k, ldx, bb, n, ldbt, y, ldy, bias, rb, ldr, act, slope,
+                                                                              p.vecout, p.staged);
+    }, Pick<1, 2, 4>{p.nt}, Flag{out_f32 != 0});
+    if (!called) return ws_no_instantiation("gemm_xbt_bf16_kernel<NT=%d, OUT_F32=%d>", p.nt, out_f32 != 0);
     WS_LAUNCH_CHECK();
     return WS_OK;
 }

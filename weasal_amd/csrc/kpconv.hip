@@ -13,6 +13,7 @@
 #include <algorithm>
 #include "ws_grid.h"
 #include "ws_bf16.h"
+#include "ws_dispatch.h"
 
 namespace {
 
@@ -2311,7 +2312,6 @@ extern "C" int ws_kpconv_grid_sorted;     // 1: ws_kpconv_gather_bwd_x_grid sums
 int ws_kpconv_grid_sorted = 0;            //    the transposed table: bit-identical to ws_kpconv_gather_bwd_x); 0: in grid-walk order
 
 #include <cstdio>
-#include <type_traits>
 
 namespace {
 
@@ -2515,18 +2515,7 @@ void plan_text(const GatherPlan& p, char* out, size_t n)
     }
 }
 
-// ---- dispatch: a plan's runtime values onto template arguments.  dispatch(f, Pick<1, 2, 4>{v}, ...) calls f with one
-//      std::integral_constant per Pick: the value of its list that equals v (none: f is not called).  What a kernel family does not
-//      instantiate is pruned with if constexpr at the launch.  The row type is one more Pick: Flag{p.bf16} -> Row<bf>.
-template <int... Vs> struct Pick { int v; };
-using Flag = Pick<0, 1>;
-template <typename F> void dispatch(F&& f) { f(); }
-template <typename F, int... Vs, typename... Rest>
-void dispatch(F&& f, Pick<Vs...> a, Rest... rest)
-{
-    (void)(((a.v == Vs) && (dispatch([&](auto... cs) { f(std::integral_constant<int, Vs>{}, cs...); }, rest...), true)) || ...);
-}
-template <int BF> using Row = std::conditional_t<BF != 0, bf16_t, float>;
+// (dispatch, Pick, Flag, Row: ws_dispatch.h)
 int launched() { WS_LAUNCH_CHECK(); return WS_OK; }      // the end of every launcher
 
 // max |kernel point| over kp4 [n] float4, the value ws_kpconv_deform_prepare hands out as kp_rmax, bit for bit (the same

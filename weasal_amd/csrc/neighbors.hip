@@ -15,6 +15,7 @@
 // pass B (fill) sorts and writes int32 or int64 rows padded with ns (neighbors.cpp:324).
 #include "ws_scan.h"
 #include "ws_grid.h"
+#include "ws_dispatch.h"
 #include <vector>
 #include <algorithm>
 
@@ -892,35 +893,23 @@ static int nb_launch_fill(ws_neighbors_ws* ws, int cap, int32_t width, int32_t* 
     int32_t* cn = with_counts ? ws->counts.p : nullptr;
     int32_t* mx = with_counts ? ws->max_count_word : nullptr;
     unsigned long long* kl = ws->key_last;
-#define WS_NB_FILL(CAP)                                                                                            \
-    do {                                                                                                           \
-        if (out_i32)                                                                                               \
-            nb_fill_kernel<CAP, int32_t><<<grid, 256, 0, st>>>(ws->queries, ws->nq, ws->grids.p, ws->nb, ws->cell_start.p, \
-                                                               ws->sorted.p, ws->r2, ws->ns, width, qo, out_i32, cn, mx, kl);  \
-        else                                                                                                       \
-            nb_fill_kernel<CAP, int64_t><<<grid, 256, 0, st>>>(ws->queries, ws->nq, ws->grids.p, ws->nb, ws->cell_start.p, \
-                                                               ws->sorted.p, ws->r2, ws->ns, width, qo, out_i64, cn, mx, kl);  \
-    } while (0)
-    if (cap <= 128) {
-#define WS_NB128(OT, OUT)                                                                                                    \
-    nb_fill128_kernel<OT><<<grid, 256, 0, st>>>(ws->queries, ws->nq, ws->grids.p, ws->nb, ws->cell_start.p, ws->sorted.p,     \
-                                                ws->r2, ws->ns, width, qo, OUT, cn, mx, kl)
-        if (out_i32) WS_NB128(int32_t, out_i32);
-        else WS_NB128(int64_t, out_i64);
-#undef WS_NB128
-    }
-    else if (cap <= 1024) {
-#define WS_NBW(OT, CAPV, OUT)                                                                                          \
-    nb_fill_wide_kernel<OT, CAPV><<<grid, 256, 0, st>>>(ws->queries, ws->nq, ws->grids.p, ws->nb, ws->cell_start.p,    \
-                                                        ws->sorted.p, ws->r2, ws->ns, width, qo, OUT, cn, mx, kl)
-        if (cap <= 576) { if (out_i32) WS_NBW(int32_t, 576, out_i32); else WS_NBW(int64_t, 576, out_i64); }
-        else if (cap <= 704) { if (out_i32) WS_NBW(int32_t, 704, out_i32); else WS_NBW(int64_t, 704, out_i64); }
-        else { if (out_i32) WS_NBW(int32_t, 1024, out_i32); else WS_NBW(int64_t, 1024, out_i64); }
-#undef WS_NBW
-    }
-    else if (cap <= 2048) WS_NB_FILL(2048);
-    else return ws_fail(WS_ERR_UNSUPPORTED, "max neighbour count %d exceeds the 2048-entry sort slab", cap);
-#undef WS_NB_FILL
+    if (cap > 2048) return ws_fail(WS_ERR_UNSUPPORTED, "max neighbour count %d exceeds the 2048-entry sort slab", cap);
+    // the slab the fill sorts in: 128 (nb_fill128_kernel), 576 / 704 / 1024 (nb_fill_wide_kernel), 2048 (nb_fill_kernel)
+    const int slab = cap <= 128 ? 128 : cap <= 576 ? 576 : cap <= 704 ? 704 : cap <= 1024 ? 1024 : 2048;
+    const bool called = dispatch([&](auto i32, auto sl) {
+        using OT = std::conditional_t<i32.value != 0, int32_t, int64_t>;
+        OT* out = i32.value ? (OT*)out_i32 : (OT*)out_i64;
+        if constexpr (sl.value == 128)
+            nb_fill128_kernel<OT><<<grid, 256, 0, st>>>(ws->queries, ws->nq, ws->grids.p, ws->nb, ws->cell_start.p, ws->sorted.p, ws->r2, ws->ns,
+                                                        width, qo, out, cn, mx, kl);
+        else if constexpr (sl.value == 2048)
+            nb_fill_kernel<2048, OT><<<grid, 256, 0, st>>>(ws->queries, ws->nq, ws->grids.p, ws->nb, ws->cell_start.p, ws->sorted.p, ws->r2, ws->ns,
+                                                           width, qo, out, cn, mx, kl);
+        else
+            nb_fill_wide_kernel<OT, sl.value><<<grid, 256, 0, st>>>(ws->queries, ws->nq, ws->grids.p, ws->nb, ws->cell_start.p, ws->sorted.p, ws->r2,
+                                                                    ws->ns, width, qo, out, cn, mx, kl);
+    }, Flag{out_i32 != nullptr}, Pick<128, 576, 704, 1024, 2048>{slab});
+    if (!called) return ws_no_instantiation("neighbour fill: slab=%d (cap=%d)", slab, cap);
     WS_LAUNCH_CHECK();
     return WS_OK;
 }

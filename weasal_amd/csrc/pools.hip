@@ -4,7 +4,7 @@
 // (csr.hip) instead of the reference's scatter_add.
 #include "ws_common.h"
 #include <algorithm>
-#include "ws_bf16.h"
+#include "ws_dispatch.h"
 
 namespace {
 
@@ -431,16 +431,15 @@ int closest_pool_bwd_impl(const T* dy, int64_t nq, int32_t h, int32_t c, const i
         const float* dyf = reinterpret_cast<const float*>(dy);
         float* dxf = reinterpret_cast<float*>(dx);
         hipStream_t st = (hipStream_t)stream;
-#define WS_CPB(GV) closest_pool_bwd_vec_kernel<GV><<<ws_grid(ns, 4), 256, 0, st>>>(dyf, h, c, t_offsets, t_pairs, ns, dxf)
         if (ws_closest_bwd_vec && al && (c == 32 || c == 64 || c == 128 || c % 256 == 0)) {
-            if (c == 32) WS_CPB(8);
-            else if (c == 64) WS_CPB(16);
-            else if (c == 128) WS_CPB(32);
-            else WS_CPB(64);
+            const int g4 = c % 256 == 0 ? 64 : c / 4;       // G: the lanes of a row (c = 4 G), a whole wave for the wide rows
+            const bool called = dispatch([&](auto g) {
+                closest_pool_bwd_vec_kernel<g.value><<<ws_grid(ns, 4), 256, 0, st>>>(dyf, h, c, t_offsets, t_pairs, ns, dxf);
+            }, Pick<8, 16, 32, 64>{g4});
+            if (!called) return ws_no_instantiation("closest_pool_bwd_vec_kernel<G=%d> c=%d", g4, c);
             WS_LAUNCH_CHECK();
             return WS_OK;
         }
-#undef WS_CPB
     }
     closest_pool_bwd_kernel<T><<<ws_grid(ns, 4), 256, 0, (hipStream_t)stream>>>(dy, h, c, t_offsets, t_pairs, ns, dx);
     WS_LAUNCH_CHECK();

@@ -241,6 +241,13 @@ int ws_radius_neighbors_order(const ws_neighbors_ws* ws, int32_t* out_order, voi
 /* per-query neighbour counts of the last plan (device int32 [nq]); valid until the next plan.
  * Feeds the neighbourhood-limit calibration (datasets/DALES_PseudoLabel.py:1238-1240). */
 const int32_t* ws_radius_neighbors_counts(const ws_neighbors_ws* ws);
+/* Which fill kernel ran.  ws_radius_neighbors_fill_variant: name of the launch that fills rows of up to `cap` neighbours,
+ * "kernel<row type[,slab]> grid<=blocks" (slabs 128 / 576 / 704 / 1024 / 2048; `beside`: through the asynchronous entries;
+ * cap 0: the nearest-only kernel; WS_ERR_UNSUPPORTED above 2048) -- the launcher's own rule, no device work.
+ * ws_radius_neighbors_last_fills: the caps of the fill launches the last public entry on `ws` made, in order (every entry
+ * resets the record; the nearest-only search records 0): *n of them, the first min(*n, max) in caps. */
+int ws_radius_neighbors_fill_variant(int32_t cap, int32_t out_i32, int32_t beside, char* out, int32_t out_cap);
+int ws_radius_neighbors_last_fills(const ws_neighbors_ws* ws, int32_t* caps, int32_t max, int32_t* n);
 
 /* Table-free backward of self-query KPConv layers (queries == supports): the cell grid of the last search and the
  * key of the last neighbour kept per query replace the transposed table (ws_transpose_build).

@@ -84,6 +84,8 @@ SIGNATURES = {
                                                   _vp, _vp]),
     "ws_radius_neighbors_order": (C.c_int, [_vp, _vp, _vp]),
     "ws_radius_neighbors_counts": (_vp, [_vp]),
+    "ws_radius_neighbors_fill_variant": (C.c_int, [_i32, _i32, _i32, C.c_char_p, _i32]),
+    "ws_radius_neighbors_last_fills": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32)]),
     "ws_subsample_ws_create": (C.c_int, [C.POINTER(_vp)]),
     "ws_subsample_ws_destroy": (None, [_vp]),
     "ws_grid_subsample_plan": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _f32, _i32, _i32, _vp,

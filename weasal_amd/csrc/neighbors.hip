@@ -728,6 +728,7 @@ struct ws_neighbors_ws {
     const float* supports = nullptr;           // supports of the current grid
     float radius = 0.f;
     std::vector<int32_t> s_lens;               // per-element support counts of the current grid
+    std::vector<int32_t> fills;                // caps of the fill launches of the last public entry (0: nb_nearest_kernel)
 };
 
 extern "C" {
@@ -754,6 +755,7 @@ static int nb_prepare(ws_neighbors_ws* ws, const float* queries, int64_t nq, con
                       const int32_t* h_q_lens, const int32_t* h_s_lens, int32_t nb, float radius, hipStream_t st)
 {
     WS_REQUIRE(ws && h_q_lens && h_s_lens, "NULL argument");
+    ws->fills.clear();
     WS_REQUIRE(nb >= 1 && nq >= 0 && ns >= 0, "bad sizes nb=%d nq=%lld ns=%lld", nb, (long long)nq, (long long)ns);
     WS_REQUIRE(ns < (1ll << 30) && nq < (1ll << 31), "point count exceeds int32 range");
     ws->max_count_host = 0;
@@ -883,19 +885,26 @@ extern "C" int ws_nb_wide_caps = 1;       // 1: slab of the wide asynchronous se
 // stream, which gets wave slots back -- DALES step 13.53 -> 13.42 ms, inference 5.20 -> 5.09 ms, config 5 38.7 -> 38.4 ms
 constexpr int NB_MAX_BLOCKS = 1024;
 
+// the slab the fill sorts rows of up to `cap` neighbours in: 128 (nb_fill128_kernel), 576 / 704 / 1024 (nb_fill_wide_kernel),
+// 2048 (nb_fill_kernel); 0: no slab holds that many.  The one rule of nb_launch_fill and ws_radius_neighbors_fill_variant.
+static int nb_fill_slab(int cap)
+{
+    return cap <= 128 ? 128 : cap <= 576 ? 576 : cap <= 704 ? 704 : cap <= 1024 ? 1024 : cap <= 2048 ? 2048 : 0;
+}
+static int nb_fill_max_blocks(bool beside) { return beside ? NB_MAX_BLOCKS : 256 * 16; }
+
 // beside: the call comes through the asynchronous entries, i.e. from a pyramid builder working beside a training stream: the
 // grid cap above applies; the synchronous entries (the drop-in `batch_query` and plan / fill) have the GPU to themselves: 4 096
 static int nb_launch_fill(ws_neighbors_ws* ws, int cap, int32_t width, int32_t* out_i32, int64_t* out_i64,
                           bool with_counts, hipStream_t st, bool beside = false)
 {
-    const int grid = ws_grid(ws->nq, 4, beside ? NB_MAX_BLOCKS : 256 * 16);
+    const int grid = ws_grid(ws->nq, 4, nb_fill_max_blocks(beside));
     const int32_t* qo = ws->self_query ? ws->order.p : nullptr;
     int32_t* cn = with_counts ? ws->counts.p : nullptr;
     int32_t* mx = with_counts ? ws->max_count_word : nullptr;
     unsigned long long* kl = ws->key_last;
-    if (cap > 2048) return ws_fail(WS_ERR_UNSUPPORTED, "max neighbour count %d exceeds the 2048-entry sort slab", cap);
-    // the slab the fill sorts in: 128 (nb_fill128_kernel), 576 / 704 / 1024 (nb_fill_wide_kernel), 2048 (nb_fill_kernel)
-    const int slab = cap <= 128 ? 128 : cap <= 576 ? 576 : cap <= 704 ? 704 : cap <= 1024 ? 1024 : 2048;
+    const int slab = nb_fill_slab(cap);
+    if (!slab) return ws_fail(WS_ERR_UNSUPPORTED, "max neighbour count %d exceeds the 2048-entry sort slab", cap);
     const bool called = dispatch([&](auto i32, auto sl) {
         using OT = std::conditional_t<i32.value != 0, int32_t, int64_t>;
         OT* out = i32.value ? (OT*)out_i32 : (OT*)out_i64;
@@ -911,6 +920,33 @@ static int nb_launch_fill(ws_neighbors_ws* ws, int cap, int32_t width, int32_t* 
     }, Flag{out_i32 != nullptr}, Pick<128, 576, 704, 1024, 2048>{slab});
     if (!called) return ws_no_instantiation("neighbour fill: slab=%d (cap=%d)", slab, cap);
     WS_LAUNCH_CHECK();
+    ws->fills.push_back(cap);
+    return WS_OK;
+}
+
+int ws_radius_neighbors_fill_variant(int32_t cap, int32_t out_i32, int32_t beside, char* out, int32_t out_cap)
+{
+    WS_REQUIRE(out && out_cap > 0 && cap >= 0, "bad argument");
+    const char* t = out_i32 ? "int32" : "int64";
+    const int slab = nb_fill_slab(cap);
+    if (cap == 0)       // what ws_radius_neighbors_last_fills reports for the nearest-only search
+        snprintf(out, (size_t)out_cap, "nb_nearest_kernel<%s> grid<=%d", t, 256 * 16);
+    else if (!slab)
+        return ws_fail(WS_ERR_UNSUPPORTED, "max neighbour count %d exceeds the 2048-entry sort slab", cap);
+    else if (slab == 128)
+        snprintf(out, (size_t)out_cap, "nb_fill128_kernel<%s> grid<=%d", t, nb_fill_max_blocks(beside != 0));
+    else if (slab == 2048)
+        snprintf(out, (size_t)out_cap, "nb_fill_kernel<2048,%s> grid<=%d", t, nb_fill_max_blocks(beside != 0));
+    else
+        snprintf(out, (size_t)out_cap, "nb_fill_wide_kernel<%s,%d> grid<=%d", t, slab, nb_fill_max_blocks(beside != 0));
+    return WS_OK;
+}
+
+int ws_radius_neighbors_last_fills(const ws_neighbors_ws* ws, int32_t* caps, int32_t max, int32_t* n)
+{
+    WS_REQUIRE(ws && n && max >= 0 && (caps || max == 0), "NULL argument");
+    *n = (int32_t)ws->fills.size();
+    for (int32_t i = 0; i < *n && i < max; ++i) caps[i] = ws->fills[(size_t)i];
     return WS_OK;
 }
 
@@ -995,6 +1031,7 @@ int ws_radius_neighbors_nearest_async(ws_neighbors_ws* ws, const float* queries,
         nb_nearest_kernel<int64_t><<<grid, 256, 0, st>>>(ws->queries, ws->nq, ws->grids.p, ws->nb, ws->cell_start.p, ws->sorted.p, ws->r2,
                                                          ws->ns, qo, out_i64, ws->max_count_word);
     WS_LAUNCH_CHECK();
+    ws->fills.push_back(0);
     WS_HIP(hipMemcpyAsync(d_any, ws->max_count_word, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     ws->max_count_host = 1;
     return WS_OK;
@@ -1006,6 +1043,7 @@ int ws_radius_neighbors_fill(ws_neighbors_ws* ws, int32_t width, int32_t* out_i3
     WS_REQUIRE(ws && ws->nq > 0 && ws->max_count_host > 0, "no successful plan to fill from");
     WS_REQUIRE((out_i32 != nullptr) != (out_i64 != nullptr), "exactly one of out_i32 / out_i64 must be given");
     WS_REQUIRE(width >= 1 && width <= ws->max_count_host, "width %d outside [1, max_count=%d]", width, ws->max_count_host);
+    ws->fills.clear();
     return nb_launch_fill(ws, ws->max_count_host, width, out_i32, out_i64, false, (hipStream_t)stream);
 }
 

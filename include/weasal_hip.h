@@ -900,6 +900,70 @@ int ws_sampler_batch(ws_sampler* ws, const void* h_draws, int32_t max_spheres, i
                      int64_t* out_input_inds, int32_t* out_lengths, float* out_scales, float* out_rots, int32_t* out_cloud_inds,
                      int32_t* out_point_inds, int64_t capacity_rows, void* d_state, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The same chain with colour columns and with centres from a list, and the class-balanced draw of that list.
+ *
+ * ws_sampler_add_cloud also takes pot_points = potentials = NULL with p = 0: a tile that only the random mode serves.
+ * ws_sampler_set_colors: sub_colors [n, ncol] f32 of an added cloud, 1 <= ncol <= 3 (any other ncol: WS_ERR_UNSUPPORTED);
+ *   replaces `self.input_colors[cloud_ind][input_inds]` (datasets/Vaihingen3D_PseudoLabel.py:366, :562; Vaihingen3D_WeakLabel.py
+ *   :463-535).  Every cloud of a sampler carries the same ncol.  Synchronises; the pointer must stay valid.
+ * ws_sampler_batch_items: ws_sampler_batch behind one descriptor; the fields named as its arguments mean what they mean
+ *   there, and with no colours, h_colour_keep = NULL and random_centres = 0 it queues the same launches and writes the same
+ *   bits (ws_sampler_batch fills this descriptor and calls it; on a sampler with colours it keeps every slot's).  In addition:
+ *     features = [1] followed by the first fd - 1 columns of [colours..., f32(f64(z') + centre_z), z']
+ *       (Vaihingen3D_PseudoLabel.py:383, :424-432); accepted fd: {1, 3} without colours, {1, 1 + ncol, 3 + ncol} with them,
+ *       any other: WS_ERR_UNSUPPORTED with the reference's message ('... 1 and 3' / '... 1, 2 and 4' for ncol = 1);
+ *     h_colour_keep: host int32 [max_spheres] or NULL (all 1) -- slot k with 0 writes +0.0f in its colour columns
+ *       (`if np.random.rand() > config.augment_color: input_colors *= 0`, :379-380), else the colour is copied bit for bit;
+ *     random_centres = 1: `random_item` (datasets/DALES_PseudoLabel.py:520-640, Vaihingen3D_PseudoLabel.py:516-643).  Slot k
+ *       takes cloud = epoch_inds[0, e], point = epoch_inds[1, e], e = *epoch_i (device int64 [2, n_centres] and device
+ *       int64; indices outside the tables are clamped into them), centre = f64(sub_points[point]) + noise (:547-551; the
+ *       tile itself is NOT modified), point_inds = point.  *epoch_i advances by one, wrapping at n_centres (:538-540), with
+ *       every sphere the chain commits, kept or dropped (n < 2; the reference has no such guard), and stays where it is
+ *       for a sphere left undone by `overflow`.  No potential is read or written, update_potentials is ignored.
+ *   Launches: 1 + 3 * max_spheres in both modes, whatever the data.
+ * ws_sampler_class_counts / ws_sampler_class_select: the lookups of the class-balanced centre draw (`*Sampler.__iter__`,
+ *   datasets/DALES_PseudoLabel.py:961-975) on the resident labels.  values: device int32 [n_class <= 64], the raw label
+ *   values of the non-ignored classes.  _counts: out_counts[cloud, c] (device int64 [n_clouds, n_class]) =
+ *   len(np.where(sub_labels == values[c])[0]) (:965); two launches; keeps per-chunk scanned counts inside `ws`.  _select:
+ *   triples device int64 [n_triples, 3] rows (cloud, c, position) -> out_points[t] = np.where(sub_labels == values[c])[0]
+ *   [position], or -1 when the class has no such member; one launch; needs the _counts of the same labels first.
+ *   Neither synchronises.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ws_sampler_items {
+    const void* h_draws;
+    const int32_t* h_colour_keep;
+    int32_t max_spheres, resume;
+    int64_t batch_limit;
+    double in_radius;
+    float augment_noise;
+    int32_t fd;
+    uint64_t seed, seq0;
+    const int32_t* label_lut;
+    int32_t lut_n, labels_zero, update_potentials, random_centres;
+    const int64_t* epoch_inds;
+    int64_t n_centres;
+    int64_t* epoch_i;
+    float* out_points;
+    float* out_features;
+    int64_t* out_labels;
+    int64_t* out_input_inds;
+    int32_t* out_lengths;
+    float* out_scales;
+    float* out_rots;
+    int32_t* out_cloud_inds;
+    int32_t* out_point_inds;
+    int64_t capacity_rows;
+    void* d_state;
+    void* stream;
+} ws_sampler_items;
+int64_t ws_sampler_items_bytes(void);   /* sizeof(ws_sampler_items) */
+int ws_sampler_set_colors(ws_sampler* ws, int32_t cloud, const float* colors, int32_t ncol, void* stream);
+int ws_sampler_batch_items(ws_sampler* ws, const ws_sampler_items* items);
+int ws_sampler_class_counts(ws_sampler* ws, const int32_t* values, int32_t n_class, int64_t* out_counts, void* stream);
+int ws_sampler_class_select(ws_sampler* ws, const int32_t* values, int32_t n_class, const int64_t* triples, int64_t n_triples,
+                            int64_t* out_points, void* stream);
+
 /* nn.Dropout on the decoder output in front of the head, training mode (models/architectures.py:345-346): out[i] = keep(i) ? in[i] / (1 - p) : 0,
  * keep(i) a pure function of (seed, i) (counter-based; Bernoulli(1 - p)): the backward is the same call on the incoming
  * gradient with the same seed, no mask is stored.  in / out float32 [n], 16-byte aligned; in == out allowed. */

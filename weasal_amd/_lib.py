@@ -166,6 +166,11 @@ SIGNATURES = {
     "ws_sampler_draw_bytes": (_i64, []),
     "ws_sampler_batch": (C.c_int, [_vp, _vp, _i32, _i32, _i64, C.c_double, _f32, C.c_uint64, C.c_uint64, _i32, _vp, _i32, _i32, _i32,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "ws_sampler_items_bytes": (_i64, []),
+    "ws_sampler_set_colors": (C.c_int, [_vp, _i32, _vp, _i32, _vp]),
+    "ws_sampler_batch_items": (C.c_int, [_vp, _vp]),
+    "ws_sampler_class_counts": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    "ws_sampler_class_select": (C.c_int, [_vp, _vp, _i32, _vp, _i64, _vp, _vp]),
     "ws_softmax_ce_scratch_bytes": (_i64, [_i64]),
     "ws_softmax_ce_fwd": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ws_softmax_ce_bwd": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),

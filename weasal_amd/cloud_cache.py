@@ -35,26 +35,61 @@ def read_tile(file_path):
     return np.ascontiguousarray(points), np.asarray(data['class'])
 
 
-def write_sub_cloud(path, sub_points, sub_labels):
-    """the cached sub-cloud file (DALES_PseudoLabel.py:797-800): fields x, y, z (float32) and class (int32)"""
-    return write_ply(path, [np.asarray(sub_points, np.float32), np.asarray(sub_labels, np.int32).reshape(-1)],
-                     ['x', 'y', 'z', 'class'])
+def read_tile_colors(file_path, color_field):
+    """(points float32 [N,3], colours float32 [N,1], labels int32 [N]) of an original tile with one colour field
+    (Vaihingen3D_PseudoLabel.py:795-799: x y z intensity class)"""
+    data = read_ply(file_path)
+    points = np.vstack((data['x'], data['y'], data['z'])).T.astype(np.float32)
+    colors = np.expand_dims(np.asarray(data[color_field]).T, axis=-1).astype(np.float32)
+    return np.ascontiguousarray(points), np.ascontiguousarray(colors), np.asarray(data['class'])
 
 
-def read_sub_cloud(path):
-    """-> (sub_points float32 [M,3], sub_labels int32 [M]) of a cached sub-cloud file (:735-737)"""
+def write_sub_cloud(path, sub_points, sub_labels, sub_colors=None, color_field=None):
+    """the cached sub-cloud file (DALES_PseudoLabel.py:797-800): fields x, y, z (float32) and class (int32); with
+    sub_colors [M,1] float32 and its field name, x, y, z, <color_field>, class (Vaihingen3D_PseudoLabel.py:821-823)"""
+    if sub_colors is None:
+        return write_ply(path, [np.asarray(sub_points, np.float32), np.asarray(sub_labels, np.int32).reshape(-1)],
+                         ['x', 'y', 'z', 'class'])
+    return write_ply(path, [np.asarray(sub_points, np.float32), np.asarray(sub_colors, np.float32).reshape(-1, 1),
+                            np.asarray(sub_labels, np.int32).reshape(-1)], ['x', 'y', 'z', color_field, 'class'])
+
+
+def read_sub_cloud(path, color_field=None):
+    """-> (sub_points float32 [M,3], sub_labels int32 [M]) of a cached sub-cloud file (:735-737); with color_field also its
+    colours float32 [M,1] as a third value (Vaihingen3D_PseudoLabel.py:745-747, :784-785)"""
     data = read_ply(path)
     pts = np.vstack((data['x'], data['y'], data['z'])).T.astype(np.float32)
-    return np.ascontiguousarray(pts), np.asarray(data['class'])
+    if color_field is None:
+        return np.ascontiguousarray(pts), np.asarray(data['class'])
+    col = np.expand_dims(np.asarray(data[color_field], np.float32), axis=-1)
+    return np.ascontiguousarray(pts), np.asarray(data['class']), np.ascontiguousarray(col)
 
 
-def load_subsampled_cloud(root, cloud_name, file_path, dl, device):
+def load_subsampled_cloud(root, cloud_name, file_path, dl, device, color_field=None):
     """One tile of ``load_subsampled_clouds``: the cached sub-cloud if ``input_{dl:.3f}/<name>.ply`` exists, else the tile
     is read, subsampled on the GPU (K2, labels by majority per cell) and the cache file written.
-    -> (sub_points [M,3] float32 device tensor, sub_labels [M] int32 device tensor, built: bool)"""
+    -> (sub_points [M,3] float32 device tensor, sub_labels [M] int32 device tensor, built: bool)
+    color_field='intensity' (Vaihingen3D_PseudoLabel.py:794-827): the tile's x y z intensity class are read, the field is
+    averaged per cell with the points (K2 features), divided by 255 in float32 (on the host: numpy's rounding, the
+    reference's `sub_colors / 255`) and written as the fourth field
+    -> (sub_points, sub_labels, sub_colors [M,1] float32 device tensor, built)"""
     d = cache_dir(root, dl)
     os.makedirs(d, exist_ok=True)
     sub_file = os.path.join(d, '{:s}.ply'.format(cloud_name))
+    if color_field is not None:
+        if os.path.exists(sub_file):
+            pts, lab, col = read_sub_cloud(sub_file, color_field)
+            return (torch.from_numpy(pts).to(device), torch.from_numpy(lab.astype(np.int32)).to(device),
+                    torch.from_numpy(col).to(device), False)
+        points, colors, labels = read_tile_colors(file_path, color_field)
+        P = torch.from_numpy(points).to(device)
+        sub_p, _, sub_f, sub_l = ops.grid_subsample(P, np.array([P.shape[0]], np.int32), dl, features=torch.from_numpy(colors).to(device),
+                                                    labels=torch.from_numpy(labels.astype(np.int32)).to(device))
+        sub_l = sub_l.reshape(-1)
+        col = (sub_f.cpu().numpy().astype(np.float32) / 255).astype(np.float32)
+        if not write_sub_cloud(sub_file, sub_p.cpu().numpy(), sub_l.cpu().numpy(), col, color_field):
+            raise RuntimeError("could not write " + sub_file)
+        return sub_p, sub_l, torch.from_numpy(col).to(device), True
     if os.path.exists(sub_file):
         pts, lab = read_sub_cloud(sub_file)
         return torch.from_numpy(pts).to(device), torch.from_numpy(lab.astype(np.int32)).to(device), False

@@ -17,6 +17,17 @@
 //   sphere_emit_kernel    workgroups [0, gp): store the updated potentials (same expression, same bits as the scan);
 //                         workgroups [gp, gp + gn): members of their chunk in ASCENDING index order at the sphere's row
 //                         offset -- centred points, augmentation, features, labels, input indices
+// Two additions leave that chain as it is (ws_sampler_batch_items):
+//   colours   a cloud may carry sub_colors [n, ncol] (ws_sampler_set_colors; Vaihingen3D_PseudoLabel.py:366, :379-383): the
+//             emit body copies them in front of the two height columns, or writes +0 for a slot whose colour_keep is 0;
+//   random    centres from a list (cloud, point) on the device instead of the potentials (`random_item`, DALES_PseudoLabel.py
+//             :520-640): gp = 0, so no workgroup touches a potential; `pick` reads epoch_inds[*epoch_i] and the decide kernel
+//             advances epoch_i with every sphere it commits (kept or dropped), never with one it leaves undone.
+// The class-balanced draw of those centres (`*Sampler.__iter__`, :941-992) is a select-by-rank on the resident labels:
+//   class_count_kernel    per (cloud, chunk): members of every class in the chunk
+//   class_scan_kernel     per cloud: exclusive scan of every class's chunk counts, totals [n_clouds, n_class] (the host reads
+//                         these, draws POSITIONS with its own stream and uploads (cloud, class, position) triples)
+//   class_select_kernel   per triple: chunk by binary search in the scanned counts, then the rank inside that one chunk
 // Every kernel starts by reading `done` and returns when it is set.  Membership is tested twice (count, emit) instead of
 // being stored: 12 bytes read per point against 4 written and 4 read for a flag array, and no N-sized scratch.
 //
@@ -32,6 +43,8 @@
 #define WS_SAMPLER_MAX_CLOUDS 4096
 #define WS_SAMPLER_GP 256               /* workgroups over the potential points, at most */
 #define WS_SAMPLER_GN 1024              /* workgroups over the cloud's points, at most (4 counts per thread in the decide kernel) */
+#define WS_SAMPLER_MAX_CLASSES 64       /* classes of the centre draw */
+#define WS_SAMPLER_MAX_COLORS 3
 
 namespace {
 
@@ -41,6 +54,8 @@ struct WsCloud {
     const float* pot_pts;    // [p,3]
     double* pot;             // [p]
     long long n, p;
+    const float* colors;     // [n,ncol] or NULL
+    long long ncol;
 };
 
 struct WsDraw {              // host-drawn values of one sphere slot (72 bytes, mirrored by weasal_amd/sampler.py)
@@ -87,6 +102,12 @@ struct WsArgs {
     float* out_rots;
     int32_t* out_cloud_inds;
     int32_t* out_point_inds;
+    const int32_t* keep;               // colour_keep per slot, or NULL (every slot keeps its colours)
+    int ncol;
+    int random;                        // centres from epoch_inds
+    const long long* epoch_inds;       // [2, n_centres]
+    long long n_centres;
+    long long* epoch_i;
 };
 
 // reduced distance of the tree: ((dx^2 + dy^2) + dz^2) in float64, d = f64(point) - centre
@@ -114,6 +135,20 @@ __device__ __forceinline__ double tukey_new(const float* __restrict__ p, double 
 // Called by all 256 threads; sv / si are free again on return.
 __device__ __forceinline__ void pick(const WsArgs& a, int k, double* sv, long long* si, int& cloud, long long& point, double* c)
 {
+    if (a.random) {          // DALES_PseudoLabel.py:534-535, :547-551: centre = f64(sub_points[point]) + noise
+        long long e = *a.epoch_i;
+        e = e < 0 ? 0 : (e >= a.n_centres ? a.n_centres - 1 : e);
+        long long cl = a.epoch_inds[e], pt = a.epoch_inds[a.n_centres + e];
+        cl = cl < 0 ? 0 : (cl >= a.nc ? a.nc - 1 : cl);            // a list from outside stays inside the tables
+        const long long n = a.clouds[cl].n;
+        pt = pt < 0 ? 0 : (pt >= n ? n - 1 : pt);
+        cloud = (int)cl;
+        point = pt;
+        const float* pp = a.clouds[cl].pts;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) c[j] = __dadd_rn((double)pp[3 * pt + j], a.draws[k].noise[j]);
+        return;
+    }
     double best = 1.0e308;
     long long bi = -1;
     for (int e = threadIdx.x; e < a.nc; e += 256) ws_argmin_take(best, bi, a.min_pot[e], e);
@@ -249,6 +284,10 @@ __global__ __launch_bounds__(256) void sphere_decide_kernel(WsArgs a)
         a.min_pot[cloud] = new_min;
         a.argmin[cloud] = new_arg;
     }
+    if ((flags & 1) && a.random) {                         // :538-540, once per attempted sphere
+        const long long e = *a.epoch_i + 1;
+        *a.epoch_i = e >= a.n_centres ? e - a.n_centres : e;
+    }
     if (st->attempts >= a.max_slots) st->done = 1;
     st->cur_flags = flags;
 }
@@ -288,6 +327,7 @@ __global__ __launch_bounds__(256) void sphere_emit_kernel(WsArgs a)
     if (!(flags & 2)) return;
     const int b = blockIdx.x - a.gp;
     const WsDraw dr = a.draws[k];
+    const bool keep_col = !a.keep || a.keep[k] != 0;
     if (b == 0 && threadIdx.x == 0) {                      // the per-sphere tail of the input list (:419-427, :456)
         const long long o = sl.ord;
         a.out_lengths[o] = (int32_t)sl.n;
@@ -321,9 +361,14 @@ __global__ __launch_bounds__(256) void sphere_emit_kernel(WsArgs a)
             }
             float* fr = a.out_features + row * a.fd;
             fr[0] = 1.0f;
-            if (a.fd == 3) {                                                                              // :389, :430-434
-                fr[1] = (float)__dadd_rn((double)q[2], c[2]);
-                fr[2] = q[2];
+            // [colours..., f32(f64(z') + centre_z), z'] cut to fd - 1 columns (:389, :430-434; Vaihingen3D_PseudoLabel.py
+            // :379-383, :424-432)
+            for (int e = 0; e < a.fd - 1; ++e) {
+                float v;
+                if (e < a.ncol) v = keep_col ? cl.colors[i * a.ncol + e] : 0.0f;
+                else if (e == a.ncol) v = (float)__dadd_rn((double)q[2], c[2]);
+                else v = q[2];
+                fr[1 + e] = v;
             }
             long long lab = 0;
             if (!a.labels_zero) {                                                                         // :377-381
@@ -349,6 +394,91 @@ __global__ __launch_bounds__(256) void sampler_cloud_min_kernel(const double* __
     if (threadIdx.x == 0) { *out_min = sv[0]; *out_arg = si[0] < 0 ? 0 : si[0]; }
 }
 
+// ---- the class-balanced centre draw (DALES_PseudoLabel.py:961-975): np.where(labels == v)[0][pos] without the index list ----
+
+// counts[(cloud * ncls + c) * gn + chunk] = members of class c (raw value values[c]) in that chunk of the cloud's labels
+__global__ __launch_bounds__(256) void class_count_kernel(const WsCloud* __restrict__ clouds, const int32_t* __restrict__ values, int ncls,
+                                                          int gn, int* __restrict__ counts)
+{
+    __shared__ int cnt[WS_SAMPLER_MAX_CLASSES];
+    __shared__ int val[WS_SAMPLER_MAX_CLASSES];
+    const int cloud = blockIdx.y, b = blockIdx.x;
+    if (threadIdx.x < ncls) { cnt[threadIdx.x] = 0; val[threadIdx.x] = values[threadIdx.x]; }
+    __syncthreads();
+    const WsCloud cl = clouds[cloud];
+    long long beg, end;
+    chunk(cl.n, gn, b, beg, end);
+    for (long long i = beg + threadIdx.x; i < end; i += 256) {
+        const int l = cl.labels[i];
+        for (int c = 0; c < ncls; ++c)
+            if (val[c] == l) atomicAdd(&cnt[c], 1);        // integer, in LDS: the sum does not depend on the order
+    }
+    __syncthreads();
+    if (threadIdx.x < ncls) counts[((long long)cloud * ncls + threadIdx.x) * gn + b] = cnt[threadIdx.x];
+}
+
+// one workgroup per cloud: every class's gn counts -> exclusive offsets in place, the class total -> totals[cloud, c]
+__global__ __launch_bounds__(256) void class_scan_kernel(int ncls, int gn, int* __restrict__ counts, long long* __restrict__ totals)
+{
+    __shared__ int lds[WS_SCAN_BLOCK / 64 + 1];
+    const int cloud = blockIdx.x;
+    for (int c = 0; c < ncls; ++c) {
+        int* row = counts + ((long long)cloud * ncls + c) * gn;
+        int v[4], s = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = threadIdx.x * 4 + e;
+            v[e] = j < gn ? row[j] : 0;
+            s += v[e];
+        }
+        int total;
+        int run = ws_block_exclusive_scan(s, lds, total);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = threadIdx.x * 4 + e;
+            if (j < gn) row[j] = run;
+            run += v[e];
+        }
+        if (threadIdx.x == 0) totals[(long long)cloud * ncls + c] = total;
+    }
+}
+
+// one workgroup per (cloud, class, position): out = index of the position-th point of that class, ascending; -1 when the
+// class has no such member (the labels changed since the counts were read)
+__global__ __launch_bounds__(256) void class_select_kernel(const WsCloud* __restrict__ clouds, int nc, const int32_t* __restrict__ values,
+                                                           int ncls, int gn, const int* __restrict__ offs,
+                                                           const long long* __restrict__ triples, long long* __restrict__ out)
+{
+    __shared__ int lds[WS_SCAN_BLOCK / 64 + 1];
+    const long long t = blockIdx.x;
+    const long long cloud = triples[3 * t], c = triples[3 * t + 1], pos = triples[3 * t + 2];
+    if (cloud < 0 || cloud >= nc || c < 0 || c >= ncls || pos < 0) return;
+    const int* row = offs + (cloud * ncls + c) * gn;
+    int lo = 0, hi = gn;                                   // last chunk whose offset is <= pos: empty chunks share the
+    while (hi - lo > 1) {                                  // offset of the next one that holds a member
+        const int mid = (lo + hi) >> 1;
+        if (row[mid] <= pos) lo = mid; else hi = mid;
+    }
+    const WsCloud cl = clouds[cloud];
+    const int v = values[c];
+    long long beg, end;
+    chunk(cl.n, gn, lo, beg, end);
+    long long r = pos - row[lo];
+    long long found = -1;
+    for (long long t0 = beg; t0 < end; t0 += 256) {
+        const long long i = t0 + threadIdx.x;
+        const int f = (i < end && cl.labels[i] == v) ? 1 : 0;
+        int tot;
+        const int p = ws_block_exclusive_scan(f, lds, tot);
+        if (r < tot) {
+            if (f && p == r) found = i;
+            break;
+        }
+        r -= tot;
+    }
+    if (found >= 0) out[t] = found;                        // `out` was filled with -1 before the launch
+}
+
 }  // namespace
 
 struct ws_sampler {
@@ -360,6 +490,10 @@ struct ws_sampler {
     double* d_pv = nullptr;
     long long* d_pi = nullptr;
     int* d_counts = nullptr;
+    int32_t* d_keep = nullptr;
+    int* d_class = nullptr;            // per (cloud, class, chunk) counts of the centre draw, scanned in place
+    size_t class_bytes = 0;
+    int class_n = 0, class_gn = 0, class_nc = 0;
     long long nmax = 0, pmax = 0;
 };
 
@@ -380,6 +514,7 @@ int ws_sampler_create(ws_sampler** out)
     WS_HIP(hipMalloc(&ws->d_pv, sizeof(double) * WS_SAMPLER_GP));
     WS_HIP(hipMalloc(&ws->d_pi, sizeof(long long) * WS_SAMPLER_GP));
     WS_HIP(hipMalloc(&ws->d_counts, sizeof(int) * (WS_SAMPLER_GN + 1)));
+    WS_HIP(hipMalloc(&ws->d_keep, sizeof(int32_t) * WS_SAMPLER_MAX_SPHERES));
     return WS_OK;
 }
 
@@ -393,21 +528,27 @@ void ws_sampler_destroy(ws_sampler* ws)
     (void)hipFree(ws->d_pv);
     (void)hipFree(ws->d_pi);
     (void)hipFree(ws->d_counts);
+    (void)hipFree(ws->d_keep);
+    (void)hipFree(ws->d_class);
     delete ws;
 }
 
 int ws_sampler_add_cloud(ws_sampler* ws, const float* sub_points, const int32_t* sub_labels, int64_t n, const float* pot_points,
                          double* potentials, int64_t p, void* stream)
 {
-    WS_REQUIRE(ws && sub_points && pot_points && potentials, "NULL argument");
-    WS_REQUIRE(n >= 1 && n < 2147483647ll && p >= 1 && p < 2147483647ll, "bad sizes n=%lld p=%lld", (long long)n, (long long)p);
+    const bool no_pot = !pot_points && !potentials && p == 0;      // a tile of the random mode: no potential is ever read
+    WS_REQUIRE(ws && sub_points && (no_pot || (pot_points && potentials)), "NULL argument");
+    WS_REQUIRE(n >= 1 && n < 2147483647ll && (no_pot || (p >= 1 && p < 2147483647ll)), "bad sizes n=%lld p=%lld", (long long)n,
+               (long long)p);
     WS_REQUIRE(ws->clouds.size() < WS_SAMPLER_MAX_CLOUDS, "more than %d clouds", WS_SAMPLER_MAX_CLOUDS);
-    const WsCloud cl{sub_points, sub_labels, pot_points, potentials, (long long)n, (long long)p};
+    const WsCloud cl{sub_points, sub_labels, pot_points, potentials, (long long)n, (long long)p, nullptr, 0};
     const size_t i = ws->clouds.size();
     hipStream_t st = (hipStream_t)stream;
     WS_HIP(hipMemcpyAsync(ws->d_clouds + i, &cl, sizeof(WsCloud), hipMemcpyHostToDevice, st));
-    sampler_cloud_min_kernel<<<1, 256, 0, st>>>(potentials, (long long)p, ws->d_min + i, ws->d_arg + i);
-    WS_LAUNCH_CHECK();
+    if (!no_pot) {
+        sampler_cloud_min_kernel<<<1, 256, 0, st>>>(potentials, (long long)p, ws->d_min + i, ws->d_arg + i);
+        WS_LAUNCH_CHECK();
+    }
     WS_HIP(hipStreamSynchronize(st));                      // `cl` is a stack value
     ws->clouds.push_back(cl);
     if (n > ws->nmax) ws->nmax = n;
@@ -415,62 +556,97 @@ int ws_sampler_add_cloud(ws_sampler* ws, const float* sub_points, const int32_t*
     return WS_OK;
 }
 
-int ws_sampler_batch(ws_sampler* ws, const void* h_draws, int32_t max_spheres, int32_t resume, int64_t batch_limit, double in_radius,
-                     float augment_noise, uint64_t seed, uint64_t seq0, int32_t fd, const int32_t* label_lut, int32_t lut_n,
-                     int32_t labels_zero, int32_t update_potentials, float* out_points, float* out_features, int64_t* out_labels,
-                     int64_t* out_input_inds, int32_t* out_lengths, float* out_scales, float* out_rots, int32_t* out_cloud_inds,
-                     int32_t* out_point_inds, int64_t capacity_rows, void* d_state, void* stream)
+int ws_sampler_set_colors(ws_sampler* ws, int32_t cloud, const float* colors, int32_t ncol, void* stream)
 {
-    WS_REQUIRE(ws && h_draws && d_state, "NULL argument");
+    WS_REQUIRE(ws && colors, "NULL argument");
+    WS_REQUIRE(cloud >= 0 && (size_t)cloud < ws->clouds.size(), "cloud=%d outside [0, %d)", cloud, (int)ws->clouds.size());
+    if (ncol < 1 || ncol > WS_SAMPLER_MAX_COLORS)
+        return ws_fail(WS_ERR_UNSUPPORTED, "ncol=%d colour columns: 1 to %d are built", ncol, WS_SAMPLER_MAX_COLORS);
+    WsCloud cl = ws->clouds[cloud];
+    cl.colors = colors;
+    cl.ncol = ncol;
+    hipStream_t st = (hipStream_t)stream;
+    WS_HIP(hipMemcpyAsync(ws->d_clouds + cloud, &cl, sizeof(WsCloud), hipMemcpyHostToDevice, st));
+    WS_HIP(hipStreamSynchronize(st));                      // `cl` is a stack value
+    ws->clouds[cloud] = cl;
+    return WS_OK;
+}
+
+int64_t ws_sampler_items_bytes(void) { return (int64_t)sizeof(ws_sampler_items); }
+
+int ws_sampler_batch_items(ws_sampler* ws, const ws_sampler_items* it)
+{
+    WS_REQUIRE(ws && it && it->h_draws && it->d_state, "NULL argument");
     WS_REQUIRE(!ws->clouds.empty(), "no cloud was added");
+    const int32_t max_spheres = it->max_spheres, fd = it->fd;
     WS_REQUIRE(max_spheres >= 1 && max_spheres <= WS_SAMPLER_MAX_SPHERES, "max_spheres=%d outside [1, %d]", max_spheres,
                WS_SAMPLER_MAX_SPHERES);
-    WS_REQUIRE(in_radius > 0.0 && capacity_rows >= 1 && batch_limit >= 0, "bad in_radius=%g capacity_rows=%lld batch_limit=%lld",
-               in_radius, (long long)capacity_rows, (long long)batch_limit);
-    if (fd != 1 && fd != 3) return ws_fail(WS_ERR_UNSUPPORTED, "Only accepted input dimensions are 1 and 3");
-    WS_REQUIRE(out_points && out_features && out_labels && out_input_inds && out_lengths && out_scales && out_rots && out_cloud_inds &&
-               out_point_inds, "NULL output");
-    if (!labels_zero)
+    WS_REQUIRE(it->in_radius > 0.0 && it->capacity_rows >= 1 && it->batch_limit >= 0, "bad in_radius=%g capacity_rows=%lld batch_limit=%lld",
+               it->in_radius, (long long)it->capacity_rows, (long long)it->batch_limit);
+    const long long ncol = ws->clouds[0].ncol;
+    for (const WsCloud& c : ws->clouds) WS_REQUIRE(c.ncol == ncol, "every cloud needs the same number of colour columns");
+    if (ncol == 0) {
+        if (fd != 1 && fd != 3) return ws_fail(WS_ERR_UNSUPPORTED, "Only accepted input dimensions are 1 and 3");
+    } else if (fd != 1 && fd != 1 + ncol && fd != 3 + ncol) {
+        return ws_fail(WS_ERR_UNSUPPORTED, "Only accepted input dimensions are 1, %d and %d", (int)(1 + ncol), (int)(3 + ncol));
+    }
+    WS_REQUIRE(it->out_points && it->out_features && it->out_labels && it->out_input_inds && it->out_lengths && it->out_scales &&
+               it->out_rots && it->out_cloud_inds && it->out_point_inds, "NULL output");
+    if (!it->labels_zero)
         for (const WsCloud& c : ws->clouds) WS_REQUIRE(c.labels, "a cloud without labels needs labels_zero");
-    WS_REQUIRE(!label_lut || lut_n >= 1, "bad lut_n=%d", lut_n);
-    hipStream_t st = (hipStream_t)stream;
-    WS_HIP(hipMemcpyAsync(ws->d_draws, h_draws, sizeof(WsDraw) * max_spheres, hipMemcpyHostToDevice, st));
+    WS_REQUIRE(!it->label_lut || it->lut_n >= 1, "bad lut_n=%d", it->lut_n);
+    if (it->random_centres) {
+        WS_REQUIRE(it->epoch_inds && it->epoch_i && it->n_centres >= 1, "the random mode needs epoch_inds [2, n_centres >= 1] and epoch_i");
+    } else {
+        for (const WsCloud& c : ws->clouds) WS_REQUIRE(c.p >= 1, "a cloud without potential points serves the random mode only");
+    }
+    hipStream_t st = (hipStream_t)it->stream;
+    WS_HIP(hipMemcpyAsync(ws->d_draws, it->h_draws, sizeof(WsDraw) * max_spheres, hipMemcpyHostToDevice, st));
+    if (it->h_colour_keep)
+        WS_HIP(hipMemcpyAsync(ws->d_keep, it->h_colour_keep, sizeof(int32_t) * max_spheres, hipMemcpyHostToDevice, st));
     WsArgs a;
     a.clouds = ws->d_clouds;
     a.nc = (int)ws->clouds.size();
     a.min_pot = ws->d_min;
     a.argmin = ws->d_arg;
     a.draws = ws->d_draws;
-    a.st = (WsState*)d_state;
+    a.st = (WsState*)it->d_state;
     a.pv = ws->d_pv;
     a.pi = ws->d_pi;
     a.counts = ws->d_counts;
     a.gp = (int)ws_ceil_div(ws->pmax, 256);
     if (a.gp > WS_SAMPLER_GP) a.gp = WS_SAMPLER_GP;
+    if (it->random_centres) a.gp = 0;                      // no workgroup over the potential points
     a.gn = (int)ws_ceil_div(ws->nmax, 256);
     if (a.gn > WS_SAMPLER_GN) a.gn = WS_SAMPLER_GN;
-    a.r2 = in_radius * in_radius;
+    a.r2 = it->in_radius * it->in_radius;
     a.max_slots = max_spheres;
-    a.batch_limit = batch_limit;
-    a.capacity = capacity_rows;
-    a.aug_noise = augment_noise;
-    a.seed = seed;
-    a.seq0 = seq0;
+    a.batch_limit = it->batch_limit;
+    a.capacity = it->capacity_rows;
+    a.aug_noise = it->augment_noise;
+    a.seed = it->seed;
+    a.seq0 = it->seq0;
     a.fd = fd;
-    a.lut = label_lut;
-    a.lut_n = lut_n;
-    a.labels_zero = labels_zero;
-    a.update_pot = update_potentials;
-    a.out_points = out_points;
-    a.out_features = out_features;
-    a.out_labels = (long long*)out_labels;
-    a.out_inds = (long long*)out_input_inds;
-    a.out_lengths = out_lengths;
-    a.out_scales = out_scales;
-    a.out_rots = out_rots;
-    a.out_cloud_inds = out_cloud_inds;
-    a.out_point_inds = out_point_inds;
-    sampler_init_kernel<<<1, 256, 0, st>>>(a.st, resume);
+    a.lut = it->label_lut;
+    a.lut_n = it->lut_n;
+    a.labels_zero = it->labels_zero;
+    a.update_pot = it->random_centres ? 0 : it->update_potentials;
+    a.out_points = it->out_points;
+    a.out_features = it->out_features;
+    a.out_labels = (long long*)it->out_labels;
+    a.out_inds = (long long*)it->out_input_inds;
+    a.out_lengths = it->out_lengths;
+    a.out_scales = it->out_scales;
+    a.out_rots = it->out_rots;
+    a.out_cloud_inds = it->out_cloud_inds;
+    a.out_point_inds = it->out_point_inds;
+    a.keep = it->h_colour_keep ? ws->d_keep : nullptr;
+    a.ncol = (int)ncol;
+    a.random = it->random_centres ? 1 : 0;
+    a.epoch_inds = (const long long*)it->epoch_inds;
+    a.n_centres = it->n_centres;
+    a.epoch_i = (long long*)it->epoch_i;
+    sampler_init_kernel<<<1, 256, 0, st>>>(a.st, it->resume);
     WS_LAUNCH_CHECK();
     for (int k = 0; k < max_spheres; ++k) {
         sphere_scan_kernel<<<a.gp + a.gn, 256, 0, st>>>(a);
@@ -483,4 +659,85 @@ int ws_sampler_batch(ws_sampler* ws, const void* h_draws, int32_t max_spheres, i
     return WS_OK;
 }
 
+int ws_sampler_batch(ws_sampler* ws, const void* h_draws, int32_t max_spheres, int32_t resume, int64_t batch_limit, double in_radius,
+                     float augment_noise, uint64_t seed, uint64_t seq0, int32_t fd, const int32_t* label_lut, int32_t lut_n,
+                     int32_t labels_zero, int32_t update_potentials, float* out_points, float* out_features, int64_t* out_labels,
+                     int64_t* out_input_inds, int32_t* out_lengths, float* out_scales, float* out_rots, int32_t* out_cloud_inds,
+                     int32_t* out_point_inds, int64_t capacity_rows, void* d_state, void* stream)
+{
+    ws_sampler_items it = {};                              // no colour flags, centres from the potentials
+    it.h_draws = h_draws;
+    it.max_spheres = max_spheres;
+    it.resume = resume;
+    it.batch_limit = batch_limit;
+    it.in_radius = in_radius;
+    it.augment_noise = augment_noise;
+    it.seed = seed;
+    it.seq0 = seq0;
+    it.fd = fd;
+    it.label_lut = label_lut;
+    it.lut_n = lut_n;
+    it.labels_zero = labels_zero;
+    it.update_potentials = update_potentials;
+    it.out_points = out_points;
+    it.out_features = out_features;
+    it.out_labels = out_labels;
+    it.out_input_inds = out_input_inds;
+    it.out_lengths = out_lengths;
+    it.out_scales = out_scales;
+    it.out_rots = out_rots;
+    it.out_cloud_inds = out_cloud_inds;
+    it.out_point_inds = out_point_inds;
+    it.capacity_rows = capacity_rows;
+    it.d_state = d_state;
+    it.stream = stream;
+    return ws_sampler_batch_items(ws, &it);
+}
+
+/* the class-balanced centre draw, device half: see include/weasal_hip.h */
+int ws_sampler_class_counts(ws_sampler* ws, const int32_t* values, int32_t n_class, int64_t* out_counts, void* stream)
+{
+    WS_REQUIRE(ws && values && out_counts, "NULL argument");
+    WS_REQUIRE(!ws->clouds.empty(), "no cloud was added");
+    WS_REQUIRE(n_class >= 1 && n_class <= WS_SAMPLER_MAX_CLASSES, "n_class=%d outside [1, %d]", n_class, WS_SAMPLER_MAX_CLASSES);
+    for (const WsCloud& c : ws->clouds) WS_REQUIRE(c.labels, "the centre draw needs the labels of every cloud");
+    const int nc = (int)ws->clouds.size();
+    int gn = (int)ws_ceil_div(ws->nmax, 256);
+    if (gn > WS_SAMPLER_GN) gn = WS_SAMPLER_GN;
+    const size_t need = sizeof(int) * (size_t)nc * n_class * gn;
+    if (need > ws->class_bytes) {
+        WS_HIP(hipStreamSynchronize((hipStream_t)stream));
+        (void)hipFree(ws->d_class);
+        ws->d_class = nullptr;
+        ws->class_bytes = 0;
+        WS_HIP(hipMalloc(&ws->d_class, need));
+        ws->class_bytes = need;
+    }
+    ws->class_n = n_class;
+    ws->class_gn = gn;
+    ws->class_nc = nc;
+    hipStream_t st = (hipStream_t)stream;
+    class_count_kernel<<<dim3(gn, nc), 256, 0, st>>>(ws->d_clouds, values, n_class, gn, ws->d_class);
+    WS_LAUNCH_CHECK();
+    class_scan_kernel<<<nc, 256, 0, st>>>(n_class, gn, ws->d_class, (long long*)out_counts);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+int ws_sampler_class_select(ws_sampler* ws, const int32_t* values, int32_t n_class, const int64_t* triples, int64_t n_triples,
+                            int64_t* out_points, void* stream)
+{
+    WS_REQUIRE(ws && values && triples && out_points, "NULL argument");
+    WS_REQUIRE(n_triples >= 1 && n_triples < 2147483647ll, "bad n_triples=%lld", (long long)n_triples);
+    WS_REQUIRE(ws->d_class && ws->class_n == n_class && ws->class_nc == (int)ws->clouds.size(),
+               "ws_sampler_class_select needs the ws_sampler_class_counts of the same classes and clouds first");
+    hipStream_t st = (hipStream_t)stream;
+    WS_HIP(hipMemsetAsync(out_points, 0xFF, sizeof(int64_t) * n_triples, st));     // -1: no such member
+    class_select_kernel<<<(unsigned)n_triples, 256, 0, st>>>(ws->d_clouds, ws->class_nc, values, n_class, ws->class_gn, ws->d_class,
+                                                             (const long long*)triples, (long long*)out_points);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
 }  // extern "C"
+

@@ -1404,6 +1404,25 @@ def region_mean(x, regions):
 # ------------------------------------------------------------------------------------------------
 # sphere sampler (datasets/DALES_PseudoLabel.py:265-518): thin binding of ws_sampler_*; the policy lives in sampler.py
 # ------------------------------------------------------------------------------------------------
+_SAMPLER_OUT = ('out_points', 'out_features', 'out_labels', 'out_input_inds', 'out_lengths', 'out_scales', 'out_rots',
+                'out_cloud_inds', 'out_point_inds')
+
+
+def _sampler_items_fields():
+    import ctypes as C
+    vp = C.c_void_p
+    return [('h_draws', vp), ('h_colour_keep', vp), ('max_spheres', C.c_int32), ('resume', C.c_int32), ('batch_limit', C.c_int64),
+            ('in_radius', C.c_double), ('augment_noise', C.c_float), ('fd', C.c_int32), ('seed', C.c_uint64), ('seq0', C.c_uint64),
+            ('label_lut', vp), ('lut_n', C.c_int32), ('labels_zero', C.c_int32), ('update_potentials', C.c_int32),
+            ('random_centres', C.c_int32), ('epoch_inds', vp), ('n_centres', C.c_int64), ('epoch_i', vp)] \
+        + [(name, vp) for name in _SAMPLER_OUT] + [('capacity_rows', C.c_int64), ('d_state', vp), ('stream', vp)]
+
+
+class SamplerItems(__import__('ctypes').Structure):
+    """mirror of `struct ws_sampler_items` (include/weasal_hip.h)"""
+    _fields_ = _sampler_items_fields()
+
+
 class SamplerHandle:
     """the library's table of resident tiles (ws_sampler).  Keeps the tensors it was given alive."""
 
@@ -1412,6 +1431,7 @@ class SamplerHandle:
         self.h = C.c_void_p()
         check(_lib.lib().ws_sampler_create(C.byref(self.h)))
         self.keep = []
+        self.keep_colors = {}
 
     def add_cloud(self, sub_points, sub_labels, pot_points, potentials):
         _need_cuda(sub_points, pot_points, potentials)
@@ -1438,11 +1458,69 @@ class SamplerHandle:
                                           0 if label_lut is None else label_lut.shape[0], int(labels_zero), int(update_potentials),
                                           *[ptr(t) for t in out], int(capacity_rows), ptr(state), current_stream()))
 
+    def add_cloud_points(self, sub_points, sub_labels):
+        """a tile of the random mode: no potential points, no potentials"""
+        _need_cuda(sub_points)
+        if sub_points.dtype != torch.float32 or not sub_points.is_contiguous():
+            raise ValueError("sub_points must be a contiguous float32 tensor")
+        if sub_labels is not None and (sub_labels.dtype != torch.int32 or not sub_labels.is_contiguous()
+                                       or sub_labels.shape[0] != sub_points.shape[0]):
+            raise ValueError("sub_labels must be a contiguous int32 tensor, one value per point")
+        check(_lib.lib().ws_sampler_add_cloud(self.h, ptr(sub_points), ptr(sub_labels), sub_points.shape[0], None, None, 0,
+                                              current_stream()))
+        self.keep.append((sub_points, sub_labels, None, None))
+
+    def set_colors(self, cloud, colors):
+        """sub_colors [N, ncol] float32 of cloud `cloud` (ws_sampler_set_colors)"""
+        _need_cuda(colors)
+        if colors.dtype != torch.float32 or not colors.is_contiguous() or colors.dim() != 2 \
+                or colors.shape[0] != self.keep[cloud][0].shape[0]:
+            raise ValueError("sub_colors must be a contiguous float32 tensor [N, ncol], one row per point")
+        check(_lib.lib().ws_sampler_set_colors(self.h, int(cloud), ptr(colors), int(colors.shape[1]), current_stream()))
+        self.keep_colors[int(cloud)] = colors
+
+    def batch_items(self, h_draws, h_colour_keep, max_spheres, resume, batch_limit, in_radius, augment_noise, seed, seq0, fd,
+                    label_lut, labels_zero, update_potentials, out, capacity_rows, state, epoch_inds=None, epoch_i=None):
+        """ws_sampler_batch_items: batch() with the colour flags of the slots (host address of int32 [max_spheres], or None)
+        and, when epoch_inds (device int64 [2, n_centres]) and epoch_i (device int64 [1]) are given, centres from that list"""
+        import ctypes as C
+        it = SamplerItems()
+        it.h_draws = h_draws
+        it.h_colour_keep = h_colour_keep
+        it.max_spheres, it.resume, it.batch_limit, it.in_radius = int(max_spheres), int(resume), int(batch_limit), float(in_radius)
+        it.augment_noise, it.fd = float(augment_noise), int(fd)
+        it.seed, it.seq0 = int(seed) & 0xFFFFFFFFFFFFFFFF, int(seq0) & 0xFFFFFFFFFFFFFFFF
+        it.label_lut = None if label_lut is None else label_lut.data_ptr()
+        it.lut_n = 0 if label_lut is None else label_lut.shape[0]
+        it.labels_zero, it.update_potentials = int(labels_zero), int(update_potentials)
+        if epoch_inds is not None:
+            if epoch_inds.dtype != torch.int64 or not epoch_inds.is_contiguous() or epoch_inds.dim() != 2 or epoch_inds.shape[0] != 2 \
+                    or epoch_i is None or epoch_i.dtype != torch.int64:
+                raise ValueError("epoch_inds must be a contiguous int64 tensor [2, n_centres], epoch_i an int64 tensor")
+            _need_cuda(epoch_inds, epoch_i)
+            it.random_centres, it.epoch_inds, it.n_centres, it.epoch_i = 1, epoch_inds.data_ptr(), epoch_inds.shape[1], epoch_i.data_ptr()
+        for name, t in zip(_SAMPLER_OUT, out):
+            setattr(it, name, t.data_ptr())
+        it.capacity_rows, it.d_state, it.stream = int(capacity_rows), state.data_ptr(), current_stream().value
+        check(_lib.lib().ws_sampler_batch_items(self.h, C.byref(it)))
+
+    def class_counts(self, values, out_counts):
+        """ws_sampler_class_counts: values int32 [n_class] -> out_counts int64 [n_clouds, n_class] (asynchronous)"""
+        _need_cuda(values, out_counts)
+        check(_lib.lib().ws_sampler_class_counts(self.h, ptr(values), values.shape[0], ptr(out_counts), current_stream()))
+
+    def class_select(self, values, triples, out_points):
+        """ws_sampler_class_select: triples int64 [T, 3] (cloud, class, position) -> out_points int64 [T] (asynchronous)"""
+        _need_cuda(values, triples, out_points)
+        check(_lib.lib().ws_sampler_class_select(self.h, ptr(values), values.shape[0], ptr(triples), triples.shape[0],
+                                                 ptr(out_points), current_stream()))
+
     def close(self):
         if self.h:
             _lib.lib().ws_sampler_destroy(self.h)
             self.h = None
             self.keep = []
+            self.keep_colors = {}
 
     def __del__(self):
         try:

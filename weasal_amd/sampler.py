@@ -16,7 +16,15 @@ Differences from the reference, all deliberate:
   * a batch is cut from at most `max_spheres` attempts (a dropped sphere, n < 2, uses one);
   * the sub-regions of the weak-label sampler (cut_regions, DALES_WeakLabel.py:424-451) are ordered by ascending anchor id,
     and `if idx.any()` (:449) drops a region that holds local row 0 alone: here row 0 is the sphere's point with the
-    smallest tile index, in the reference whatever its KD-tree returned first.
+    smallest tile index, in the reference whatever its KD-tree returned first (DESIGN.md section 14);
+  * `use_potentials=False` (`random_item`, DALES_PseudoLabel.py:520-640): the centre is a copy there too (the reference adds
+    the noise into the KD-tree's own data, :547-551), and a sphere with n < 2 is dropped and counted in `failed` as in the
+    potential mode (the reference's `random_item` has no such guard and would hand an empty cloud to the pyramid).
+
+Colours (datasets/Vaihingen3D_PseudoLabel.py:364-432, Vaihingen3D_WeakLabel.py:463-535): a cloud may come with `sub_colors`
+[N, ncol]; the feature row is [1] + the first in_features_dim - 1 columns of [colours..., absolute height, reduced height],
+and the host draws one more `rand()` per sphere slot, after the augmentation draws, for `augment_color` -- only when the
+sampler holds colours, so the host stream of a colourless sampler is what it was.
 """
 import numpy as np
 import torch
@@ -55,6 +63,64 @@ def draw_augmentation(config, rng):
     return R, scale
 
 
+def accepted_dims(ncol):
+    """the feature widths a sampler with ncol colour columns cuts (Vaihingen3D_PseudoLabel.py:424-432 for ncol = 1)"""
+    return (1, 3) if ncol == 0 else (1, 1 + ncol, 3 + ncol)
+
+
+def check_dims(fd, ncol):
+    dims = accepted_dims(ncol)
+    if fd not in dims:
+        raise ValueError('Only accepted input dimensions are %d and %d' % dims if ncol == 0 else
+                         'Only accepted input dimensions are %d, %d and %d' % dims)
+
+
+def draw_slots(config, rng, n, centre_noise=True, colours=False):
+    """-> (DRAW_DTYPE [n], colour_keep int32 [n]): per slot the centre noise (DALES_PseudoLabel.py:333; not for set 'ERF'),
+    the rotation and scales (common.py:260-302) and, when the sampler holds colours, the colour drop
+    `np.random.rand() > config.augment_color` (Vaihingen3D_PseudoLabel.py:379), in the reference's order"""
+    d = np.zeros(n, DRAW_DTYPE)
+    keep = np.ones(n, np.int32)
+    for k in range(n):
+        if centre_noise:
+            d['noise'][k] = rng.normal(scale=config.in_radius / 10, size=(1, 3))[0]
+        d['R'][k], d['scale'][k] = draw_augmentation(config, rng)
+        if colours and rng.rand() > config.augment_color:
+            keep[k] = 0
+    return d, keep
+
+
+def draw_epoch_positions(counts, n_centres, rng):
+    """The class-balanced centre draw of `*Sampler.__iter__` (DALES_PseudoLabel.py:954-985) in POSITION space.
+    counts [n_clouds, n_class]: members of every non-ignored class (in `label_values` order) per cloud; n_centres =
+    epoch steps * batch_num.  -> int64 [T, 3] rows (cloud, class, position): entry t of the epoch list is the position-th
+    point of that class in ascending index order, np.where(labels == v)[0][position].  `rng` is consumed exactly as the
+    reference consumes np.random: choice(arr, k, replace=False) and choice(len(arr), k, replace=False) permute alike, and
+    np.unique(choice(arr, k)) of an ascending arr is arr[np.unique(choice(len(arr), k))]."""
+    counts = np.asarray(counts, np.int64)
+    n_clouds, n_class = counts.shape
+    pick_n = int(np.ceil(n_centres / (n_clouds * n_class)))
+    rows = []
+    for cloud in range(n_clouds):
+        for c in range(n_class):
+            m = int(counts[cloud, c])
+            if m <= pick_n:
+                pos = np.arange(m, dtype=np.int64)
+            elif m < 50 * pick_n:
+                pos = rng.choice(m, size=pick_n, replace=False)
+            else:
+                pos = []
+                while len(pos) < pick_n:
+                    pos = np.unique(rng.choice(m, size=5 * pick_n, replace=True))
+                pos = pos[:pick_n]
+            t = np.empty((len(pos), 3), np.int64)
+            t[:, 0], t[:, 1], t[:, 2] = cloud, c, pos
+            rows.append(t)
+    rows = np.concatenate(rows, axis=0) if rows else np.zeros((0, 3), np.int64)
+    order = rng.permutation(rows.shape[0])
+    return np.ascontiguousarray(rows[order][:n_centres])
+
+
 def label_lut(label_values):
     """int32 table raw label value -> position in the sorted label values, -1 elsewhere (`label_to_idx`,
     datasets/common.py:245-250, with its exception: the uncertain pseudo label 10 stays 10)"""
@@ -71,18 +137,30 @@ class SphereSampler:
     `lengths` a host int32 array (its device copy is `lengths_dev`) -- the `source` a PyramidPrefetcher takes.
 
     clouds: [(sub_points [N,3] float32, sub_labels [N] int32 or None), ...] device tensors, what
-    cloud_cache.load_subsampled_cloud returns.  set: 'training' / 'validation' (labels through label_values), 'test' (zero
-    labels), 'ERF' (zero labels, no centre noise, potentials not updated: DALES_PseudoLabel.py:241-244, :332, :344).
+    cloud_cache.load_subsampled_cloud returns; an entry of length 3 adds sub_colors [N, ncol] float32, 1 <= ncol <= 3
+    (Vaihingen3D: one column, intensity / 255), and every entry must then have them.  use_potentials=False: centres from
+    `epoch_inds` (draw_epoch_centres(), once per epoch) instead of the potentials, no potential points are built.
+    set: 'training' / 'validation' (labels through label_values), 'test' (zero labels), 'ERF' (zero labels, no centre
+    noise, potentials not updated: DALES_PseudoLabel.py:241-244, :332, :344).
     `batch_limit` is an attribute (calibration.BatchLimitController drives it; the reference starts at 1, :202).
     Data parallelism: one sampler per rank with seed = base + rank."""
 
     def __init__(self, config, clouds, set='training', label_values=None, ignored_labels=(), seed=None, max_spheres=None,
-                 device=None, batch_limit=1.0):
-        if config.in_features_dim not in (1, 3):
-            raise ValueError('Only accepted input dimensions are 1 and 3')
+                 device=None, batch_limit=1.0, use_potentials=True):
         if not clouds:
             raise ValueError("SphereSampler needs at least one cloud")
+        ncols = {0 if len(c) < 3 or c[2] is None else int(c[2].shape[1]) for c in clouds}
+        if len(ncols) != 1:
+            raise ValueError("every cloud needs the same number of colour columns")
+        self.ncol = ncols.pop()
+        check_dims(config.in_features_dim, self.ncol)
         self.config = config
+        self.use_potentials = bool(use_potentials)
+        self.label_values = None if label_values is None else np.asarray(label_values, np.int64)
+        self.epoch_inds = None            # [2, n_centres] device int64: draw_epoch_centres()
+        self.epoch_i = None               # device int64 [1], advanced by the chain
+        self._epoch_sync_count = 0        # blocking device-to-host reads made by draw_epoch_centres()
+        self.through_items = False        # queue a colourless potential batch through ws_sampler_batch_items as well
         self.set = set
         self.device = device if device is not None else clouds[0][0].device
         self.rng = np.random.RandomState(seed) if seed is not None else np.random
@@ -99,16 +177,25 @@ class SphereSampler:
         self._state_bytes = int(lib.ws_sampler_state_bytes())
         assert int(lib.ws_sampler_draw_bytes()) == DRAW_DTYPE.itemsize
         self.handle = ops.SamplerHandle()
-        self.sub_points, self.sub_labels, self.pot_points, self.potentials = [], [], [], []
-        for pts, lab in clouds:
+        self.sub_points, self.sub_labels, self.pot_points, self.potentials, self.sub_colors = [], [], [], [], []
+        for cloud in clouds:
+            pts, lab = cloud[0], cloud[1]
             pts = ops._f32c(pts)
             lab = None if lab is None else lab.detach().to(torch.int32).reshape(-1).contiguous()
             if lab is None and not self.labels_zero:
                 raise ValueError("set '%s' needs the labels of every cloud" % set)
-            pot_pts = coarse_potential_points(pts, config.in_radius).contiguous()
-            pot = torch.from_numpy(self.rng.rand(pot_pts.shape[0]) * 1e-3).to(self.device)      # :211
-            self.handle.add_cloud(pts, lab, pot_pts, pot)
-            self.sub_points.append(pts); self.sub_labels.append(lab); self.pot_points.append(pot_pts); self.potentials.append(pot)
+            if self.use_potentials:
+                pot_pts = coarse_potential_points(pts, config.in_radius).contiguous()
+                pot = torch.from_numpy(self.rng.rand(pot_pts.shape[0]) * 1e-3).to(self.device)      # :211
+                self.handle.add_cloud(pts, lab, pot_pts, pot)
+                self.pot_points.append(pot_pts); self.potentials.append(pot)
+            else:                                       # random_item reads no potential (:520-640)
+                self.handle.add_cloud_points(pts, lab)
+            self.sub_points.append(pts); self.sub_labels.append(lab)
+            if self.ncol:
+                col = ops._f32c(cloud[2])
+                self.handle.set_colors(len(self.sub_points) - 1, col)
+                self.sub_colors.append(col)
         self.noise_seed = int(seed) if seed is not None else int(self.rng.randint(2 ** 31 - 1))
         self.seq = 0                      # sphere sequence number of the next slot
         self.failed = 0                   # dropped spheres so far
@@ -119,29 +206,74 @@ class SphereSampler:
         self._last_batch = None
         self._max_n = 0
         self._h_draws = torch.empty(MAX_SPHERES * DRAW_DTYPE.itemsize, dtype=torch.uint8, pin_memory=True)
+        self._h_keep = torch.ones(MAX_SPHERES, dtype=torch.int32, pin_memory=True)     # the colour flags travel next to the draws
 
     # -----------------------------------------------------------------------------------------------------------
     def draw(self, n=None):
         """the host-drawn values of n sphere slots (centre noise :333, rotation and scales common.py:260-302), in the
-        order the reference consumes its stream for one sphere after the other"""
+        order the reference consumes its stream for one sphere after the other: a DRAW_DTYPE array; for a sampler with
+        colours a dict of its three fields plus 'colour_keep' [n] (one more rand() per slot, Vaihingen3D_PseudoLabel.py:379)"""
         n = self.max_spheres if n is None else n
-        d = np.zeros(n, DRAW_DTYPE)
-        for k in range(n):
-            if self.set != 'ERF':
-                d['noise'][k] = self.rng.normal(scale=self.config.in_radius / 10, size=(1, 3))[0]
-            d['R'][k], d['scale'][k] = draw_augmentation(self.config, self.rng)
-        return d
+        d, keep = draw_slots(self.config, self.rng, n, centre_noise=self.set != 'ERF', colours=self.ncol > 0)
+        if not self.ncol:
+            return d
+        return {'noise': d['noise'], 'R': d['R'], 'scale': d['scale'], 'colour_keep': keep}    # what sample(draws=) takes
 
     def set_potentials(self, values):
         """replace the potentials of every cloud (float64 arrays) and recompute the per-cloud (min, arg-min) pairs: a
         restart from saved potentials"""
+        if not self.use_potentials:
+            raise ValueError("a sampler with use_potentials=False holds no potentials")
         torch.cuda.current_stream(self.device).synchronize()
         for p, v in zip(self.potentials, values):
             p.copy_(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)))
         self.handle.close()
         self.handle = ops.SamplerHandle()
-        for args in zip(self.sub_points, self.sub_labels, self.pot_points, self.potentials):
+        for i, args in enumerate(zip(self.sub_points, self.sub_labels, self.pot_points, self.potentials)):
             self.handle.add_cloud(*args)
+            if self.ncol:
+                self.handle.set_colors(i, self.sub_colors[i])
+
+    def set_epoch_inds(self, epoch_inds):
+        """the centres of the random mode, rows (cloud, point index into that cloud's sub-points), [2, n_centres]; resets
+        epoch_i (DALES_PseudoLabel.py:950-951, :988)"""
+        e = torch.as_tensor(epoch_inds, dtype=torch.int64).to(self.device).contiguous()
+        if e.dim() != 2 or e.shape[0] != 2 or e.shape[1] < 1:
+            raise ValueError("epoch_inds must be [2, n_centres >= 1]")
+        self.epoch_inds = e
+        self.epoch_i = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def draw_epoch_centres(self, n_steps=None):
+        """The class-balanced centre draw of `*Sampler.__iter__` (DALES_PseudoLabel.py:941-992): fills `epoch_inds` with
+        n_steps * batch_num centres (n_steps: config.epoch_steps for 'training', else config.validation_size) and resets
+        epoch_i; call it at the start of every epoch.  The labels are read where they live: the device counts every
+        non-ignored class per cloud (the ONE blocking read, counted in `_epoch_sync_count`), the host draws positions from
+        the counts with the sampler's stream (draw_epoch_positions), the device turns (cloud, class, position) into point
+        indices.  -> epoch_inds"""
+        if self.label_values is None or any(l is None for l in self.sub_labels):
+            raise ValueError("draw_epoch_centres needs label_values and the labels of every cloud")
+        if n_steps is None:
+            n_steps = self.config.epoch_steps if self.set == 'training' else self.config.validation_size
+        n_centres = int(n_steps) * int(self.config.batch_num)
+        values = np.array([v for v in self.label_values if v not in self.ignored_labels], np.int32)
+        if n_centres < 1 or len(values) < 1:
+            raise ValueError("draw_epoch_centres needs n_steps * batch_num >= 1 and one class that is not ignored")
+        d_values = torch.from_numpy(values).to(self.device)
+        d_counts = torch.empty((len(self.sub_points), len(values)), dtype=torch.int64, device=self.device)
+        self.handle.class_counts(d_values, d_counts)
+        self._epoch_sync_count += 1
+        counts = d_counts.cpu().numpy()
+        triples = draw_epoch_positions(counts, n_centres, self.rng)
+        if triples.shape[0] < 1:
+            raise ValueError("no point of any cloud carries a class that is not ignored")
+        d_triples = torch.from_numpy(triples).to(self.device)
+        inds = torch.empty((2, triples.shape[0]), dtype=torch.int64, device=self.device)
+        inds[0].copy_(d_triples[:, 0])
+        self.handle.class_select(d_values, d_triples, inds[1])
+        self.epoch_inds = inds
+        self.epoch_i = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.last_class_counts = counts
+        return inds
 
     def reveal_labels(self, cloud, ids, truth_labels):
         """Give the points `ids` of tile `cloud` their true label (datasets/Vaihingen3D_PseudoLabel.py:775:
@@ -183,21 +315,28 @@ class SphereSampler:
         cfg = self.config
         S = self.max_spheres
         fd = int(cfg.in_features_dim)
-        if fd not in (1, 3):
-            raise ValueError('Only accepted input dimensions are 1 and 3')
+        check_dims(fd, self.ncol)
+        if not self.use_potentials and self.epoch_inds is None:
+            raise ValueError("use_potentials=False needs draw_epoch_centres() (or epoch_inds) before the first batch")
         injected = draws is not None
         fails = 0
         while True:
             d = self.draw(S) if draws is None else draws
+            keep = None
             if isinstance(d, dict):
                 dd = np.zeros(S, DRAW_DTYPE)
                 for key in ('noise', 'R', 'scale'):
                     dd[key] = np.asarray(d[key])[:S]
+                if d.get('colour_keep') is not None:
+                    keep = np.asarray(d['colour_keep'])[:S]
+                    if keep.shape != (S,):
+                        raise ValueError("'colour_keep' must hold max_spheres = %d flags" % S)
                 d = dd
             if d.dtype != DRAW_DTYPE or d.shape[0] < S:
                 raise ValueError("draws must hold max_spheres = %d records of sampler.DRAW_DTYPE" % S)
             host = self._h_draws.numpy().view(DRAW_DTYPE)
             host[:S] = d[:S]
+            self._h_keep.numpy()[:S] = 1 if keep is None else (keep != 0)
             out = self._chain(host, S, fd, capacity_rows, cfg.augment_noise if augment_noise is None else augment_noise)
             if out is not None:
                 return out
@@ -221,9 +360,15 @@ class SphereSampler:
                 for a, b in zip(new, rows):
                     a[:head['row_off']].copy_(b[:head['row_off']])
             rows = new
-            self.handle.batch(host.ctypes.data, S, resume, int(self.batch_limit), float(self.config.in_radius), augment_noise,
-                              self.noise_seed, self.seq, fd, self.lut, self.labels_zero, self.set != 'ERF',
-                              rows + per_sphere, cap, state)
+            if self.ncol or not self.use_potentials or self.through_items:
+                self.handle.batch_items(host.ctypes.data, self._h_keep.data_ptr() if self.ncol else None, S, resume,
+                                        int(self.batch_limit), float(self.config.in_radius), augment_noise, self.noise_seed, self.seq,
+                                        fd, self.lut, self.labels_zero, self.set != 'ERF', rows + per_sphere, cap, state,
+                                        None if self.use_potentials else self.epoch_inds, self.epoch_i)
+            else:
+                self.handle.batch(host.ctypes.data, S, resume, int(self.batch_limit), float(self.config.in_radius), augment_noise,
+                                  self.noise_seed, self.seq, fd, self.lut, self.labels_zero, self.set != 'ERF',
+                                  rows + per_sphere, cap, state)
             head, slots = self._read_state(state)
             if not head['overflow']:
                 break

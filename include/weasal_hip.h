@@ -313,7 +313,8 @@ int ws_kpconv_gather_bwd_x_grid_gated(const float* s_pts, int64_t ns, const void
  * Per batch element: origin = floor(min*(1/dl))*dl, cell key = iX + nX*iY + nX*nY*iZ (all f32,
  * IEEE divide), per cell the SEQUENTIAL f32 sum of its points in input order times
  * (float)(1.0/count); features: sequential sum / (float)count; labels: arg-max of the per-cell
- * histogram (first-seen label wins ties -- the reference's tie order is implementation-defined).
+ * histogram, the first maximum in the iteration order of the reference's libstdc++
+ * unordered_map<int,int> (replayed for any number of distinct labels in a cell).
  * order_mode WS_ORDER_REFERENCE reproduces the reference's row order (the iteration order of a
  * libstdc++ unordered_map filled in first-occurrence order); WS_ORDER_FIRST_SEEN orders cells by
  * first occurrence (cheaper; same set of rows).

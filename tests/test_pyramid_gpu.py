@@ -392,6 +392,22 @@ def test_one_call_pyramid_equals_the_per_call_loop():
     """ws_pyramid_build (one library call per batch) against the per-call loop of pyramid.segmentation_inputs on the same
     inputs and the same np.random stream: points, index matrices, lengths, cell orders, search grids and transposed tables
     bit-identical; also after a deliberately tiny arena (the WS_ERR_CAPACITY round trip)"""
+    import ctypes as C
+    from weasal_amd import _lib
+    # All three builds run with the full 1024-entry slab of the asynchronous search.  With the width-sized slab the first
+    # build (the per-call loop) overflows at one level, drops that level's grid and widens the slabs for the process
+    # (ops.widen_async_slabs), so the other two would be built in another state: the outcome then depended on whether an
+    # earlier test of the same process had already widened them.
+    flag = C.c_int.in_dll(_lib.lib(), "ws_nb_wide_caps")
+    saved = flag.value
+    flag.value = 0
+    try:
+        _one_call_pyramid_equals_the_per_call_loop()
+    finally:
+        flag.value = saved
+
+
+def _one_call_pyramid_equals_the_per_call_loop():
     from weasal_amd import config as wcfg, pyramid, synthetic
     dev = torch.device("cuda:0")
     for name, cfgn in (("vaihingen", "Vaihingen3DPLConfig"), ("dales_deform", "DALESDeformConfig")):

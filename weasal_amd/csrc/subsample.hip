@@ -8,7 +8,11 @@
 //   1. min/max reduction -> origin = floor(min * (1/dl)) * dl, nX, nY            (:25-31)
 //   2. cell key per point, IEEE f32 divide + floor                               (:53-56)
 //   3. keys are inserted into an open-addressing hash table in HBM (64-bit CAS); per slot the
-//      point count and the smallest point index (= first occurrence) are kept with atomics
+//      point count and the smallest point index (= first occurrence) are kept with atomics.
+//      The key 2^64-1 is the table's empty marker and a key the reference can produce (origin
+//      above the minimum: iX = (size_t)-1, iY = iZ = 0): every element has a slot of its own
+//      for it behind all the tables, whose key word is never written and so already reads as
+//      that key
 //   4. cells are ranked by first occurrence (mark + prefix sum) and the point lists of the
 //      cells are built by a counting sort and sorted by point index, so that
 //   5. the per-cell sums run SEQUENTIALLY in input order -- bit-identical to the reference's
@@ -92,7 +96,7 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long k)
 
 __global__ __launch_bounds__(256) void sub_insert_kernel(const float* __restrict__ pts, int64_t n,
                                                           const SubCloud* __restrict__ clouds, int nb, float dl,
-                                                          unsigned long long* __restrict__ tab_key,
+                                                          int tab_slots, unsigned long long* __restrict__ tab_key,
                                                           int32_t* __restrict__ tab_cnt, int32_t* __restrict__ tab_first,
                                                           int32_t* __restrict__ slot_of)
 {
@@ -104,8 +108,14 @@ __global__ __launch_bounds__(256) void sub_insert_kernel(const float* __restrict
         const unsigned long long iX = (unsigned long long)(long long)floorf(__fdiv_rn(p[0] - g.org[0], dl));
         const unsigned long long iY = (unsigned long long)(long long)floorf(__fdiv_rn(p[1] - g.org[1], dl));
         const unsigned long long iZ = (unsigned long long)(long long)floorf(__fdiv_rn(p[2] - g.org[2], dl));
-        unsigned long long key = iX + g.nX * iY + g.nX * g.nY * iZ;           // :56
-        if (key == EMPTY_KEY) key = EMPTY_KEY - 1;                            // reserved value
+        const unsigned long long key = iX + g.nX * iY + g.nX * g.nY * iZ;     // :56
+        if (key == EMPTY_KEY) {                                               // the marker itself: slot tab_slots + b, no probing
+            const int slot = tab_slots + b;
+            atomicAdd(&tab_cnt[slot], 1);
+            atomicMin(&tab_first[slot], (int)i);
+            slot_of[i] = slot;
+            continue;
+        }
         unsigned h = (unsigned)mix64(key) & (unsigned)g.tab_mask;
         for (;;) {
             const int slot = g.tab_base + (int)h;
@@ -348,27 +358,28 @@ __global__ __launch_bounds__(256) void sub_emit_features_kernel(const float* __r
 
 // Label of a cell = first maximum of an unordered_map<int,int> histogram in iteration order
 // (grid_subsampling.cpp:99-101).  The histogram's iteration order follows the same libstdc++
-// insertion rule as the cell map; it is replayed here for up to MAXL distinct labels per cell
-// (bucket count 13, then 29, 59, ... on growth); beyond that the first-seen label among the
-// maxima is used.
+// insertion rule as the cell map (bucket count 13, then 29, 59, ... on growth) and is replayed by
+// label_argmax for any number of distinct labels.  Up to MAXL distinct labels per cell the
+// histogram and the replay live in the thread's registers / private memory.  A cell with more
+// starts over on its own stretch of lab_scratch in global memory (5 ints per point and label
+// column: labs, cnts, order, tmp, actv, each as long as the cell's point list, which bounds the
+// number of distinct labels): slow, simple and rare, with the same result rule.
 constexpr int MAXL = 48;
-__device__ int label_argmax(const int* labs, const int* cnts, int nl, const unsigned long long* primes)
+// labs/cnts: the histogram in first-seen order; order, tmp, actv: nl ints of working storage each
+__device__ __forceinline__ int label_argmax(const int* labs, const int* cnts, int nl, int* order, int* tmp, int* actv,
+                                            const unsigned long long* primes)
 {
     // order[] = current list order (indices into labs)
-    int order[MAXL], tmp[MAXL], actv[MAXL];
     int nprev = 0;
     for (int j = 0; nprev < nl; ++j) {
         const unsigned long long B = primes[j];
         const int n = (unsigned long long)nl < B ? nl : (int)B;
-        // sequence S = order[0..nprev) ++ nprev..n-1 ; bucket of element
-        int seq[MAXL];
-        for (int i = 0; i < n; ++i) seq[i] = i < nprev ? order[i] : i;
-        // activation time of each element's bucket
+        // sequence S = order[0..nprev) ++ nprev..n-1 ; activation time of each element's bucket
         for (int i = 0; i < n; ++i) {
-            const unsigned long long bi = (unsigned long long)(long long)labs[seq[i]] % B;
+            const unsigned long long bi = (unsigned long long)(long long)labs[i < nprev ? order[i] : i] % B;
             int a = i;
             for (int i2 = 0; i2 < i; ++i2)
-                if ((unsigned long long)(long long)labs[seq[i2]] % B == bi) { a = i2; break; }
+                if ((unsigned long long)(long long)labs[i2 < nprev ? order[i2] : i2] % B == bi) { a = i2; break; }
             actv[i] = a;
         }
         // final position: sort by (activation desc, i desc)
@@ -376,7 +387,7 @@ __device__ int label_argmax(const int* labs, const int* cnts, int nl, const unsi
             int pos = 0;
             for (int i2 = 0; i2 < n; ++i2)
                 if (actv[i2] > actv[i] || (actv[i2] == actv[i] && i2 > i)) ++pos;
-            tmp[pos] = seq[i];
+            tmp[pos] = i < nprev ? order[i] : i;
         }
         for (int i = 0; i < n; ++i) order[i] = tmp[i];
         nprev = n;
@@ -387,11 +398,12 @@ __device__ int label_argmax(const int* labs, const int* cnts, int nl, const unsi
     return labs[best];
 }
 
-__global__ __launch_bounds__(64) void sub_emit_labels_kernel(const int32_t* __restrict__ labels, int ld,
+__global__ __launch_bounds__(64) void sub_emit_labels_kernel(const int32_t* __restrict__ labels, int ld, int64_t n_points,
                                                               const SubCloud* __restrict__ clouds, int nb, int M,
                                                               const int32_t* __restrict__ cell_off, const int32_t* __restrict__ list,
                                                               const int32_t* __restrict__ out_pos,
                                                               const unsigned long long* __restrict__ primes,
+                                                              int32_t* lab_scratch /*[5 * n_points * ld]*/,
                                                               int32_t* __restrict__ out_l)
 {
     const int64_t total = (int64_t)M * ld;
@@ -411,15 +423,27 @@ __global__ __launch_bounds__(64) void sub_emit_labels_kernel(const int32_t* __re
             for (int a = 0; a < nl; ++a) if (labs[a] == v) { f = a; break; }
             if (f >= 0) cnts[f]++;
             else if (nl < MAXL) { labs[nl] = v; cnts[nl] = 1; ++nl; }
-            else overflow = true;
+            else { overflow = true; break; }
         }
         int res;
         if (overflow) {
-            int best = 0;
-            for (int a = 1; a < nl; ++a) if (cnts[a] > cnts[best]) best = a;
-            res = labs[best];
+            // more than MAXL distinct labels: the whole histogram again, in this (cell, column)'s stretch of the scratch.
+            // The stretches of different cells and columns are disjoint: [5 (k n + beg), 5 (k n + end)).
+            const int len = end - beg;
+            int* glabs = lab_scratch + 5 * ((int64_t)k * n_points + beg);
+            int* gcnts = glabs + len;
+            nl = 0;
+            for (int p = beg; p < end; ++p) {
+                const int v = labels[(int64_t)list[p] * ld + k];
+                int f = -1;
+                for (int a = 0; a < nl; ++a) if (glabs[a] == v) { f = a; break; }
+                if (f >= 0) gcnts[f]++;
+                else { glabs[nl] = v; gcnts[nl] = 1; ++nl; }      // nl <= len
+            }
+            res = label_argmax(glabs, gcnts, nl, gcnts + len, gcnts + 2 * len, gcnts + 3 * len, primes);
         } else {
-            res = label_argmax(labs, cnts, nl, primes);
+            int order[MAXL], tmp[MAXL], actv[MAXL];
+            res = label_argmax(labs, cnts, nl, order, tmp, actv, primes);
         }
         out_l[(int64_t)(g.out_base + pos) * ld + k] = res;
     }
@@ -517,7 +541,7 @@ struct ws_subsample_ws {
     DevBuf<SubCloud> clouds;
     DevBuf<unsigned long long> tab_key, cell_key, primes;
     DevBuf<int32_t> tab_cnt, tab_first, slot_of, flag, first_slot, slot_rank, cell_cnt, cell_off, cursor, list,
-        out_pos, scan_scratch, ord_scratch;
+        out_pos, scan_scratch, ord_scratch, lab_scratch;
     std::vector<SubCloud> h_clouds;
     const float* points = nullptr;
     int64_t n = 0, m_total = 0, m_out = 0;
@@ -541,7 +565,7 @@ void ws_subsample_ws_destroy(ws_subsample_ws* w)
     w->tab_cnt.release(); w->tab_first.release(); w->slot_of.release(); w->flag.release();
     w->first_slot.release(); w->slot_rank.release(); w->cell_cnt.release(); w->cell_off.release();
     w->cursor.release(); w->list.release(); w->out_pos.release(); w->scan_scratch.release();
-    w->ord_scratch.release();
+    w->ord_scratch.release(); w->lab_scratch.release();
     delete w;
 }
 
@@ -577,6 +601,8 @@ int ws_grid_subsample_plan(ws_subsample_ws* w, const float* points, int64_t n, c
         h_out_lens[b] = 0;
     }
     WS_REQUIRE(sum == n, "batch lengths sum to %lld, expected %lld", (long long)sum, (long long)n);
+    const int64_t tab_slots = tab;   // the hash tables; behind them one slot per element for the key EMPTY_KEY
+    tab += nb;
     WS_REQUIRE(tab < (1ll << 31) && ord < (1ll << 31), "workspace exceeds int32 indexing");
     if (n == 0) return ws_fail(WS_ERR_EMPTY, "Error");      // wrapper.cpp:266-270
     WS_REQUIRE(points, "NULL argument");
@@ -610,7 +636,7 @@ int ws_grid_subsample_plan(ws_subsample_ws* w, const float* points, int64_t n, c
 
     sub_bbox_kernel<<<nb, 1024, 0, st>>>(points, w->clouds.p);
     WS_LAUNCH_CHECK();
-    sub_insert_kernel<<<ws_grid(n, 256), 256, 0, st>>>(points, n, w->clouds.p, nb, dl, w->tab_key.p, w->tab_cnt.p,
+    sub_insert_kernel<<<ws_grid(n, 256), 256, 0, st>>>(points, n, w->clouds.p, nb, dl, (int)tab_slots, w->tab_key.p, w->tab_cnt.p,
                                                        w->tab_first.p, w->slot_of.p);
     WS_LAUNCH_CHECK();
     sub_mark_kernel<<<ws_grid(tab, 256), 256, 0, st>>>(tab, w->tab_cnt.p, w->tab_first.p, w->flag.p, w->first_slot.p);
@@ -672,8 +698,12 @@ int ws_grid_subsample_fill(ws_subsample_ws* w, const float* features, int32_t fd
         WS_LAUNCH_CHECK();
     }
     if (labels) {
-        sub_emit_labels_kernel<<<ws_grid((int64_t)M * ld, 64), 64, 0, st>>>(labels, ld, w->clouds.p, w->nb, M, w->cell_off.p,
-                                                                            w->list.p, w->out_pos.p, w->primes.p, out_labels);
+        // storage for cells with more than MAXL distinct labels (see sub_emit_labels_kernel); grows with the first such call
+        int rc = w->lab_scratch.ensure((size_t)5 * (size_t)w->n * (size_t)ld);
+        if (rc) return rc;
+        sub_emit_labels_kernel<<<ws_grid((int64_t)M * ld, 64), 64, 0, st>>>(labels, ld, w->n, w->clouds.p, w->nb, M, w->cell_off.p,
+                                                                            w->list.p, w->out_pos.p, w->primes.p,
+                                                                            w->lab_scratch.p, out_labels);
         WS_LAUNCH_CHECK();
     }
     return WS_OK;

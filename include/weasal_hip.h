@@ -143,6 +143,18 @@ int ws_closest_pool_fwd(const float* x, int64_t ns, int32_t c, const int64_t* in
 int ws_closest_pool_bwd(const float* dy, int64_t nq, int32_t h, int32_t c,
                         const int32_t* t_offsets, const int32_t* t_pairs, int64_t ns,
                         float* dx, void* stream);
+/* the launch a pooling entry makes for these arguments (the launchers' own plan functions; pointers are only tested for
+ * alignment, nothing is read or launched), as a name into out[cap]: "max_fwd vec G=32 U=4 AT=i32 f32 split=1 interleaved"
+ * (G lanes per row, U neighbour rows in flight, the arg-max record's element, the row type, channel chunks per row, the
+ * work assignment), "max_bwd generic bf16", "closest_fwd scalar f32", "closest_bwd vec G=16".  op names the entry family
+ * (its _bf16 / _ordered forms included: rows_bf16 = 1 for bf16 rows, ordered = 1 when an order is passed); rows = nq for
+ * the forwards, ns for the backwards; rows_a, rows_b: x and out, or dy and dx; arg: the arg-max record (the closest pools
+ * ignore it), arg_bytes 4, or 1 for the byte record the fused blocks keep (f32 rows, c % 4 == 0, 16-byte aligned rows:
+ * refused otherwise).  grid, when not NULL, receives the workgroups of the launch.  The closest backward follows
+ * ws_closest_bwd_vec. */
+enum { WS_POOL_MAX_FWD = 0, WS_POOL_MAX_BWD = 1, WS_POOL_CLOSEST_FWD = 2, WS_POOL_CLOSEST_BWD = 3 };
+int ws_pool_variant(int32_t op, int64_t rows, int32_t c, const void* rows_a, const void* rows_b, const void* arg, int32_t rows_bf16,
+                    int32_t arg_bytes, int32_t ordered, char* out, int32_t cap, int32_t* grid);
 
 /* ------------------------------------------------------------------------------------------
  * Tall-skinny fp32 GEMMs on the f32-input MFMA -- the dense parts of the path:

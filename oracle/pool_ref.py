@@ -156,46 +156,3 @@ def transposed_table_ref(inds, ns):
     offsets[1:] = np.cumsum(counts)
     pairs = ids[np.argsort(s, kind="stable")]                # ids ascend, the sort is stable: every list ascending
     return offsets, pairs.astype(np.int64)
-
-
-# ------------------------------------------------------------------------------------------------------------------
-# the launchers' if-ladders (pools.hip: max_pool_fwd_impl / _bwd_impl, the _u8 forms, closest_pool_*_impl), restated
-# ------------------------------------------------------------------------------------------------------------------
-POOL_SPLIT_ROWS = 8192
-OPS = ("max_fwd", "max_bwd", "closest_fwd", "closest_bwd")
-
-
-def pool_split(rows, c):
-    return -(-c // 256) if (rows < POOL_SPLIT_ROWS and c > 256) else 1
-
-
-def pool_plan(op, dtype, c, rows, aligned=True, ordered=False, arg_bytes=4, vec_flag=True):
-    """name of the kernel form a call takes.  op: one of OPS; dtype "f32" / "bf16"; rows = nq (forward) or ns (backward);
-    aligned: every row pointer on its vector alignment (16 bytes, bf16: 8) and the arg record on 16; ordered: a scheduling
-    order is passed; arg_bytes 4 (the C ABI) or 1 (the private byte-record forms: f32, c % 4 == 0 and aligned rows are
-    the caller's preconditions); vec_flag: ws_closest_bwd_vec"""
-    assert op in OPS and dtype in ("f32", "bf16") and arg_bytes in (1, 4)
-    if op == "closest_fwd":
-        return "closest_fwd scalar %s" % dtype
-    if op == "closest_bwd":
-        if dtype == "f32" and vec_flag and aligned and (c in (32, 64, 128) or c % 256 == 0):
-            return "closest_bwd vec G=%d" % (min(c, 256) // 4)
-        return "closest_bwd scalar %s" % dtype
-    if arg_bytes == 1:
-        assert dtype == "f32" and c % 4 == 0 and aligned
-    elif not (c % 4 == 0 and aligned):
-        return "%s generic %s" % (op, dtype)                  # one wave per row; takes no order
-    if op == "max_fwd" and c <= 16:
-        g = 4
-    elif c <= 32:
-        g = 8
-    elif c <= 64:
-        g = 16
-    elif c <= 128:
-        g = 32
-    else:
-        g = 64
-    split = pool_split(rows, c) if g == 64 else 1
-    u = 8 if (op == "max_fwd" and arg_bytes == 1 and g == 32) else 4
-    return "%s vec G=%d U=%d AT=%s %s split=%d %s" % (op, g, u, "u8" if arg_bytes == 1 else "i32", dtype, split,
-                                                      "interleaved" if ordered else "contiguous")

@@ -1,16 +1,20 @@
 """CPU side of tests/test_pool_branches_gpu.py: the references of oracle/pool_ref.py are right, the bound has teeth, and the
-case tables cover the launchers' ladders.
+case tables cover the launchers' plans.
 
 * max_pool_ref / closest_pool_ref and their float64 backwards agree with the torch restatement (oracle.kpconv_ref, autograd
   on the CPU) on tie-heavy integer data, exactly, and with the g6 golden.
 * transposed_table_ref agrees with a brute-force nonzero per support.
-* The pool_plan names of the GPU case tables cover every name a sweep of the ladders produces, and straddle each threshold.
+* Which form a call takes is asked of the library: ws_pool_variant formats the plan functions the launchers of pools.hip
+  dispatch on (no device needed).  The names it gives for the GPU case tables are every name it gives over a sweep of
+  widths, row counts, alignments, orders and records; the set is the expected one, counted here from literals; the tables
+  straddle each threshold; the grids are the literal values of the formulas.
 * The index matrices of the GPU cases hold what the cases rely on: shadow entries, an empty support, a crowded one, list
   lengths 0 ... 9.
 """
 import itertools
 
 import numpy as np
+import pytest
 import torch
 
 import test_pool_branches_gpu as PB
@@ -134,20 +138,46 @@ def test_transposed_table_ref_against_nonzero():
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# the case tables cover the ladders
+# the case tables cover the plans (ws_pool_variant: PB.variant)
 # ------------------------------------------------------------------------------------------------------------------
 SWEEP_C = (1, 4, 5, 16, 20, 30, 32, 36, 64, 68, 96, 128, 130, 132, 256, 260, 512, 1024)
 SWEEP_ROWS = (1, 8191, 8192, 20000)
 
 
 def sweep_plans():
+    """every name the reporter gives over the product; misaligned rows sit where the GPU tables' shift puts them (4 bytes
+    off for f32, 2 for bf16)"""
     plans = set()
-    for op, d, c, rows, al, o, ab, flag in itertools.product(P.OPS, ("f32", "bf16"), SWEEP_C, SWEEP_ROWS, (True, False),
-                                                             (False, True), (4, 1), (True, False)):
-        if ab == 1 and (not op.startswith("max") or d != "f32" or c % 4 or not al):
-            continue                                           # the byte forms' preconditions (their caller checks them)
-        plans.add(P.pool_plan(op, d, c, rows, al, o, ab, flag))
+    for flag in (1, 0):
+        with PB.closest_vec_switch(flag):
+            for op, d, c, rows, al, o, ab in itertools.product(PB.POOL_OPS, ("f32", "bf16"), SWEEP_C, SWEEP_ROWS, (True, False),
+                                                               (False, True), (4, 1)):
+                if ab == 1 and (not op.startswith("max") or d != "f32" or c % 4 or not al):
+                    continue                                   # the byte forms' preconditions (their caller checks them)
+                plans.add(PB.variant(op, d, c, rows, *PB.fake_rows(d, 0 if al else 1), PB.FAKE_ARG, ab, o)[0])
     return plans
+
+
+def _field(name, key):
+    """the integer after `key` in a reporter name ('G=', 'split=')"""
+    return int(name.split(key)[1].split()[0])
+
+
+def test_reporter_refuses_what_no_entry_takes():
+    """the byte record outside its preconditions, an unknown operation, an unknown record width: refused, nothing named"""
+    from weasal_amd import _lib
+    a, b = PB.fake_rows("f32")
+    for args in (("max_fwd", "f32", 6, 10, a, b, PB.FAKE_ARG, 1), ("max_bwd", "f32", 8, 10, a + 4, b, PB.FAKE_ARG, 1),
+                 ("max_fwd", "bf16", 8, 10, a, b, PB.FAKE_ARG, 1), ("closest_fwd", "f32", 8, 10, a, b, PB.FAKE_ARG, 1),
+                 ("max_fwd", "f32", 8, 10, a, b, PB.FAKE_ARG, 2)):
+        with pytest.raises(_lib.WeasalHipError):
+            PB.variant(*args)
+    # one operand off its alignment is enough for the generic form; the forward's arg may be NULL
+    for op, d in itertools.product(("max_fwd", "max_bwd"), ("f32", "bf16")):
+        off = 2 if d == "bf16" else 4
+        for da, db, darg in ((off, 0, 0), (0, off, 0), (0, 0, 4), (0, 0, 8)):
+            assert PB.variant(op, d, 64, 100, a + da, b + db, PB.FAKE_ARG + darg)[0] == "%s generic %s" % (op, d)
+    assert PB.variant("max_fwd", "f32", 64, 100, a, b, None)[0] == "max_fwd vec G=16 U=4 AT=i32 f32 split=1 contiguous"
 
 
 def test_case_tables_cover_every_plan():
@@ -182,10 +212,24 @@ def test_tables_straddle_the_thresholds():
     cs = {r["c"] for r in PB.MAX_ROWS}
     for edge in (16, 32, 64, 128, 256):
         assert edge in cs and min(c for c in cs if c > edge and c % 4 == 0) == edge + 4
-    big = [r for r in PB.MAX_ROWS if r["sizes"][0][0] >= P.POOL_SPLIT_ROWS]
+    big = [r for r in PB.MAX_ROWS if r["sizes"][0][0] >= 8192]
     assert {r["c"] for r in big if r["c"] > 256} == {260, 512}                # unsplit G = 64, several channel trips
-    assert all(P.pool_split(r["sizes"][0][0], r["c"]) == 1 for r in big)
-    assert {P.pool_split(r["sizes"][0][0], r["c"]) for r in PB.MAX_ROWS if r["c"] > 256 and r not in big} == {2, 4}
+
+    def splits(r):
+        """split= of every max-pool launch of a row of the table, forward and backward"""
+        a, b = PB.fake_rows(r["dtype"], r["shift"])
+        return {_field(PB.variant(op, r["dtype"], r["c"], rows, a, b, PB.FAKE_ARG)[0], "split=")
+                for nq, ns, _h in r["sizes"] for op, rows in (("max_fwd", nq), ("max_bwd", ns))}
+
+    assert all(splits(r) == {1} for r in big)
+    wide = [r for r in PB.MAX_ROWS if r["c"] > 256 and r not in big]
+    assert set().union(*map(splits, wide)) == {2, 4} and all(1 not in splits(r) for r in wide)
+    # the row threshold itself: 8191 rows split, 8192 do not
+    for op in ("max_fwd", "max_bwd"):
+        assert [_field(PB.variant(op, "f32", 1024, rows, *PB.fake_rows("f32"), PB.FAKE_ARG)[0], "split=")
+                for rows in (8191, 8192)] == [4, 1]
+        assert [_field(PB.variant(op, "f32", c, 8191, *PB.fake_rows("f32"), PB.FAKE_ARG)[0], "split=")
+                for c in (256, 260, 512, 516)] == [1, 2, 2, 3]
     assert any(r["sizes"][0][0] > 4 * 4096 and r["orders"] == (None,) for r in big)      # past the grid cap, contiguous
     assert any(r["sizes"][0][0] > 8192 and "perm" in r["orders"] for r in big)           # several interleaved trips
     assert any(r["shift"] and r["c"] % 4 == 0 for r in PB.MAX_ROWS)
@@ -201,6 +245,38 @@ def test_tables_straddle_the_thresholds():
     assert {3, 8, 9, 59, 255} <= {h for c, _, _, h in u8 if c == 128} and all(nq <= 64 for _, nq, _, h in u8 if h == 255)
     assert set(PB.TABLE_LENGTHS) >= {64, 65, 2048, 2049} and {4094, 4095} <= set(PB.TABLE_NS)
     assert -(-(PB.TABLE_NS_3LEVEL + 2) // 4096) > 4095 and -(-(PB.TABLE_NS_3LEVEL + 1) // 4096) <= 4096
+
+
+def test_table_lanes_per_row_are_the_reporters():
+    """PB._g, which sizes the case tables at import time, is the library's G for every width of MAX_ROWS, forward and
+    backward (widths that are no multiple of 4 have no vector form: the reporter names the generic kernel for them)"""
+    for d, c in sorted({(r["dtype"], r["c"]) for r in PB.MAX_ROWS}):
+        for op in ("fwd", "bwd"):
+            name = PB.variant("max_" + op, d, c, 100, *PB.fake_rows(d), PB.FAKE_ARG)[0]
+            if c % 4:
+                assert name == "max_%s generic %s" % (op, d)
+            else:
+                assert _field(name, "G=") == PB._g(op, c), (name, c)
+
+
+def test_grids_are_the_literal_values():
+    """workgroups per launch, worked out by hand from the formulas: contiguous = ceil(groups / 4) capped at 4096 and rounded
+    up to whole rounds of 8 past 8; interleaved = 8 min(256, ceil(groups / 32)); groups = ceil(rows / (64 / G)) split"""
+    a, b = PB.fake_rows("f32")
+
+    def grid(op, c, rows, ordered=False, rows_a=a):
+        return PB.variant(op, "f32", c, rows, rows_a, b, PB.FAKE_ARG, ordered=ordered)[1]
+
+    for op in ("max_fwd", "max_bwd"):
+        assert (grid(op, 128, 71000, True), grid(op, 128, 71000)) == (2048, 4096)      # G = 32: 35 500 groups
+        assert (grid(op, 128, 37, True), grid(op, 128, 37)) == (8, 5)                  # 19 groups
+        assert (grid(op, 1024, 11, True), grid(op, 1024, 11)) == (16, 16)              # split 4: 44 groups
+        assert (grid(op, 5, 37), grid(op, 5, 37, True)) == (16, 16)                    # generic: a wave per row, no order
+        assert grid(op, 64, 37, True, a + 4) == 16                                     # ... on misaligned rows too
+    assert grid("max_fwd", 16, 71000, True) == 8 * 139 and grid("max_bwd", 16, 71000, True) == 2048    # G = 4 / 8: 4438 / 8875 groups
+    with PB.closest_vec_switch(1):
+        assert PB.variant("closest_bwd", "f32", 64, 37, a, b) == ("closest_bwd vec G=16", 16)
+    assert PB.variant("closest_fwd", "f32", 64, 37, a, b)[1] == 16 and PB.variant("closest_fwd", "f32", 64, 71000, a, b)[1] == 4096
 
 
 def test_case_index_matrices_hold_what_the_cases_rely_on():

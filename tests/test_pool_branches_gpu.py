@@ -15,10 +15,14 @@ Orders.  None (the plain entries), a random permutation and the identity (the _o
 bit-identical under all three, on normal data too -- the pair lists are sorted, so the sums run in the same order.  Every
 backward runs twice and must repeat its bits.
 
-The case tables below are plain data (tests/test_pool_branches_cpu.py asserts that their oracle.pool_ref.pool_plan names
-cover every form the launchers' ladders produce).
+The case tables below are plain data.  Which form a call takes is the library's own statement: ws_pool_variant formats the
+plan functions the launchers dispatch on (pools.hip: max_pool_plan, closest_fwd_plan, closest_bwd_plan).  Every launch made
+here asks it first, with the device pointers of the run, and must get a name of case_plans();
+tests/test_pool_branches_cpu.py asserts that those names are every form the plan functions produce.
 """
+import contextlib
 import ctypes as C
+import functools
 import zlib
 
 import numpy as np
@@ -37,7 +41,8 @@ DATA = ("mixed", "negative", "normal")
 
 
 def _g(op, c):
-    """lanes per row of the vectorised max-pool kernels (pools.hip: the launchers' ladders)"""
+    """lanes per row of the vectorised max-pool kernels: the case tables need it at import time, before the library is
+    loaded; tests/test_pool_branches_cpu.py holds it to the reporter's G= for every width of MAX_ROWS"""
     if op == "fwd" and c <= 16:
         return 4
     return 8 if c <= 32 else 16 if c <= 64 else 32 if c <= 128 else 64
@@ -93,25 +98,69 @@ TABLE_NS = (0, 1, 4093, 4094, 4095, 4096, 8191)              # the scan runs ove
 TABLE_NS_3LEVEL = 16777215                                    # 4097 tiles: the smallest three-level scan
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# the library's own statement of a launch: ws_pool_variant
+# ------------------------------------------------------------------------------------------------------------------
+POOL_OPS = dict(max_fwd=0, max_bwd=1, closest_fwd=2, closest_bwd=3)      # WS_POOL_* (include/weasal_hip.h)
+FAKE_ARG = 0x30000000
+
+
+def variant(op, dtype, c, rows, rows_a, rows_b, arg=None, arg_bytes=4, ordered=False):
+    """(name, grid) of the launch an entry makes; rows = nq (forwards) or ns (backwards); rows_a / rows_b / arg are
+    addresses (only their alignment counts)"""
+    buf, grid = C.create_string_buffer(128), C.c_int32(-1)
+    check(_lib.lib().ws_pool_variant(POOL_OPS[op], rows, c, rows_a, rows_b, arg, int(dtype == "bf16"), arg_bytes, int(ordered),
+                                     buf, 128, C.byref(grid)))
+    return buf.value.decode(), grid.value
+
+
+def fake_rows(dtype, shift=0):
+    """the two row addresses the GPU run sees, alignment-wise: allocations are 256-byte aligned, `shift` elements into one"""
+    off = shift * (2 if dtype == "bf16" else 4)
+    return 0x10000000 + off, 0x20000000 + off
+
+
+@contextlib.contextmanager
+def closest_vec_switch(value):
+    """ws_closest_bwd_vec set to `value`, put back afterwards"""
+    flag = C.c_int.in_dll(_lib.lib(), "ws_closest_bwd_vec")
+    keep = flag.value
+    flag.value = value
+    try:
+        yield
+    finally:
+        flag.value = keep
+
+
+@functools.lru_cache(None)
 def case_plans():
-    """the oracle.pool_ref.pool_plan name of every launch the tables above make"""
+    """the ws_pool_variant name of every launch the tables above make"""
     plans = set()
     for r in MAX_ROWS:
-        aligned = r["shift"] == 0
+        a, b = fake_rows(r["dtype"], r["shift"])
         for nq, ns, _h in r["sizes"]:
             for o in r["orders"]:
-                plans.add(P.pool_plan("max_fwd", r["dtype"], r["c"], nq, aligned, o is not None))
-                plans.add(P.pool_plan("max_bwd", r["dtype"], r["c"], ns, aligned, o is not None))
+                plans.add(variant("max_fwd", r["dtype"], r["c"], nq, a, b, FAKE_ARG, ordered=o is not None)[0])
+                plans.add(variant("max_bwd", r["dtype"], r["c"], ns, a, b, FAKE_ARG, ordered=o is not None)[0])
+    a, b = fake_rows("f32")
     for c, nq, ns, _h in U8_CASES:
         for o in (False, True):
-            plans.add(P.pool_plan("max_fwd", "f32", c, nq, True, o, arg_bytes=1))
-            plans.add(P.pool_plan("max_bwd", "f32", c, ns, True, o, arg_bytes=1))
+            plans.add(variant("max_fwd", "f32", c, nq, a, b, FAKE_ARG, 1, o)[0])
+            plans.add(variant("max_bwd", "f32", c, ns, a, b, FAKE_ARG, 1, o)[0])
     for c, d, _h in CLOSEST_FWD:
-        plans.add(P.pool_plan("closest_fwd", d, c, 1))
+        plans.add(variant("closest_fwd", d, c, 1, *fake_rows(d))[0])
     for c, d, shift, _h in CLOSEST_BWD:
-        for flag in (True, False):
-            plans.add(P.pool_plan("closest_bwd", d, c, 1, shift == 0, vec_flag=flag))
-    return plans
+        for flag in (1, 0):
+            with closest_vec_switch(flag):
+                plans.add(variant("closest_bwd", d, c, 1, *fake_rows(d, shift))[0])
+    return frozenset(plans)
+
+
+def reported(op, rows, c, a, b, arg=None, arg_bytes=4, order=None):
+    """before a launch: the reporter answers for its device pointers (status 0) with a name the case tables are known by"""
+    name, grid = variant(op, "bf16" if a.dtype == torch.bfloat16 else "f32", c, rows, ptr(a), ptr(b), ptr(arg), arg_bytes,
+                         order is not None)
+    assert name in case_plans() and grid >= 1, (name, grid)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -196,6 +245,7 @@ def max_fwd(x, inds, order, shift=0):
     out = blank((nq, c), x.dtype, x.device, shift)
     arg = blank((nq, c), torch.int32, x.device)
     sfx = "_bf16" if x.dtype == torch.bfloat16 else ""
+    reported("max_fwd", nq, c, x, out, arg, order=order)
     if order is None:
         check(getattr(lib, "ws_max_pool_fwd" + sfx)(ptr(x), ns, c, ptr(inds), nq, h, ptr(out), ptr(arg), current_stream()))
     else:
@@ -209,6 +259,7 @@ def max_bwd(dy, arg, table, order, shift=0):
     nq, c = dy.shape
     dx = blank((table.ns, c), dy.dtype, dy.device, shift)
     sfx = "_bf16" if dy.dtype == torch.bfloat16 else ""
+    reported("max_bwd", table.ns, c, dy, dx, arg, order=order)
     if order is None:
         check(getattr(lib, "ws_max_pool_bwd" + sfx)(ptr(dy), ptr(arg), nq, table.h, c, ptr(table.offsets), ptr(table.pairs),
                                                   table.ns, ptr(dx), current_stream()))
@@ -236,6 +287,7 @@ def closest_fwd(x, inds):
     (ns, c), (nq, h) = x.shape, inds.shape
     out = blank((nq, c), x.dtype, x.device)
     name = "ws_closest_pool_fwd" + ("_bf16" if x.dtype == torch.bfloat16 else "")
+    reported("closest_fwd", nq, c, x, out)
     check(getattr(lib, name)(ptr(x), ns, c, ptr(inds), nq, h, ptr(out), current_stream()))
     return out
 
@@ -245,6 +297,7 @@ def closest_bwd(dy, table, shift=0):
     nq, c = dy.shape
     dx = blank((table.ns, c), dy.dtype, dy.device, shift)
     name = "ws_closest_pool_bwd" + ("_bf16" if dy.dtype == torch.bfloat16 else "")
+    reported("closest_bwd", table.ns, c, dy, dx)
     check(getattr(lib, name)(ptr(dy), nq, table.h, c, ptr(table.offsets), ptr(table.pairs), table.ns, ptr(dx), current_stream()))
     return dx
 
@@ -335,11 +388,13 @@ def test_max_pool_byte_record(gpu, case):
             oq, osup = make_order(okind, nq, rng, gpu), make_order(okind, ns, rng, gpu)
             out = blank((nq, c), torch.float32, gpu)
             arg8 = blank((nq, c), torch.uint8, gpu)
+            reported("max_fwd", nq, c, x, out, arg8, 1, oq)
             check(fwd8(ptr(x), ns, c, ptr(inds), nq, h, ptr(out), ptr(arg8), ptr(oq), current_stream()))
             assert torch.equal(out.cpu(), torch.from_numpy(ref_out)), "%s order=%s: out" % (what, okind)
             assert torch.equal(arg8.to(torch.int32), pub_arg), "%s order=%s: the byte record differs from the int32 one" % (what, okind)
             for a_np, a in ((None, None), (add_np, add)):
                 dx = blank((ns, c), torch.float32, gpu)
+                reported("max_bwd", ns, c, dy, dx, arg8, 1, osup)
                 check(bwd8(ptr(dy), ptr(arg8), nq, h, c, ptr(table.offsets), ptr(table.pairs), ns, ptr(dx), ptr(osup), ptr(a),
                            current_stream()))
                 tag = "%s order=%s add=%s: dx" % (what, okind, a is not None)
@@ -383,34 +438,28 @@ def closest_ladder_inds(rng, c, h):
 
 @pytest.mark.parametrize("c,dtype,shift,h", CLOSEST_BWD, ids=["c%d_%s_s%d_h%d" % t for t in CLOSEST_BWD])
 def test_closest_pool_backward(gpu, c, dtype, shift, h):
-    lib = _lib.lib()
     rng = _rng("cb", c, dtype, shift, h)
     inds_np, ns = closest_ladder_inds(rng, c, h)
     nq = inds_np.shape[0]
     inds = torch.from_numpy(inds_np).to(gpu)
     table = ops.TransposedTable(inds, ns)
-    flag = C.c_int.in_dll(lib, "ws_closest_bwd_vec")
-    keep = flag.value
-    try:
-        for data in ("mixed", "normal"):
-            dy_np = make_rows(rng, data, (nq, c), dtype, "g")
-            ref, n, sabs = P.closest_pool_bwd_ref(dy_np, inds_np, ns)
-            assert n[:, 0].max() > n[:-3, 0].max() and (n[:, 0] == 0).sum() >= 2
-            dy = dev(dy_np, DT[dtype], gpu, shift)
-            got = {}
-            for f in (1, 0):
-                flag.value = f
+    for data in ("mixed", "normal"):
+        dy_np = make_rows(rng, data, (nq, c), dtype, "g")
+        ref, n, sabs = P.closest_pool_bwd_ref(dy_np, inds_np, ns)
+        assert n[:, 0].max() > n[:-3, 0].max() and (n[:, 0] == 0).sum() >= 2
+        dy = dev(dy_np, DT[dtype], gpu, shift)
+        got = {}
+        for f in (1, 0):
+            with closest_vec_switch(f):
                 got[f] = closest_bwd(dy, table, shift)
                 what = "closest bwd c=%d %s shift=%d h=%d %s vec=%d" % (c, dtype, shift, h, data, f)
                 assert torch.equal(bits(got[f]), bits(closest_bwd(dy, table, shift))), what + ": does not repeat its bits"
-                if data == "normal":
-                    assert_bound(got[f], ref, n, sabs, dtype == "bf16", what)
-                else:
-                    assert torch.equal(got[f].cpu(), rounded(ref, DT[dtype])), what
-            if data == "mixed":
-                assert torch.equal(bits(got[1]), bits(got[0]))
-    finally:
-        flag.value = keep
+            if data == "normal":
+                assert_bound(got[f], ref, n, sabs, dtype == "bf16", what)
+            else:
+                assert torch.equal(got[f].cpu(), rounded(ref, DT[dtype])), what
+        if data == "mixed":
+            assert torch.equal(bits(got[1]), bits(got[0]))
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -106,6 +106,7 @@ SIGNATURES = {
     "ws_max_pool_bwd_bf16": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
     "ws_closest_pool_fwd_bf16": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp]),
     "ws_closest_pool_bwd_bf16": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "ws_pool_variant": (C.c_int, [_i32, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, C.c_char_p, _i32, C.POINTER(_i32)]),
     "ws_gemm_xbt_bf16": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _i64, _i32, _f32, _vp, _i64, _i32, _vp]),
     "ws_gemm_xty_bf16": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _vp]),
     "ws_act_bwd_colsum_bf16_scratch_bytes": (_i64, [_i64, _i32]),

@@ -313,137 +313,159 @@ __global__ __launch_bounds__(256) void closest_pool_bwd_vec_kernel(const float* 
 // of the DALES step (71 000 x 59 rows of 512 bytes): forward 245 -> 195 us in the step, 136 -> 97 us alone
 constexpr int POOL_INTERLEAVE = 256;
 constexpr int POOL_SPLIT_ROWS = 8192;   // max-pools over fewer rows than this give every 256-channel chunk of a row a wave of its own
-static int pool_split(int64_t rows, int c)
-{
-    return (rows < POOL_SPLIT_ROWS && c > 256) ? (int)ws_ceil_div(c, 256) : 1;
-}
 extern "C" int ws_closest_bwd_vec = 1;      // nearest-upsampling backward: 1 = float4 lanes, several incoming rows side by side (A/B: WEASAL_CLOSEST_BWD_VEC)
-static inline int pool_grid(int64_t groups, int ilv)
+
+// ---- plans: what an entry launches, from its arguments alone (pointers only for their alignment).  The launchers below and the
+//      reporter (ws_pool_variant) call the same plan function; every selection rule is here.
+enum { PK_MAX_FWD_VEC, PK_MAX_FWD, PK_MAX_BWD_VEC, PK_MAX_BWD, PK_CLOSEST_FWD, PK_CLOSEST_BWD, PK_CLOSEST_BWD_VEC };
+struct PoolPlan {
+    int kernel;         // PK_*: the kernel family
+    bool bf16;          // row type T: bf16_t instead of float
+    int g;              // G: lanes per row (the vector forms)
+    int u;              // U: neighbour rows in flight per lane (PK_MAX_FWD_VEC)
+    int arg_bytes;      // AT of the arg-max record: 4 = int32_t (the C ABI), 1 = uint8_t (the block calls)
+    int split;          // channel chunks of a row that are groups of their own (1: a row is one group)
+    int ilv;            // workgroups per XCD of the interleaved assignment; 0: contiguous chunks
+    int grid;           // workgroups of 256 threads
+};
+const char* row_name(const PoolPlan& p) { return p.bf16 ? "bf16" : "f32"; }
+
+int pool_grid(int64_t groups, int ilv)
 {
     if (ilv <= 0) return ws_grid(groups, 4);
     const int64_t need = (groups + 31) / 32;              // never more workgroups per XCD than groups / 4 / 8
     return 8 * (int)std::max<int64_t>(1, std::min<int64_t>(ilv, need));
 }
 
-template <typename T>
-int max_pool_fwd_impl(const T* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h,
-                      T* out, int32_t* arg, void* stream, const int32_t* order = nullptr)
+// every max-pool entry.  fwd: rows = nq, a / b = x / out, arg may be NULL (which counts as aligned); backward: rows = ns,
+// a / b = dy / dx.  arg_bytes = 1 (f32 rows in float4 pieces: the caller's precondition) has the vector forms only.
+PoolPlan max_pool_plan(bool fwd, bool bf16, int64_t rows, int c, const void* a, const void* b, const void* arg, int arg_bytes, bool ordered)
 {
-    WS_REQUIRE(ns >= 0 && nq >= 0 && c >= 1 && h >= 1, "bad sizes");
-    if (nq == 0) return WS_OK;
-    WS_REQUIRE(inds && out && (ns == 0 || x), "NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    const bool vec = (c % 4 == 0) && ws_row_aligned<T>(x) && ws_row_aligned<T>(out) && (!arg || al16p(arg));
-    const int ilv = order ? POOL_INTERLEAVE : 0;
-    if (vec && c <= 16) max_pool_fwd_vec_kernel<4, T><<<pool_grid(ws_ceil_div(nq, 16), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
-    else if (vec && c <= 32) max_pool_fwd_vec_kernel<8, T><<<pool_grid(ws_ceil_div(nq, 8), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
-    else if (vec && c <= 64) max_pool_fwd_vec_kernel<16, T><<<pool_grid(ws_ceil_div(nq, 4), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
-    else if (vec && c <= 128) max_pool_fwd_vec_kernel<32, T><<<pool_grid(ws_ceil_div(nq, 2), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
-    else if (vec) {
-        const int sp = pool_split(nq, c);
-        max_pool_fwd_vec_kernel<64, T><<<pool_grid(nq * sp, ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv, sp);
-    }
-    else max_pool_fwd_kernel<T><<<ws_grid(nq, 4), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg);
-    WS_LAUNCH_CHECK();
-    return WS_OK;
-}
-
-template <typename T>
-int max_pool_bwd_impl(const T* dy, const int32_t* arg, int64_t nq, int32_t h, int32_t c,
-                      const int32_t* t_offsets, const int32_t* t_pairs, int64_t ns, T* dx, void* stream,
-                      const int32_t* order = nullptr)
-{
-    WS_REQUIRE(ns >= 0 && nq >= 0 && c >= 1 && h >= 1, "bad sizes");
-    if (ns == 0) return WS_OK;
-    WS_REQUIRE(t_offsets && dx && (nq == 0 || (dy && arg && t_pairs)), "NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    const bool vec = (c % 4 == 0) && ws_row_aligned<T>(dy) && ws_row_aligned<T>(dx) && al16p(arg);
-    const int ilv = order ? POOL_INTERLEAVE : 0;
-    if (vec && c <= 32) max_pool_bwd_vec_kernel<8, T><<<pool_grid(ws_ceil_div(ns, 8), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv);
-    else if (vec && c <= 64) max_pool_bwd_vec_kernel<16, T><<<pool_grid(ws_ceil_div(ns, 4), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv);
-    else if (vec && c <= 128) max_pool_bwd_vec_kernel<32, T><<<pool_grid(ws_ceil_div(ns, 2), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv);
-    else if (vec) {
-        const int sp = pool_split(ns, c);
-        max_pool_bwd_vec_kernel<64, T><<<pool_grid(ns * sp, ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv, nullptr, sp);
-    }
-    else max_pool_bwd_kernel<T><<<ws_grid(ns, 4), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx);
-    WS_LAUNCH_CHECK();
-    return WS_OK;
-}
-
-// the block calls' private form: arg-max record in bytes (h <= 255, c % 4 == 0, aligned rows: the caller checks)
-int max_pool_fwd_u8_impl(const float* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h, float* out, uint8_t* arg,
-                         const int32_t* order, hipStream_t st)
-{
-    if (nq == 0) return WS_OK;
-    const int ilv = order ? POOL_INTERLEAVE : 0;       // (only with a spatial order is a neighbouring group a neighbouring place)
-    if (c <= 16) max_pool_fwd_vec_kernel<4, float, uint8_t><<<pool_grid(ws_ceil_div(nq, 16), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
-    else if (c <= 32) max_pool_fwd_vec_kernel<8, float, uint8_t><<<pool_grid(ws_ceil_div(nq, 8), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
-    else if (c <= 64) max_pool_fwd_vec_kernel<16, float, uint8_t><<<pool_grid(ws_ceil_div(nq, 4), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
+    PoolPlan p{fwd ? PK_MAX_FWD : PK_MAX_BWD, bf16, 0, 0, arg_bytes, 1, 0, ws_grid(rows, 4)};      // one wave per row; takes no order
+    const bool rows_al = bf16 ? ws_row_aligned<bf16_t>(a) && ws_row_aligned<bf16_t>(b) : ws_row_aligned<float>(a) && ws_row_aligned<float>(b);
+    if (arg_bytes != 1 && !(c % 4 == 0 && rows_al && al16p(arg))) return p;
+    p.kernel = fwd ? PK_MAX_FWD_VEC : PK_MAX_BWD_VEC;
+    p.g = (fwd && c <= 16) ? 4 : (c <= 32 ? 8 : (c <= 64 ? 16 : (c <= 128 ? 32 : 64)));           // (the backward has no G = 4)
     // 128 channels: 8 neighbour rows in flight per lane (level 0 of the DALES step: 184 -> 172 us alone, against 4)
-    else if (c <= 128) max_pool_fwd_vec_kernel<32, float, uint8_t, 8><<<pool_grid(ws_ceil_div(nq, 2), ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv);
-    else {
-        const int sp = pool_split(nq, c);
-        max_pool_fwd_vec_kernel<64, float, uint8_t><<<pool_grid(nq * sp, ilv), 256, 0, st>>>(x, ns, c, inds, nq, h, out, arg, order, ilv, sp);
-    }
-    WS_LAUNCH_CHECK();
-    return WS_OK;
+    p.u = (fwd && arg_bytes == 1 && p.g == 32) ? 8 : 4;
+    p.split = (rows < POOL_SPLIT_ROWS && c > 256) ? (int)ws_ceil_div(c, 256) : 1;                 // (c > 256: G = 64)
+    p.ilv = ordered ? POOL_INTERLEAVE : 0;               // (only with a spatial order is a neighbouring group a neighbouring place)
+    p.grid = pool_grid(ws_ceil_div(rows, 64 / p.g) * p.split, p.ilv);
+    return p;
 }
 
-int max_pool_bwd_u8_impl(const float* dy, const uint8_t* arg, int64_t nq, int32_t h, int32_t c, const int32_t* t_offsets,
-                         const int32_t* t_pairs, int64_t ns, float* dx, const int32_t* order, hipStream_t st, const float* add = nullptr)
+PoolPlan closest_fwd_plan(bool bf16, int64_t nq) { return PoolPlan{PK_CLOSEST_FWD, bf16, 0, 0, 0, 1, 0, ws_grid(nq, 4)}; }
+
+// vector form: f32 rows of c = 4 G channels, G | 64, or whole waves (G = 64) over rows of c % 256 == 0
+PoolPlan closest_bwd_plan(bool bf16, int64_t ns, int c, const void* dy, const void* dx)
 {
-    (void)nq;
-    if (ns == 0) return WS_OK;
-    const int ilv = order ? POOL_INTERLEAVE : 0;       // (only with a spatial order is a neighbouring group a neighbouring place)
-    if (c <= 32) max_pool_bwd_vec_kernel<8, float, uint8_t><<<pool_grid(ws_ceil_div(ns, 8), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv, add);
-    else if (c <= 64) max_pool_bwd_vec_kernel<16, float, uint8_t><<<pool_grid(ws_ceil_div(ns, 4), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv, add);
-    else if (c <= 128) max_pool_bwd_vec_kernel<32, float, uint8_t><<<pool_grid(ws_ceil_div(ns, 2), ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv, add);
-    else {
-        const int sp = pool_split(ns, c);
-        max_pool_bwd_vec_kernel<64, float, uint8_t><<<pool_grid(ns * sp, ilv), 256, 0, st>>>(dy, arg, h, c, t_offsets, t_pairs, ns, dx, order, ilv, add, sp);
+    PoolPlan p{PK_CLOSEST_BWD, bf16, 0, 0, 0, 1, 0, ws_grid(ns, 4)};
+    if (!bf16 && ws_closest_bwd_vec && al16p(dy) && al16p(dx) && (c == 32 || c == 64 || c == 128 || c % 256 == 0)) {
+        p.kernel = PK_CLOSEST_BWD_VEC;
+        p.g = c % 256 == 0 ? 64 : c / 4;
     }
+    return p;
+}
+
+// the name of a plan: what tests/test_pool_branches_*.py count and compare
+void plan_text(const PoolPlan& p, char* out, size_t n)
+{
+    const char* op = (p.kernel == PK_MAX_FWD_VEC || p.kernel == PK_MAX_FWD) ? "max_fwd" : "max_bwd";
+    switch (p.kernel) {
+    case PK_MAX_FWD_VEC: case PK_MAX_BWD_VEC:
+        snprintf(out, n, "%s vec G=%d U=%d AT=%s %s split=%d %s", op, p.g, p.u, p.arg_bytes == 1 ? "u8" : "i32", row_name(p), p.split,
+                 p.ilv ? "interleaved" : "contiguous");
+        break;
+    case PK_MAX_FWD: case PK_MAX_BWD: snprintf(out, n, "%s generic %s", op, row_name(p)); break;
+    case PK_CLOSEST_FWD: snprintf(out, n, "closest_fwd scalar %s", row_name(p)); break;
+    case PK_CLOSEST_BWD: snprintf(out, n, "closest_bwd scalar %s", row_name(p)); break;
+    default: snprintf(out, n, "closest_bwd vec G=%d", p.g);
+    }
+}
+
+// ---- launchers: one dispatch on the plan per kernel family.  `hit` stays false where the plan names what is not instantiated
+int launched(bool hit, const PoolPlan& p)
+{
+    if (!hit) return ws_no_instantiation("pool kernel family %d <G=%d, U=%d> bf16=%d arg_bytes=%d", p.kernel, p.g, p.u, p.bf16, p.arg_bytes);
     WS_LAUNCH_CHECK();
     return WS_OK;
 }
 
-template <typename T>
-int closest_pool_fwd_impl(const T* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h,
-                          T* out, void* stream)
+// the forwards: max_pool_fwd_vec_kernel (the byte record: f32 rows only; U = 8: its G = 32 form only), or a wave per row
+// (max_pool_fwd_kernel, closest_pool_fwd_kernel)
+int launch_fwd(const PoolPlan& p, void* stream, const void* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h, void* out,
+               void* arg, const int32_t* order)
+{
+    hipStream_t st = (hipStream_t)stream;
+    bool hit = false;
+    if (p.kernel == PK_MAX_FWD_VEC)
+        dispatch([&](auto bf, auto g, auto u, auto u8) {
+            using T = Row<bf.value>;
+            using AT = std::conditional_t<u8.value != 0, uint8_t, int32_t>;
+            if constexpr (!(bf.value && u8.value) && (u.value == 8) == (u8.value && g.value == 32)) {
+                max_pool_fwd_vec_kernel<g.value, T, AT, u.value><<<p.grid, 256, 0, st>>>((const T*)x, ns, c, inds, nq, h, (T*)out, (AT*)arg, order,
+                                                                                         p.ilv, p.split);
+                hit = true;
+            }
+        }, Flag{p.bf16}, Pick<4, 8, 16, 32, 64>{p.g}, Pick<4, 8>{p.u}, Flag{p.arg_bytes == 1});
+    else
+        hit = dispatch([&](auto bf) {
+            using T = Row<bf.value>;
+            if (p.kernel == PK_MAX_FWD) max_pool_fwd_kernel<T><<<p.grid, 256, 0, st>>>((const T*)x, ns, c, inds, nq, h, (T*)out, (int32_t*)arg);
+            else closest_pool_fwd_kernel<T><<<p.grid, 256, 0, st>>>((const T*)x, ns, c, inds, nq, h, (T*)out);
+        }, Flag{p.bf16});
+    return launched(hit, p);
+}
+
+// the backwards: max_pool_bwd_vec_kernel (no G = 4; the byte record: f32 rows only; add: the byte-record entry's),
+// closest_pool_bwd_vec_kernel (f32 rows), or a wave per row (max_pool_bwd_kernel, closest_pool_bwd_kernel)
+int launch_bwd(const PoolPlan& p, void* stream, const void* dy, const void* arg, int32_t h, int32_t c, const int32_t* t_offsets,
+               const int32_t* t_pairs, int64_t ns, void* dx, const int32_t* order, const float* add = nullptr)
+{
+    hipStream_t st = (hipStream_t)stream;
+    bool hit = false;
+    if (p.kernel == PK_MAX_BWD_VEC)
+        dispatch([&](auto bf, auto g, auto u8) {
+            using T = Row<bf.value>;
+            using AT = std::conditional_t<u8.value != 0, uint8_t, int32_t>;
+            if constexpr (!(bf.value && u8.value)) {
+                max_pool_bwd_vec_kernel<g.value, T, AT><<<p.grid, 256, 0, st>>>((const T*)dy, (const AT*)arg, h, c, t_offsets, t_pairs, ns, (T*)dx,
+                                                                                order, p.ilv, (const T*)add, p.split);
+                hit = true;
+            }
+        }, Flag{p.bf16}, Pick<8, 16, 32, 64>{p.g}, Flag{p.arg_bytes == 1});
+    else if (p.kernel == PK_CLOSEST_BWD_VEC)
+        hit = dispatch([&](auto g) {
+            closest_pool_bwd_vec_kernel<g.value><<<p.grid, 256, 0, st>>>((const float*)dy, h, c, t_offsets, t_pairs, ns, (float*)dx);
+        }, Pick<8, 16, 32, 64>{p.g});
+    else
+        hit = dispatch([&](auto bf) {
+            using T = Row<bf.value>;
+            if (p.kernel == PK_MAX_BWD) max_pool_bwd_kernel<T><<<p.grid, 256, 0, st>>>((const T*)dy, (const int32_t*)arg, h, c, t_offsets, t_pairs, ns, (T*)dx);
+            else closest_pool_bwd_kernel<T><<<p.grid, 256, 0, st>>>((const T*)dy, h, c, t_offsets, t_pairs, ns, (T*)dx);
+        }, Flag{p.bf16});
+    return launched(hit, p);
+}
+
+// ---- the public entries: validate, plan, launch.  closest: the closest pools, which have neither arg nor order
+int pool_fwd_impl(bool closest, bool bf16, const void* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h, void* out,
+                  int32_t* arg, const int32_t* order, void* stream)
 {
     WS_REQUIRE(ns >= 0 && nq >= 0 && c >= 1 && h >= 1, "bad sizes");
     if (nq == 0) return WS_OK;
     WS_REQUIRE(inds && out && (ns == 0 || x), "NULL argument");
-    closest_pool_fwd_kernel<T><<<ws_grid(nq, 4), 256, 0, (hipStream_t)stream>>>(x, ns, c, inds, nq, h, out);
-    WS_LAUNCH_CHECK();
-    return WS_OK;
+    const PoolPlan p = closest ? closest_fwd_plan(bf16, nq) : max_pool_plan(true, bf16, nq, c, x, out, arg, 4, order != nullptr);
+    return launch_fwd(p, stream, x, ns, c, inds, nq, h, out, arg, order);
 }
 
-template <typename T>
-int closest_pool_bwd_impl(const T* dy, int64_t nq, int32_t h, int32_t c, const int32_t* t_offsets,
-                          const int32_t* t_pairs, int64_t ns, T* dx, void* stream)
+int pool_bwd_impl(bool closest, bool bf16, const void* dy, const int32_t* arg, int64_t nq, int32_t h, int32_t c, const int32_t* t_offsets,
+                  const int32_t* t_pairs, int64_t ns, void* dx, const int32_t* order, void* stream)
 {
     WS_REQUIRE(ns >= 0 && nq >= 0 && c >= 1 && h >= 1, "bad sizes");
     if (ns == 0) return WS_OK;
-    WS_REQUIRE(t_offsets && dx && (nq == 0 || (dy && t_pairs)), "NULL argument");
-    if constexpr (sizeof(T) == 4) {
-        const bool al = ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15u) == 0;
-        const float* dyf = reinterpret_cast<const float*>(dy);
-        float* dxf = reinterpret_cast<float*>(dx);
-        hipStream_t st = (hipStream_t)stream;
-        if (ws_closest_bwd_vec && al && (c == 32 || c == 64 || c == 128 || c % 256 == 0)) {
-            const int g4 = c % 256 == 0 ? 64 : c / 4;       // G: the lanes of a row (c = 4 G), a whole wave for the wide rows
-            const bool called = dispatch([&](auto g) {
-                closest_pool_bwd_vec_kernel<g.value><<<ws_grid(ns, 4), 256, 0, st>>>(dyf, h, c, t_offsets, t_pairs, ns, dxf);
-            }, Pick<8, 16, 32, 64>{g4});
-            if (!called) return ws_no_instantiation("closest_pool_bwd_vec_kernel<G=%d> c=%d", g4, c);
-            WS_LAUNCH_CHECK();
-            return WS_OK;
-        }
-    }
-    closest_pool_bwd_kernel<T><<<ws_grid(ns, 4), 256, 0, (hipStream_t)stream>>>(dy, h, c, t_offsets, t_pairs, ns, dx);
-    WS_LAUNCH_CHECK();
-    return WS_OK;
+    WS_REQUIRE(t_offsets && dx && (nq == 0 || (dy && (closest || arg) && t_pairs)), "NULL argument");
+    const PoolPlan p = closest ? closest_bwd_plan(bf16, ns, c, dy, dx) : max_pool_plan(false, bf16, ns, c, dy, dx, arg, 4, order != nullptr);
+    return launch_bwd(p, stream, dy, arg, h, c, t_offsets, t_pairs, ns, dx, order);
 }
 
 }  // namespace
@@ -453,78 +475,74 @@ extern "C" {
 int ws_max_pool_fwd(const float* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h,
                     float* out, int32_t* arg, void* stream)
 {
-    return max_pool_fwd_impl<float>(x, ns, c, inds, nq, h, out, arg, stream);
+    return pool_fwd_impl(false, false, x, ns, c, inds, nq, h, out, arg, nullptr, stream);
 }
 
 int ws_max_pool_bwd(const float* dy, const int32_t* arg, int64_t nq, int32_t h, int32_t c,
                     const int32_t* t_offsets, const int32_t* t_pairs, int64_t ns, float* dx, void* stream)
 {
-    return max_pool_bwd_impl<float>(dy, arg, nq, h, c, t_offsets, t_pairs, ns, dx, stream);
+    return pool_bwd_impl(false, false, dy, arg, nq, h, c, t_offsets, t_pairs, ns, dx, nullptr, stream);
 }
 
 int ws_max_pool_fwd_ordered(const float* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h, float* out, int32_t* arg,
                             const int32_t* order_q, void* stream)
 {
-    return max_pool_fwd_impl<float>(x, ns, c, inds, nq, h, out, arg, stream, order_q);
+    return pool_fwd_impl(false, false, x, ns, c, inds, nq, h, out, arg, order_q, stream);
 }
 
 int ws_max_pool_bwd_ordered(const float* dy, const int32_t* arg, int64_t nq, int32_t h, int32_t c, const int32_t* t_offsets,
                             const int32_t* t_pairs, int64_t ns, float* dx, const int32_t* order_s, void* stream)
 {
-    return max_pool_bwd_impl<float>(dy, arg, nq, h, c, t_offsets, t_pairs, ns, dx, stream, order_s);
+    return pool_bwd_impl(false, false, dy, arg, nq, h, c, t_offsets, t_pairs, ns, dx, order_s, stream);
 }
 
 int ws_max_pool_fwd_ordered_bf16(const uint16_t* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h, uint16_t* out,
                                  int32_t* arg, const int32_t* order_q, void* stream)
 {
-    return max_pool_fwd_impl<bf16_t>(reinterpret_cast<const bf16_t*>(x), ns, c, inds, nq, h, reinterpret_cast<bf16_t*>(out), arg, stream,
-                                     order_q);
+    return pool_fwd_impl(false, true, x, ns, c, inds, nq, h, out, arg, order_q, stream);
 }
 
 int ws_max_pool_bwd_ordered_bf16(const uint16_t* dy, const int32_t* arg, int64_t nq, int32_t h, int32_t c, const int32_t* t_offsets,
                                  const int32_t* t_pairs, int64_t ns, uint16_t* dx, const int32_t* order_s, void* stream)
 {
-    return max_pool_bwd_impl<bf16_t>(reinterpret_cast<const bf16_t*>(dy), arg, nq, h, c, t_offsets, t_pairs, ns,
-                                     reinterpret_cast<bf16_t*>(dx), stream, order_s);
+    return pool_bwd_impl(false, true, dy, arg, nq, h, c, t_offsets, t_pairs, ns, dx, order_s, stream);
 }
 
 int ws_closest_pool_fwd(const float* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h,
                         float* out, void* stream)
 {
-    return closest_pool_fwd_impl<float>(x, ns, c, inds, nq, h, out, stream);
+    return pool_fwd_impl(true, false, x, ns, c, inds, nq, h, out, nullptr, nullptr, stream);
 }
 
 int ws_closest_pool_bwd(const float* dy, int64_t nq, int32_t h, int32_t c, const int32_t* t_offsets,
                         const int32_t* t_pairs, int64_t ns, float* dx, void* stream)
 {
-    return closest_pool_bwd_impl<float>(dy, nq, h, c, t_offsets, t_pairs, ns, dx, stream);
+    return pool_bwd_impl(true, false, dy, nullptr, nq, h, c, t_offsets, t_pairs, ns, dx, nullptr, stream);
 }
 
 // bf16 feature rows (BASELINE config 5): same kernels, 8-byte row pieces
 int ws_max_pool_fwd_bf16(const uint16_t* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h,
                          uint16_t* out, int32_t* arg, void* stream)
 {
-    return max_pool_fwd_impl<bf16_t>(reinterpret_cast<const bf16_t*>(x), ns, c, inds, nq, h, reinterpret_cast<bf16_t*>(out), arg, stream);
+    return pool_fwd_impl(false, true, x, ns, c, inds, nq, h, out, arg, nullptr, stream);
 }
 
 int ws_max_pool_bwd_bf16(const uint16_t* dy, const int32_t* arg, int64_t nq, int32_t h, int32_t c,
                          const int32_t* t_offsets, const int32_t* t_pairs, int64_t ns, uint16_t* dx, void* stream)
 {
-    return max_pool_bwd_impl<bf16_t>(reinterpret_cast<const bf16_t*>(dy), arg, nq, h, c, t_offsets, t_pairs, ns,
-                                     reinterpret_cast<bf16_t*>(dx), stream);
+    return pool_bwd_impl(false, true, dy, arg, nq, h, c, t_offsets, t_pairs, ns, dx, nullptr, stream);
 }
 
 int ws_closest_pool_fwd_bf16(const uint16_t* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h,
                              uint16_t* out, void* stream)
 {
-    return closest_pool_fwd_impl<bf16_t>(reinterpret_cast<const bf16_t*>(x), ns, c, inds, nq, h, reinterpret_cast<bf16_t*>(out), stream);
+    return pool_fwd_impl(true, true, x, ns, c, inds, nq, h, out, nullptr, nullptr, stream);
 }
 
 int ws_closest_pool_bwd_bf16(const uint16_t* dy, int64_t nq, int32_t h, int32_t c, const int32_t* t_offsets,
                              const int32_t* t_pairs, int64_t ns, uint16_t* dx, void* stream)
 {
-    return closest_pool_bwd_impl<bf16_t>(reinterpret_cast<const bf16_t*>(dy), nq, h, c, t_offsets, t_pairs, ns,
-                                         reinterpret_cast<bf16_t*>(dx), stream);
+    return pool_bwd_impl(true, true, dy, nullptr, nq, h, c, t_offsets, t_pairs, ns, dx, nullptr, stream);
 }
 
 // private to the library (declared in ws_common.h, not part of include/weasal_hip.h): the block calls keep their arg-max
@@ -532,13 +550,40 @@ int ws_closest_pool_bwd_bf16(const uint16_t* dy, int64_t nq, int32_t h, int32_t 
 int ws_priv_max_pool_fwd_u8(const float* x, int64_t ns, int32_t c, const int64_t* inds, int64_t nq, int32_t h, float* out,
                             uint8_t* arg, const int32_t* order_q, void* stream)
 {
-    return max_pool_fwd_u8_impl(x, ns, c, inds, nq, h, out, arg, order_q, (hipStream_t)stream);
+    if (nq == 0) return WS_OK;
+    return launch_fwd(max_pool_plan(true, false, nq, c, x, out, arg, 1, order_q != nullptr), stream, x, ns, c, inds, nq, h, out, arg, order_q);
 }
 
 int ws_priv_max_pool_bwd_u8(const float* dy, const uint8_t* arg, int64_t nq, int32_t h, int32_t c, const int32_t* t_offsets,
                             const int32_t* t_pairs, int64_t ns, float* dx, const int32_t* order_s, const float* add, void* stream)
 {
-    return max_pool_bwd_u8_impl(dy, arg, nq, h, c, t_offsets, t_pairs, ns, dx, order_s, (hipStream_t)stream, add);
+    (void)nq;
+    if (ns == 0) return WS_OK;
+    return launch_bwd(max_pool_plan(false, false, ns, c, dy, dx, arg, 1, order_s != nullptr), stream, dy, arg, h, c, t_offsets, t_pairs, ns,
+                          dx, order_s, add);
+}
+
+// What the entries of this file launch for these arguments, as the name tests/test_pool_branches_*.py count ("max_fwd vec G=32
+// U=4 AT=i32 f32 split=1 interleaved", "max_bwd generic bf16", "closest_bwd vec G=16", ...): the plan function of the entry
+// named by op (WS_POOL_*, weasal_hip.h), nothing read or launched.  rows = nq (forwards) or ns (backwards); rows_a / rows_b: the two
+// row operands (x and out, or dy and dx) and arg: tested for alignment only.  grid (may be NULL): the workgroups of the launch.
+int ws_pool_variant(int32_t op, int64_t rows, int32_t c, const void* rows_a, const void* rows_b, const void* arg, int32_t rows_bf16,
+                    int32_t arg_bytes, int32_t ordered, char* out, int32_t cap, int32_t* grid)
+{
+    WS_REQUIRE(out && cap > 0 && rows >= 0 && c >= 1 && (arg_bytes == 4 || arg_bytes == 1), "bad argument");
+    const bool bf = rows_bf16 != 0, max_op = op == WS_POOL_MAX_FWD || op == WS_POOL_MAX_BWD;
+    WS_REQUIRE(arg_bytes == 4 || (max_op && !bf && c % 4 == 0 && al16p(rows_a) && al16p(rows_b) && (reinterpret_cast<uintptr_t>(arg) & 3u) == 0),
+               "the byte arg-max record: max-pools of f32 rows, c %% 4 == 0, 16-byte aligned rows, 4-byte aligned arg");
+    PoolPlan p;
+    switch (op) {
+    case WS_POOL_MAX_FWD: case WS_POOL_MAX_BWD: p = max_pool_plan(op == WS_POOL_MAX_FWD, bf, rows, c, rows_a, rows_b, arg, arg_bytes, ordered != 0); break;
+    case WS_POOL_CLOSEST_FWD: p = closest_fwd_plan(bf, rows); break;
+    case WS_POOL_CLOSEST_BWD: p = closest_bwd_plan(bf, rows, c, rows_a, rows_b); break;
+    default: return ws_fail(WS_ERR_INVALID, "unknown pool operation %d", op);
+    }
+    plan_text(p, out, (size_t)cap);
+    if (grid) *grid = p.grid;
+    return WS_OK;
 }
 
 }  // extern "C"

@@ -617,6 +617,8 @@ typedef struct ws_upunary {
     int32_t gate_dxc;                    /* backward: write dxc * LeakyReLU'(xc) (xc = the activated output of its producer) */
 } ws_upunary;
 
+int64_t ws_kpblock_bytes(void);   /* sizeof(ws_kpblock), sizeof(ws_upunary): hold a binding's layout of the descriptors */
+int64_t ws_upunary_bytes(void);   /* to the compiler's, as ws_pyramid_desc_bytes does */
 int64_t ws_upunary_fwd_scratch_bytes(const ws_upunary* d);
 int64_t ws_upunary_bwd_scratch_bytes(const ws_upunary* d);
 int ws_upunary_fwd(const ws_upunary* d, void* scratch, int64_t scratch_bytes, void* stream);

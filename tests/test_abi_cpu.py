@@ -29,6 +29,106 @@ def test_library_exports_every_declared_symbol():
     assert isinstance(lib.ws_device_count(), int)
 
 
+def test_parser_drops_no_declared_name():
+    """the name regex above and weasal_amd._abi.parse find the same ws_* functions in the header: nothing is skipped"""
+    from weasal_amd import _abi, _lib
+    parsed = _abi.parse(open(_lib.HEADER_PATH).read())
+    assert sorted(parsed.prototypes) == _declared()
+    assert _lib.SIGNATURES == parsed.prototypes
+
+
+def test_descriptor_layouts_have_the_compilers_size():
+    """sizeof of each structure derived from the header text equals what the compiler laid out"""
+    from weasal_amd import _lib, fused, ops, pyramid
+    lib = _lib.lib()
+    assert C.sizeof(fused.KPBlockDesc) == lib.ws_kpblock_bytes()
+    assert C.sizeof(fused.UpUnaryDesc) == lib.ws_upunary_bytes()
+    assert C.sizeof(pyramid.PyramidDesc) == lib.ws_pyramid_desc_bytes()
+    assert C.sizeof(ops.SamplerItems) == lib.ws_sampler_items_bytes()
+    assert (pyramid._ML, pyramid._MB) == (_lib.ABI.constants["WS_PYRAMID_MAX_LEVELS"], _lib.ABI.constants["WS_PYRAMID_MAX_BATCH"])
+
+
+_SNIPPET = """
+#define N 8
+#define M 4
+/* int ws_in_block_comment(int32_t a); */
+// int ws_behind_slashes(int32_t a);
+typedef struct ws_s {
+    const float *a, *b;      // two pointers from one declaration
+    int32_t v[3 * N + 1];
+    int32_t m[N][M];
+    double d; uint8_t u; char* name;
+} ws_s;
+struct ws_t { int64_t n; uint64_t* p; };
+int64_t ws_f(void);
+const int32_t* ws_g(const ws_s* s, int64_t n, float x, const char* text, char* out, ws_s** pp, const float row[]);
+void ws_h(int a, uint32_t b, double c);
+const char* ws_name(void);
+static inline int ws_defined_here(int a) { return ws_f() + a; }
+"""
+
+
+def test_parser_on_literal_snippets():
+    from weasal_amd import _abi
+    abi = _abi.parse(_SNIPPET)
+    vp, i32 = C.c_void_p, C.c_int32
+    assert abi.constants == {"N": 8, "M": 4}
+    assert abi.structs["ws_s"] == [("a", vp), ("b", vp), ("v", i32 * 25), ("m", (i32 * 4) * 8), ("d", C.c_double),
+                                   ("u", C.c_uint8), ("name", C.c_char_p)]
+    assert C.sizeof(type("S", (C.Structure,), {"_fields_": abi.structs["ws_s"]})) == 16 + 100 + 128 + 4 + 8 + 8 + 8
+    assert abi.structs["ws_t"] == [("n", C.c_int64), ("p", vp)]
+    assert abi.prototypes == {
+        "ws_f": (C.c_int64, []),
+        "ws_g": (vp, [vp, C.c_int64, C.c_float, C.c_char_p, C.c_char_p, vp, vp]),
+        "ws_h": (None, [C.c_int, C.c_uint32, C.c_double]),
+        "ws_name": (C.c_char_p, []),
+    }
+
+
+@pytest.mark.parametrize("text, named", [
+    ("int ws_bad(unsigned long n);", "ws_bad"),                      # an unknown scalar type
+    ("int ws_bad2(size_t n);", "ws_bad2"),
+    ("long ws_bad3(void);", "ws_bad3"),
+    ("struct ws_s { int32_t a; }; int ws_by_value(struct ws_s s);", "ws_by_value"),      # a struct by value
+    ("typedef struct ws_s { int32_t a; } ws_s; int ws_by_value2(ws_s s, int32_t n);", "ws_by_value2"),
+    ("int ws_variadic(const char* fmt, ...);", "ws_variadic"),
+    ("struct ws_u { long double x; };", "ws_u"),
+    ("struct ws_v { int32_t a[K]; };", "ws_v"),                       # an extent that is no known constant
+    ("struct ws_w { int32_t a[]; };", "ws_w"),
+])
+def test_parser_refuses_what_it_cannot_type(text, named):
+    from weasal_amd import _abi
+    with pytest.raises(_abi.AbiError, match=r"\b%s\b" % named):
+        _abi.parse(text)
+
+
+def test_a_mutated_header_changes_the_table():
+    """the table comes from the text: one int32_t parameter widened and two struct fields swapped show in the result"""
+    from weasal_amd import _abi, _lib
+    text = open(_lib.HEADER_PATH).read()
+    real = _abi.parse(text)
+    old_proto = "int64_t ws_transpose_scratch_bytes(int64_t nq, int32_t h, int64_t ns);"
+    old_fields = "float *dw1, *db1, *dwk, *dbk, *dw2, *db2, *dws;"
+    assert text.count(old_proto) == 1 and text.count(old_fields) == 1
+    mutated = _abi.parse(text.replace(old_proto, old_proto.replace("int32_t h", "int64_t h"))
+                             .replace(old_fields, old_fields.replace("*dw2, *db2", "*db2, *dw2")))
+    assert real.prototypes["ws_transpose_scratch_bytes"] == (C.c_int64, [C.c_int64, C.c_int32, C.c_int64])
+    assert mutated.prototypes["ws_transpose_scratch_bytes"] == (C.c_int64, [C.c_int64, C.c_int64, C.c_int64])
+    names = [n for n, _ in real.structs["ws_kpblock"]]
+    swapped = [n for n, _ in mutated.structs["ws_kpblock"]]
+    i = names.index("dw2")
+    assert names[i:i + 2] == ["dw2", "db2"] and swapped[i:i + 2] == ["db2", "dw2"]
+    assert names[:i] + names[i + 2:] == swapped[:i] + swapped[i + 2:]
+    others = lambda abi: {k: v for k, v in abi.prototypes.items() if k != "ws_transpose_scratch_bytes"}
+    assert others(real) == others(mutated)
+
+
+def test_missing_header_fails_loudly(tmp_path):
+    from weasal_amd import _lib
+    with pytest.raises(_lib.WeasalHipError, match="weasal_hip.h"):
+        _lib.header_abi(str(tmp_path / "include" / "weasal_hip.h"))
+
+
 def test_env_switches_resolve():
     """every WEASAL_* variable that _lib.lib() maps onto a library switch names an integer global the library exports"""
     from weasal_amd import _lib

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+import priv_abi
 from oracle import gemm_branch_ref as R
 from weasal_amd import _lib
 
@@ -447,11 +448,7 @@ def run_xb(r):
             return lib.ws_gemm_xb_gated_strided(*common, P(biasd), P(resd), r["ldr"], 1 if r["act"] else 0, SLOPE, P(gyd), n, SLOPE,
                                                 P(mkd), n, mscale, yp, r["ldy"], P(scr), sb, st)
         if g["drop"] or r["rrows"]:
-            f = lib.ws_priv_gemm_xb_ex
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
-                          C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_uint64,
-                          C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+            f = priv_abi.entry("ws_priv_gemm_xb_ex")
             return f(*common, P(biasd), P(resd), r["ldr"], P(rrd), lay["rld"], rn, 1 if r["act"] else 0, SLOPE,
                      DROP_P if g["drop"] else 0.0, SEED, yp, r["ldy"], P(scr), sb, st)
         return lib.ws_gemm_xb_epilogue_strided(*common, P(biasd), P(resd), r["ldr"], 1 if r["act"] else 0, SLOPE, yp, r["ldy"], P(scr),
@@ -548,9 +545,7 @@ def run_xty(r):
     if r["bf16"]:
         _lib.check(lib.ws_gemm_xty_bf16(V(xp), m, k, r["ldx"], V(yp), n, r["ldy"], V(optr), _lib.ptr(scr), st))
     elif r["ldo"]:
-        f = lib.ws_priv_gemm_xty_pitched
-        f.restype = C.c_int
-        f.argtypes = [V, C.c_int64, C.c_int32, C.c_int64, V, C.c_int32, C.c_int64, V, C.c_int64, V, V]
+        f = priv_abi.entry("ws_priv_gemm_xty_pitched")
         _lib.check(f(V(xp), m, k, r["ldx"], V(yp), n, r["ldy"], V(optr), r["ldo"], _lib.ptr(scr), st))
     else:
         _lib.check(lib.ws_gemm_xty(V(xp), m, k, r["ldx"], V(yp), n, r["ldy"], V(optr), _lib.ptr(scr), st))
@@ -714,11 +709,7 @@ def test_dropout_bits_at_row_times_n():
     x = torch.zeros(m, k, device=DEV)
     b = torch.randn(k, n, device=DEV)
     bias = torch.ones(n, device=DEV)
-    f = lib.ws_priv_gemm_xb_ex
-    V = C.c_void_p
-    f.restype = C.c_int
-    f.argtypes = [V, C.c_int64, C.c_int32, C.c_int64, V, C.c_int64, C.c_int64, C.c_int32, V, V, C.c_int64, V, C.c_int64, C.c_int64,
-                  C.c_int32, C.c_float, C.c_float, C.c_uint64, V, C.c_int64, V, C.c_int64, V]
+    f = priv_abi.entry("ws_priv_gemm_xb_ex")
     y = torch.full((m, ldy), SENT, device=DEV)
     _lib.check(f(P(x), m, k, k, P(b), -1, 1, n, P(bias), None, 0, None, 1, 0, 0, 0.0, DROP_P, SEED, P(y), ldy, None, 0, st))
     ones = torch.ones(m, k, device=DEV)

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import priv_abi
 from oracle import gemm_branch_ref as R
 from weasal_amd import _lib
 
@@ -28,36 +29,14 @@ DROP_P = 0.3
 SEED = 0x1234567
 BIG_PITCH = 1 << 23
 V = C.c_void_p
-_i32, _i64, _f32 = C.c_int32, C.c_int64, C.c_float
-
-
-class XbProblem(C.Structure):
-    """mirror of `struct ws_xb_problem` (weasal_amd/csrc/ws_common.h)"""
-    _fields_ = [("x", V), ("m", _i64), ("k", _i32), ("ldx", _i64), ("b", V), ("b_row_stride", _i64), ("b_col_stride", _i64), ("n", _i32),
-                ("bias", V), ("residual", V), ("ldr", _i64), ("res_rows", V), ("res_rows_ld", _i64), ("res_nrows", _i64),
-                ("act", _i32), ("slope", _f32), ("gate_y", V), ("ldg", _i64), ("gate_slope", _f32), ("mask", V), ("ldm", _i64),
-                ("mask_scale", _f32), ("drop_p", _f32), ("drop_seed", C.c_uint64), ("y", V), ("ldy", _i64), ("scratch", V),
-                ("scratch_bytes", _i64)]
-
-
-class XtyProblem(C.Structure):
-    """mirror of `struct ws_xty_problem`"""
-    _fields_ = [("x", V), ("m", _i64), ("k", _i32), ("ldx", _i64), ("y", V), ("n", _i32), ("ldy", _i64), ("out", V), ("ldo", _i64),
-                ("scratch", V), ("scratch_bytes", _i64)]
+XbProblem = priv_abi.struct("ws_xb_problem")          # laid out as weasal_amd/csrc/ws_common.h declares them
+XtyProblem = priv_abi.struct("ws_xty_problem")
 
 
 def _bind():
-    lib = _lib.lib()
-    lib.ws_priv_gemm_xb_group.restype = C.c_int
-    lib.ws_priv_gemm_xb_group.argtypes = [V, _i32, V]
-    lib.ws_priv_gemm_xty_group.restype = C.c_int
-    lib.ws_priv_gemm_xty_group.argtypes = [V, _i32, V]
-    lib.ws_priv_gemm_xb_ex.restype = C.c_int
-    lib.ws_priv_gemm_xb_ex.argtypes = [V, _i64, _i32, _i64, V, _i64, _i64, _i32, V, V, _i64, V, _i64, _i64, _i32, _f32, _f32, C.c_uint64,
-                                       V, _i64, V, _i64, V]
-    lib.ws_priv_gemm_xty_pitched.restype = C.c_int
-    lib.ws_priv_gemm_xty_pitched.argtypes = [V, _i64, _i32, _i64, V, _i32, _i64, V, _i64, V, V]
-    return lib
+    for name in ("ws_priv_gemm_xb_group", "ws_priv_gemm_xty_group", "ws_priv_gemm_xb_ex", "ws_priv_gemm_xty_pitched"):
+        priv_abi.entry(name)
+    return _lib.lib()
 
 
 def _p(t):

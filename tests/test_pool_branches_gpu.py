@@ -29,6 +29,7 @@ import numpy as np
 import pytest
 import torch
 
+import priv_abi
 from oracle import pool_ref as P
 from weasal_amd import _lib, ops
 from weasal_amd._lib import check, current_stream, ptr
@@ -269,17 +270,9 @@ def max_bwd(dy, arg, table, order, shift=0):
     return dx
 
 
-_vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
-
-
 def u8_entries():
     """the byte-record forms: exported by the library, declared in csrc/ws_common.h (not in include/weasal_hip.h)"""
-    lib = _lib.lib()
-    fwd, bwd = lib.ws_priv_max_pool_fwd_u8, lib.ws_priv_max_pool_bwd_u8
-    fwd.restype = bwd.restype = C.c_int
-    fwd.argtypes = [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp]
-    bwd.argtypes = [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]
-    return fwd, bwd
+    return priv_abi.entry("ws_priv_max_pool_fwd_u8"), priv_abi.entry("ws_priv_max_pool_bwd_u8")
 
 
 def closest_fwd(x, inds):

@@ -520,6 +520,9 @@ int upunary_bwd(const ws_upunary* d, Arena& ar, hipStream_t st, bool run)
 
 extern "C" {
 
+int64_t ws_kpblock_bytes(void) { return (int64_t)sizeof(ws_kpblock); }
+int64_t ws_upunary_bytes(void) { return (int64_t)sizeof(ws_upunary); }
+
 int64_t ws_kpblock_fwd_scratch_bytes(const ws_kpblock* d)
 {
     if (check_kpblock(d)) return -1;

@@ -40,27 +40,13 @@ _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 
 class KPBlockDesc(C.Structure):
-    """mirror of `struct ws_kpblock` (include/weasal_hip.h), field by field"""
-    _fields_ = [("q_pts", _vp), ("nq", _i64), ("s_pts", _vp), ("ns", _i64), ("inds", _vp), ("h", _i32),
-                ("kernel_points", _vp), ("k", _i32), ("extent", _f32), ("order_q", _vp), ("order_s", _vp),
-                ("grid_blob", _vp), ("grid_nb", _i32), ("grid_cells", _i64), ("key_last", _vp), ("grid_radius", _f32),
-                ("grid_overflow", _vp), ("t_offsets", _vp), ("t_pairs", _vp),
-                ("in_dim", _i32), ("conv_in", _i32), ("conv_out", _i32), ("out_dim", _i32), ("strided", _i32),
-                ("slope", _f32),
-                ("w1", _vp), ("b1", _vp), ("wk", _vp), ("bk", _vp), ("w2", _vp), ("b2", _vp), ("ws", _vp), ("bs", _vp),
-                ("feat", _vp), ("x1", _vp), ("wf", _vp), ("x2", _vp), ("pooled", _vp), ("arg", _vp), ("out", _vp),
-                ("dout", _vp), ("dfeat", _vp), ("dw1", _vp), ("db1", _vp), ("dwk", _vp), ("dbk", _vp), ("dw2", _vp),
-                ("db2", _vp), ("dws", _vp), ("timed", _i32), ("rows_sorted", _i32), ("infer", _i32), ("dout_pregated", _i32),
-                ("gate_dfeat", _i32), ("dfeat_add", _vp)]
+    """`struct ws_kpblock`: the fields are read from include/weasal_hip.h"""
+    _fields_ = _lib.ABI.structs["ws_kpblock"]
 
 
 class UpUnaryDesc(C.Structure):
-    """mirror of `struct ws_upunary`"""
-    _fields_ = [("xc", _vp), ("nc", _i64), ("c_up", _i32), ("skip", _vp), ("nf", _i64), ("c_skip", _i32),
-                ("ups", _vp), ("h_up", _i32), ("t_offsets", _vp), ("t_pairs", _vp),
-                ("w", _vp), ("ldw", _i64), ("b", _vp), ("out_dim", _i32), ("relu", _i32), ("slope", _f32),
-                ("yc", _vp), ("out", _vp), ("dout", _vp), ("dxc", _vp), ("dskip", _vp), ("dw", _vp), ("db", _vp),
-                ("drop_p", _f32), ("drop_seed", C.c_uint64), ("dout_pregated", _i32), ("gate_dxc", _i32)]
+    """`struct ws_upunary`, likewise"""
+    _fields_ = _lib.ABI.structs["ws_upunary"]
 
 
 _GATES_SET = False

@@ -1408,19 +1408,9 @@ _SAMPLER_OUT = ('out_points', 'out_features', 'out_labels', 'out_input_inds', 'o
                 'out_cloud_inds', 'out_point_inds')
 
 
-def _sampler_items_fields():
-    import ctypes as C
-    vp = C.c_void_p
-    return [('h_draws', vp), ('h_colour_keep', vp), ('max_spheres', C.c_int32), ('resume', C.c_int32), ('batch_limit', C.c_int64),
-            ('in_radius', C.c_double), ('augment_noise', C.c_float), ('fd', C.c_int32), ('seed', C.c_uint64), ('seq0', C.c_uint64),
-            ('label_lut', vp), ('lut_n', C.c_int32), ('labels_zero', C.c_int32), ('update_potentials', C.c_int32),
-            ('random_centres', C.c_int32), ('epoch_inds', vp), ('n_centres', C.c_int64), ('epoch_i', vp)] \
-        + [(name, vp) for name in _SAMPLER_OUT] + [('capacity_rows', C.c_int64), ('d_state', vp), ('stream', vp)]
-
-
 class SamplerItems(__import__('ctypes').Structure):
-    """mirror of `struct ws_sampler_items` (include/weasal_hip.h)"""
-    _fields_ = _sampler_items_fields()
+    """`struct ws_sampler_items`: the fields are read from include/weasal_hip.h"""
+    _fields_ = _lib.ABI.structs["ws_sampler_items"]
 
 
 class SamplerHandle:

@@ -164,26 +164,15 @@ import ctypes as _C
 import os as _os
 import threading as _threading
 
+from . import _lib
+
 NATIVE_PYRAMID = _os.environ.get("WEASAL_NATIVE_PYRAMID", "1") != "0"     # A/B switch: 0 = the per-call loop above
-_ML, _MB = 8, 64          # WS_PYRAMID_MAX_LEVELS, WS_PYRAMID_MAX_BATCH
+_ML, _MB = _lib.ABI.constants["WS_PYRAMID_MAX_LEVELS"], _lib.ABI.constants["WS_PYRAMID_MAX_BATCH"]
 
 
 class PyramidDesc(_C.Structure):
-    """mirror of `struct ws_pyramid_desc` (include/weasal_hip.h)"""
-    _fields_ = ([("n_levels", _C.c_int32), ("nb", _C.c_int32), ("want_grids", _C.c_int32), ("want_tables", _C.c_int32),
-                 ("points", _C.c_void_p), ("n0", _C.c_int64), ("h_rot", _C.c_void_p),
-                 ("arena", _C.c_void_p), ("arena_bytes", _C.c_int64), ("scratch", _C.c_void_p), ("scratch_bytes", _C.c_int64),
-                 ("conv_on", _C.c_int32 * _ML), ("pool_on", _C.c_int32 * _ML),
-                 ("r_conv", _C.c_float * _ML), ("r_pool", _C.c_float * _ML), ("r_up", _C.c_float * _ML), ("dl", _C.c_float * _ML),
-                 ("limit", _C.c_int32 * (_ML + 1)), ("nearest_up", _C.c_int32),
-                 ("lens", (_C.c_int32 * _MB) * _ML),
-                 ("needed_bytes", _C.c_int64), ("n", _C.c_int64 * _ML)]
-                + [(name, _C.c_int64 * _ML) for name in ("off_points", "off_neighbors", "off_pools", "off_upsamples", "off_order",
-                                                          "off_key_last", "off_blob", "blob_bytes", "grid_cells")]
-                + [("off_lens", _C.c_int64), ("off_slots", _C.c_int64),
-                   ("max_count", _C.c_int32 * (3 * _ML)), ("width", _C.c_int32 * (3 * _ML)),
-                   ("final_width", _C.c_int32 * (3 * _ML)), ("cap", _C.c_int32 * (3 * _ML)),
-                   ("off_toffsets", _C.c_int64 * (3 * _ML)), ("off_tpairs", _C.c_int64 * (3 * _ML))])
+    """`struct ws_pyramid_desc`: the fields are read from include/weasal_hip.h"""
+    _fields_ = _lib.ABI.structs["ws_pyramid_desc"]
 
 
 _arena_hint = {}          # (device index, thread, n0, limits) -> bytes the previous batch of that shape needed
@@ -234,7 +223,6 @@ def segmentation_inputs_native(config, stacked_points, stacked_features, labels,
     """segmentation_inputs for device tensors with neighbourhood limits, through ws_pyramid_build: same flat list, same
     side lists (orders / grids / radii); every output is a view of one arena tensor.  `tables`: a dict that receives the
     pre-built transposed tables {"full": [(matrix, ns, table)], "col0": [(upsampling matrix, nc, table)]}."""
-    from . import _lib
     lib = _lib.lib()
     dev = stacked_points.device
     P0 = stacked_points.detach().to(torch.float32).contiguous()

@@ -698,6 +698,42 @@ int ws_potentials_update(const float* pot_points, int64_t n, const double* h_cen
                          double* out_min, int64_t* out_argmin, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The validation pass that closes every training epoch (csrc/validation.hip): utils/trainer_PseudoLabel.py:368-407
+ * (votes) and :423-436 with utils/metrics.py:35-110 (confusion); utils/trainer_WeakLabel.py:312- is the same routine.
+ * ws_validation_update: ONE launch for all nb spheres of a batch.  logits [n, c] float32 with leading dimension ld,
+ *   input_inds [n] int64, ASCENDING inside every sphere.  Per sphere b, HOST arrays [nb] that travel as kernel arguments
+ *   (no copy, no synchronisation): h_offsets (first row), h_lens, h_clouds (cloud id in [0, n_clouds)) and h_overlap, a
+ *   bit mask of the other spheres that may share points with b (bit b2 of word b must equal bit b of word b2; pairs on
+ *   different clouds and the sphere itself are dropped here).  Spheres lie in ascending, disjoint row ranges inside
+ *   [0, n); a row outside every range takes no part.  votes [n_clouds]: device table of the per-cloud vote buffers
+ *   [cloud_rows[k], c] float32, cloud_rows int64 [n_clouds] on the device.
+ *   Votes (:401-402): votes[cloud_b][inds_b] = smooth * votes[cloud_b][inds_b] + (1 - smooth) * softmax(logits_b) for
+ *   b = 0, 1, ... in order, in the float32 expressions of ws_vote_update.  A point listed by several spheres takes the
+ *   chain of updates in sphere order: the row in the last such sphere reads the vote row once, applies all of them and
+ *   writes it once; no other row touches it (no atomics on floats, the same bits on every run).  radius_mask > 0 (the
+ *   test loop, utils/tester_PseudoLabel.py:168-194): only rows with sum(points^2) < radius_mask^2 take part, as updates
+ *   and as owners; points [n,3] may be NULL otherwise.
+ *   Confusion (labels != NULL): for EVERY row in a sphere, whatever the mask, k = the first maximum of its float32
+ *   softmax; confusion[true_row[labels[i]] * nc + pred_row[k]] += 1.  true_row int32 [n_true] and pred_row int32 [c] on
+ *   the device carry fast_confusion's label_map for the truth position and the predicted value (validation.py:
+ *   confusion_tables); confusion int64 [nc, nc], ACCUMULATED.  labels == NULL: votes only, nc / tables / confusion unused.
+ *   status: WS_VAL_STATUS_WORDS int64 on the device, accumulated, never a fault: [WS_VAL_UNSORTED] += 1 per row whose
+ *   index is not above its predecessor's in the same sphere (the votes of that batch are then unspecified, every access
+ *   stays in bounds); [WS_VAL_BAD_INDEX] += 1 per row whose index is outside [0, cloud_rows[cloud]) (skipped, in the
+ *   votes and in every chain); [WS_VAL_BAD_LABEL] += 1 per row whose label is outside [0, n_true) or whose table entry is
+ *   outside [0, nc) (left out of the confusion).
+ *   c, nc <= 64 and nb <= WS_PYRAMID_MAX_BATCH, else WS_ERR_UNSUPPORTED; other bad sizes, a NULL required pointer or an
+ *   inconsistent host array: WS_ERR_INVALID; n == 0: WS_OK and nothing is queued; all found before the device is touched.
+ *   The launch is queued on `stream`; nothing synchronises and nothing is read back.
+ * ------------------------------------------------------------------------------------------ */
+enum { WS_VAL_UNSORTED = 0, WS_VAL_BAD_INDEX = 1, WS_VAL_BAD_LABEL = 2, WS_VAL_STATUS_WORDS = 3 };
+int ws_validation_update(const float* logits, int64_t n, int32_t c, int64_t ld, const int64_t* input_inds, const int64_t* labels,
+                         const float* points, float radius_mask, const int64_t* h_offsets, const int32_t* h_lens,
+                         const int32_t* h_clouds, const uint64_t* h_overlap, int32_t nb, float* const* votes,
+                         const int64_t* cloud_rows, int32_t n_clouds, float smooth, const int32_t* true_row, int32_t n_true,
+                         const int32_t* pred_row, int32_t nc, int64_t* confusion, int64_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Active-learning selection on the votes of a pass over the training clouds (csrc/active.hip).
  * ws_al_point_scores: utils/tester_PseudoLabel.py:400-414 -- per row of probs [n,c] (float32 votes, c <= 32, else
  *   WS_ERR_UNSUPPORTED): entropy = -sum_k p_k * log2f(p_k + 1e-12f), float32, summed in column order; preds = the first

@@ -149,6 +149,91 @@ class VoteAccumulator:
                                      ptr(inds[i0:i0 + n]), ptr(p), p.shape[0], self.smooth, current_stream()))
             i0 += n
 
+    def _tables(self):
+        """(device table of the vote buffers' addresses, device int64 row counts), rebuilt when a buffer was replaced"""
+        key = tuple(p.data_ptr() for p in self.probs)
+        if getattr(self, "_table_key", None) != key:
+            for p in self.probs:
+                if p.dtype != torch.float32 or not p.is_contiguous() or p.dim() != 2 or p.shape[1] != self.c:
+                    raise ValueError("every vote buffer must be a contiguous float32 [N, %d] tensor" % self.c)
+            self._table = torch.tensor(key, dtype=torch.int64).to(self.device)
+            self._table_rows = torch.tensor([p.shape[0] for p in self.probs], dtype=torch.int64).to(self.device)
+            self._table_key = key
+        return self._table, self._table_rows
+
+    def update_batch(self, logits, lengths, input_inds, cloud_inds, points0=None, radius_mask=0.0, overlap=None, status=None,
+                     labels=None, true_row=None, pred_row=None, confusion=None):
+        """update() for all spheres of a batch in ONE launch (ws_validation_update), without any device-to-host read.
+
+        lengths / cloud_inds: HOST values per sphere (array, list or CPU tensor; a device tensor raises: reading it would
+        block).  input_inds must ascend inside every sphere, as the sphere sampler delivers them.  overlap: uint64 [B], bit
+        b2 of word b set when spheres b and b2 may share points (validation.overlap_from_centres); None = every pair on
+        the same cloud.  A point that several spheres list gets their updates in sphere order, exactly like the loop of
+        update().  status: int64 [3] device words (weasal_hip.h: WS_VAL_*) the launch adds its counts to; None: the words
+        kept in `self.batch_status` (validation.raise_on_status(self.batch_status.cpu()) reads them, when the caller
+        chooses to).  labels / true_row / pred_row / confusion: the epoch confusion of validation.Validator."""
+        lib = _lib.lib()
+        ops._need_cuda(logits, input_inds, points0, status, labels, true_row, pred_row, confusion)
+        for name, v in (("lengths", lengths), ("cloud_inds", cloud_inds), ("overlap", overlap)):
+            if isinstance(v, torch.Tensor) and v.is_cuda:
+                raise ValueError("update_batch: %s must be on the host (a device tensor would need a blocking read)" % name)
+        lens = np.ascontiguousarray(np.asarray(lengths).reshape(-1), dtype=np.int32)
+        clouds = np.ascontiguousarray(np.asarray(cloud_inds).reshape(-1), dtype=np.int32)
+        nb = lens.shape[0]
+        if clouds.shape[0] != nb:
+            raise ValueError("update_batch: %d lengths for %d cloud ids" % (nb, clouds.shape[0]))
+        if nb == 0 or int(lens.sum()) == 0:
+            return
+        if overlap is None:
+            same = clouds[:, None] == clouds[None, :]
+            np.fill_diagonal(same, False)
+            masks = (same.astype(np.uint64) << np.arange(nb, dtype=np.uint64)[None, :]).sum(axis=1, dtype=np.uint64)
+        else:
+            masks = np.asarray(overlap).reshape(-1).astype(np.uint64)
+            if masks.shape[0] != nb:
+                raise ValueError("update_batch: overlap must hold one mask per sphere")
+        masks = np.ascontiguousarray(masks)
+        offs = np.ascontiguousarray(np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.int64)]), dtype=np.int64)
+        lg = logits.detach()
+        if lg.dtype != torch.float32 or lg.dim() != 2 or lg.stride(1) != 1 or lg.stride(0) < lg.shape[1]:
+            lg = lg.float().contiguous()
+        n = lg.shape[0]
+        if lg.shape[1] != self.c or int(lens.sum()) != n:
+            raise ValueError("update_batch: logits must be [sum(lengths) = %d, %d]" % (int(lens.sum()), self.c))
+        inds = input_inds.detach().to(torch.int64).contiguous()
+        if inds.shape != (n,):
+            raise ValueError("update_batch: input_inds must hold one index per row of the logits")
+        pts = None
+        if radius_mask > 0:
+            if points0 is None:
+                raise ValueError("update_batch: a radius mask needs points0")
+            pts = ops._f32c(points0)
+            if pts.shape != (n, 3):
+                raise ValueError("update_batch: points0 must be [%d, 3]" % n)
+        if status is None:
+            if getattr(self, "batch_status", None) is None:
+                self.batch_status = torch.zeros(3, dtype=torch.int64, device=self.device)
+            status = self.batch_status
+        lab, n_true, nc = None, 0, 0
+        if labels is not None:
+            lab = labels.detach().reshape(-1).to(torch.int64).contiguous()
+            if lab.shape[0] != n:
+                raise ValueError("update_batch: labels must hold one label per row of the logits")
+            if true_row is None or pred_row is None or confusion is None:
+                raise ValueError("update_batch: labels need true_row, pred_row and a confusion matrix")
+            if true_row.dtype != torch.int32 or pred_row.dtype != torch.int32 or pred_row.shape[0] != self.c:
+                raise ValueError("update_batch: true_row / pred_row must be int32, pred_row with one entry per vote column")
+            if confusion.dtype != torch.int64 or confusion.dim() != 2 or confusion.shape[0] != confusion.shape[1] \
+                    or not confusion.is_contiguous():
+                raise ValueError("update_batch: confusion must be a contiguous int64 [nc, nc] tensor (accumulated in place)")
+            n_true, nc = true_row.shape[0], confusion.shape[0]
+        table, rows = self._tables()
+        hp = lambda a: C.c_void_p(a.ctypes.data)
+        check(lib.ws_validation_update(ptr(lg), n, self.c, lg.stride(0), ptr(inds), ptr(lab), ptr(pts), float(radius_mask),
+                                       hp(offs), hp(lens), hp(clouds), hp(masks), nb, ptr(table), ptr(rows), len(self.probs),
+                                       self.smooth, ptr(true_row), n_true, ptr(pred_row), nc, ptr(confusion), ptr(status),
+                                       current_stream()))
+
     def predictions(self, cloud, proj=None, labels=None, label_values=None, ignored_labels=()):
         """-> (preds int32 [M] as label VALUES, confusion int64 [C, C] or None): arg-max of the (re-projected) votes and
         the confusion against `labels` (label values; mapped to positions in the sorted label_values like fast_confusion).

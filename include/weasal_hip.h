@@ -240,6 +240,21 @@ int ws_radius_neighbors_search_async(ws_neighbors_ws* ws,
                                      const int32_t* h_q_lens, const int32_t* h_s_lens, int32_t nb,
                                      float radius, int32_t width, int32_t* out_i32, int64_t* out_i64,
                                      int32_t* d_max_count, void* stream);
+/* Count-only search for the neighbourhood-limit calibration (datasets/DALES_PseudoLabel.py:1238-1240): the arguments of
+ * ws_radius_neighbors_plan without the host count; builds the cell grid as the plan does, then ADDS to hist[c] (DEVICE int64
+ * [hist_n], zeroed by the caller once per calibration) the number of queries with exactly c supports inside the radius.  A
+ * count of hist_n or more is dropped, as np.bincount(c, minlength=hist_n)[:hist_n] does (:1239).  No row, no per-query count
+ * (ws_radius_neighbors_counts is not refreshed) and no device-to-host read: nothing synchronises beyond the staging copy of
+ * the per-element table for nb > 48.  Integer atomics only -- per workgroup a histogram in LDS, flushed once with 64-bit adds
+ * -- so the bins are bit-identical from run to run.  1 <= hist_n <= WS_NB_HIST_MAX (32 KB of LDS per workgroup; the
+ * reference's histogram size ceil(4/3 pi (deform_radius + 1)^3) is 5576 at deform_radius 10): hist_n < 1 is WS_ERR_INVALID,
+ * above the maximum WS_ERR_UNSUPPORTED, both found before the device is touched.  WS_ERR_EMPTY for nq == 0 or ns == 0, as
+ * the plan.  A fill after it needs a plan of its own. */
+#define WS_NB_HIST_MAX 8192
+int ws_radius_neighbors_histogram(ws_neighbors_ws* ws,
+                                  const float* queries, int64_t nq, const float* supports, int64_t ns,
+                                  const int32_t* h_q_lens, const int32_t* h_s_lens, int32_t nb,
+                                  float radius, int64_t* hist, int32_t hist_n, void* stream);
 /* Nearest neighbour only (opt-in): out [nq] = column 0 of the row ws_radius_neighbors_search_async would write -- the support
  * with the smallest (distance, index) inside `radius`, or ns -- without building and sorting the row.  For the UPSAMPLING
  * searches of the pyramid, of which KP-FCNN reads the first column only (models/blocks.py:80-92); *d_any (device) becomes
@@ -410,6 +425,23 @@ typedef struct ws_pyramid_desc {
 } ws_pyramid_desc;
 int ws_pyramid_build(ws_neighbors_ws* nws, ws_subsample_ws* sws, ws_pyramid_desc* desc, void* stream);
 int64_t ws_pyramid_desc_bytes(void);   /* sizeof(ws_pyramid_desc): lets a binding check its mirror of the struct */
+
+/* The pyramid of one calibration batch, count-only (DALES_PseudoLabel.py:1238-1240 reads one number per point and layer of
+ * an un-limited batch: how many supports lie inside the convolution radius).  Per level with conv_on one
+ * ws_radius_neighbors_histogram of the level's points against themselves at r_conv[l], ADDED to row l of `hists` (device
+ * int64 [n_levels][hist_n], zeroed by the caller once per calibration); per level with pool_on the rotation, grid
+ * subsampling and back rotation of ws_pyramid_build (the same code), which give the next level.  No index matrix, no pool or
+ * upsample search, no table, no arena.
+ * Reads of `desc`: n_levels, nb, points, n0, h_rot, conv_on, pool_on, r_conv, dl, lens[0], scratch, scratch_bytes (at least
+ * ws_pyramid_histograms_scratch_bytes(n0) = 2 * align256(12 n0), 256-byte aligned); the limits, the arena and the
+ * want-flags are ignored.  Writes lens[l] and n[l] of every level, nothing else.
+ * Host waits: the ones ws_grid_subsample_plan makes, one per pooling level = n_levels - 1 per batch (the next level's size
+ * is data); the count passes and their flushes are queued behind them without a read.
+ * hist_n as ws_radius_neighbors_histogram; a NULL argument or inconsistent sizes: WS_ERR_INVALID; all found before the device
+ * is touched.  WS_ERR_EMPTY where ws_pyramid_build returns it (a level subsampled to nothing). */
+int64_t ws_pyramid_histograms_scratch_bytes(int64_t n0);
+int ws_pyramid_histograms(ws_neighbors_ws* nws, ws_subsample_ws* sws, ws_pyramid_desc* desc, int64_t* hists, int32_t hist_n,
+                          void* stream);
 
 
 

@@ -201,6 +201,50 @@ __global__ __launch_bounds__(256) void nb_count_kernel(const float* __restrict__
     nb_publish_max(max_count, local_max, lane);
 }
 
+// Count-only pass of the neighbourhood-limit calibration (datasets/DALES_PseudoLabel.py:1238-1240): the walk of nb_count_kernel,
+// but what leaves the wave is one increment of bin [count] instead of a row length.  The bins of a workgroup's range live in
+// LDS (hist_n ints, dynamic): one LDS add per query, by lane 0.  Only when the range is done do the non-zero bins go to `hist`,
+// as 64-bit adds -- once per workgroup, not per query (see nb_publish_max for the price of per-wave atomics on one word).
+// A count of hist_n or more is dropped: np.bincount(c, minlength=hist_n)[:hist_n] (:1239).  Integer adds only: the result
+// does not depend on the arrival order.
+__global__ __launch_bounds__(256) void nb_hist_kernel(const float* __restrict__ queries, int64_t nq,
+                                                       const CloudGrid* __restrict__ grids, int nb,
+                                                       const int32_t* __restrict__ cell_start,
+                                                       const float4* __restrict__ sorted, float r2,
+                                                       const int32_t* __restrict__ qorder,
+                                                       unsigned long long* __restrict__ hist, int hist_n)
+{
+    extern __shared__ int nb_hist_bins[];      // [hist_n]; a workgroup's range is < 2^31 queries
+    for (int i = threadIdx.x; i < hist_n; i += 256) nb_hist_bins[i] = 0;
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    int64_t ibeg, iend;
+    ws_block_range(nq, ibeg, iend);
+    int b = 0;
+    CloudGrid g = grids[0];
+    for (int64_t it = ibeg + wave; it < iend; it += 4) {
+        const int64_t q = qorder ? (int64_t)qorder[it] : it;
+        if (q < g.q_base || q >= g.q_base + g.q_len) {
+            b = find_cloud_q(grids, nb, q);
+            g = grids[b];
+        }
+        const float qx = queries[3 * q], qy = queries[3 * q + 1], qz = queries[3 * q + 2];
+        int cnt = 0;
+        if (g.s_len > 0) {
+            for_each_candidate(g, qx, qy, qz, cell_start, sorted, lane, [&](const float4& c, bool active) {
+                const bool hit = active && ref_d2(qx, qy, qz, c) < r2;
+                cnt += __builtin_popcountll(__ballot(hit));
+            });
+        }
+        if (lane == 0 && cnt < hist_n) atomicAdd(&nb_hist_bins[cnt], 1);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < hist_n; i += 256) {
+        const int v = nb_hist_bins[i];
+        if (v) atomicAdd(&hist[i], (unsigned long long)v);
+    }
+}
+
 template <int CAP, typename OutT>
 __global__ __launch_bounds__(256) void nb_fill_kernel(const float* __restrict__ queries, int64_t nq,
                                                        const CloudGrid* __restrict__ grids, int nb,
@@ -1010,6 +1054,27 @@ int ws_radius_neighbors_search_async(ws_neighbors_ws* ws, const float* queries, 
     WS_HIP(hipMemcpyAsync(d_max_count, ws->max_count_word, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     ws->max_count_host = cap;   // unknown on the host; rows beyond the slab are reported through d_max_count
     return WS_OK;
+}
+
+int ws_radius_neighbors_histogram(ws_neighbors_ws* ws, const float* queries, int64_t nq, const float* supports,
+                                  int64_t ns, const int32_t* h_q_lens, const int32_t* h_s_lens, int32_t nb,
+                                  float radius, int64_t* hist, int32_t hist_n, void* stream)
+{
+    KeyLastGuard guard{ws};
+    WS_REQUIRE(hist, "NULL argument");
+    WS_REQUIRE(hist_n >= 1, "hist_n must be >= 1");
+    if (hist_n > WS_NB_HIST_MAX)
+        return ws_fail(WS_ERR_UNSUPPORTED, "hist_n = %d exceeds the %d bins a workgroup keeps in LDS", hist_n, WS_NB_HIST_MAX);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = nb_prepare(ws, queries, nq, supports, ns, h_q_lens, h_s_lens, nb, radius, st);
+    if (rc) { if (ws) ws->nq = 0; return rc; }
+    // at least 16 queries per workgroup (4 per wave) behind every flush; the grid cap of the asynchronous entries
+    const int grid = ws_grid(nq, 16, NB_MAX_BLOCKS);
+    nb_hist_kernel<<<grid, 256, sizeof(int) * (size_t)hist_n, st>>>(queries, nq, ws->grids.p, nb, ws->cell_start.p, ws->sorted.p, ws->r2,
+                                                                     ws->self_query ? ws->order.p : nullptr,
+                                                                     reinterpret_cast<unsigned long long*>(hist), hist_n);
+    WS_LAUNCH_CHECK();
+    return WS_OK;       // no row lengths on the host: ws->max_count_host stays 0, a fill needs a plan of its own
 }
 
 int ws_radius_neighbors_nearest_async(ws_neighbors_ws* ws, const float* queries, int64_t nq, const float* supports,

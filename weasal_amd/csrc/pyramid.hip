@@ -35,6 +35,47 @@ __global__ __launch_bounds__(256) void pyr_trim_kernel(const int64_t* __restrict
         dst[i] = src[(i / mc) * w + (i % mc)];
 }
 
+// Level l -> level l + 1: rotation (with h_rot), grid subsampling, back rotation -- the per-level body of phase A, shared by
+// ws_pyramid_build and ws_pyramid_histograms.  The plan synchronises (the next level's size is data) and fills lens[l + 1] and
+// n[l + 1]; `place(m)` then names where the m points go, or nullptr: they stay in a scratch half (tmp_a / tmp_b, each
+// align256(12 n0) bytes), never the one that holds this level's input.  *next = the points of level l + 1.
+template <typename Place>
+int pyr_subsample_level(ws_subsample_ws* sws, ws_pyramid_desc* d, int l, const float* pts_l, float* tmp_a, float* tmp_b,
+                        Place&& place, const float** next, hipStream_t st)
+{
+    const int nb = d->nb;
+    int rc;
+    const float* src = pts_l;
+    const float* rot = d->h_rot ? d->h_rot + (size_t)l * nb * 9 : nullptr;
+    if (rot) {
+        if ((rc = ws_rotate_clouds_host(src, d->n[l], d->lens[l], nb, rot, 0, tmp_a, st))) return rc;
+        src = tmp_a;
+    }
+    int64_t m = 0;
+    if ((rc = ws_grid_subsample_plan(sws, src, d->n[l], d->lens[l], nb, d->dl[l], 0, WS_ORDER_REFERENCE, d->lens[l + 1], &m, st)))
+        return rc;
+    d->n[l + 1] = m;
+    float* dst = place(m);
+    float* spare = (pts_l == tmp_b) ? tmp_a : tmp_b;
+    if (rot) {
+        // src = tmp_a (rotated copy); the subsampled points go to tmp_b, then back-rotated to their place.  Without a
+        // place: tmp_b -> tmp_a (the rotated input is not needed any more), and tmp_a is the next level's input
+        if ((rc = ws_grid_subsample_fill(sws, nullptr, 0, nullptr, 0, tmp_b, nullptr, nullptr, nullptr, nullptr, st))) return rc;
+        float* back = dst ? dst : tmp_a;
+        if ((rc = ws_rotate_clouds_host(tmp_b, m, d->lens[l + 1], nb, rot, 1, back, st))) return rc;
+        if (!dst) {     // the next round rotates the next level INTO tmp_a: move it out of the way first
+            WS_HIP(hipMemcpyAsync(tmp_b, tmp_a, (size_t)m * 12, hipMemcpyDeviceToDevice, st));
+            *next = tmp_b;
+        } else *next = dst;
+    } else {
+        float* out = dst ? dst : spare;
+        if ((rc = ws_grid_subsample_fill(sws, nullptr, 0, nullptr, 0, out, nullptr, nullptr, nullptr, nullptr, st))) return rc;
+        *next = out;
+    }
+    if (m == 0) return ws_fail(WS_ERR_EMPTY, "Error");
+    return WS_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t ws_pyramid_desc_bytes(void) { return (int64_t)sizeof(ws_pyramid_desc); }
@@ -71,38 +112,13 @@ extern "C" int ws_pyramid_build(ws_neighbors_ws* nws, ws_subsample_ws* sws, ws_p
     for (int l = 0; l < L; ++l) {
         last_level = l;
         if (!d->pool_on[l]) break;
-        const float* src = pts[l];
-        const float* rot = d->h_rot ? d->h_rot + (size_t)l * nb * 9 : nullptr;
-        if (rot) {
-            if ((rc = ws_rotate_clouds_host(src, d->n[l], d->lens[l], nb, rot, 0, tmp_a, st))) return rc;
-            src = tmp_a;
-        }
-        int64_t m = 0;
-        if ((rc = ws_grid_subsample_plan(sws, src, d->n[l], d->lens[l], nb, d->dl[l], 0, WS_ORDER_REFERENCE, d->lens[l + 1], &m, st)))
-            return rc;
-        d->n[l + 1] = m;
-        d->off_points[l + 1] = A.take(m * 12);
-        const bool fits = A.used <= A.cap;
         // an arena that is already too small: keep going through the scratch halves only, to learn every level's size
-        // (`needed_bytes` for the caller's second attempt); the scratch half that holds this level's input is never the target
-        float* spare = (pts[l] == tmp_b) ? tmp_a : tmp_b;
-        float* dst = fits ? (float*)(A.base + d->off_points[l + 1]) : nullptr;
-        if (rot) {
-            // src = tmp_a (rotated copy); the subsampled points go to tmp_b, then back-rotated to their place.  Without a
-            // place: tmp_b -> tmp_a (the rotated input is not needed any more), and tmp_a is the next level's input
-            if ((rc = ws_grid_subsample_fill(sws, nullptr, 0, nullptr, 0, tmp_b, nullptr, nullptr, nullptr, nullptr, st))) return rc;
-            float* back = dst ? dst : tmp_a;
-            if ((rc = ws_rotate_clouds_host(tmp_b, m, d->lens[l + 1], nb, rot, 1, back, st))) return rc;
-            if (!dst) {     // the next round rotates pts[l + 1] INTO tmp_a: move it out of the way first
-                WS_HIP(hipMemcpyAsync(tmp_b, tmp_a, (size_t)m * 12, hipMemcpyDeviceToDevice, st));
-                pts[l + 1] = tmp_b;
-            } else pts[l + 1] = dst;
-        } else {
-            float* out = dst ? dst : spare;
-            if ((rc = ws_grid_subsample_fill(sws, nullptr, 0, nullptr, 0, out, nullptr, nullptr, nullptr, nullptr, st))) return rc;
-            pts[l + 1] = out;
-        }
-        if (m == 0) return ws_fail(WS_ERR_EMPTY, "Error");
+        // (`needed_bytes` for the caller's second attempt)
+        auto place = [&](int64_t m) -> float* {
+            d->off_points[l + 1] = A.take(m * 12);
+            return A.used <= A.cap ? (float*)(A.base + d->off_points[l + 1]) : nullptr;
+        };
+        if ((rc = pyr_subsample_level(sws, d, l, pts[l], tmp_a, tmp_b, place, &pts[l + 1], st))) return rc;
     }
     const int levels = last_level + 1;
     WS_REQUIRE(levels == L, "n_levels = %d but the pooling flags end the pyramid at level %d", L, levels);
@@ -259,5 +275,50 @@ extern "C" int ws_pyramid_build(ws_neighbors_ws* nws, ws_subsample_ws* sws, ws_p
                     return rc;
             } else d->off_toffsets[3 * l + 2] = -1;
         }
+    return WS_OK;
+}
+
+extern "C" int64_t ws_pyramid_histograms_scratch_bytes(int64_t n0) { return n0 >= 0 ? 2 * al256(n0 * 12) : 0; }
+
+// The count-only pyramid of the calibration: level by level one histogram pass, then the subsampling step of ws_pyramid_build.
+// Every level's points but the caller's live in the two scratch halves (the branch ws_pyramid_build takes without an arena).
+extern "C" int ws_pyramid_histograms(ws_neighbors_ws* nws, ws_subsample_ws* sws, ws_pyramid_desc* d, int64_t* hists, int32_t hist_n,
+                                     void* stream)
+{
+    WS_REQUIRE(nws && sws && d && hists, "NULL argument");
+    WS_REQUIRE(hist_n >= 1, "hist_n must be >= 1");
+    if (hist_n > WS_NB_HIST_MAX)
+        return ws_fail(WS_ERR_UNSUPPORTED, "hist_n = %d exceeds the %d bins a workgroup keeps in LDS", hist_n, WS_NB_HIST_MAX);
+    WS_REQUIRE(d->n_levels >= 1 && d->n_levels <= WS_PYRAMID_MAX_LEVELS, "1 <= n_levels <= %d", WS_PYRAMID_MAX_LEVELS);
+    WS_REQUIRE(d->nb >= 1 && d->nb <= WS_PYRAMID_MAX_BATCH, "1 <= nb <= %d batch elements", WS_PYRAMID_MAX_BATCH);
+    WS_REQUIRE(d->points && d->scratch && d->n0 >= 1, "NULL argument / empty batch");
+    hipStream_t st = (hipStream_t)stream;
+    const int L = d->n_levels, nb = d->nb;
+    int64_t sum0 = 0;
+    for (int b = 0; b < nb; ++b) { WS_REQUIRE(d->lens[0][b] >= 0, "negative batch length"); sum0 += d->lens[0][b]; }
+    WS_REQUIRE(sum0 == d->n0, "batch lengths do not sum to the point count");
+    WS_REQUIRE(d->scratch_bytes >= 2 * al256(d->n0 * 12), "scratch too small: 2 x n0 x 12 bytes (256-byte aligned) needed");
+    WS_REQUIRE(((uintptr_t)d->scratch & 255) == 0, "scratch must be 256-byte aligned");
+    for (int l = 0; l < L; ++l) {
+        if (l + 1 < L) WS_REQUIRE(d->pool_on[l] && d->dl[l] > 0.0f, "n_levels = %d but the pooling flags end the pyramid at level %d", L, l + 1);
+        else WS_REQUIRE(!d->pool_on[l], "a pooling level needs a next level");
+        if (d->conv_on[l]) WS_REQUIRE(d->r_conv[l] > 0.0f, "level %d: the convolution radius must be positive", l);
+    }
+    d->n[0] = d->n0;
+    float* tmp_a = (float*)d->scratch;
+    float* tmp_b = (float*)((char*)d->scratch + al256(d->n0 * 12));
+    const float* pts = d->points;
+    int rc;
+    for (int l = 0; l < L; ++l) {
+        // the count pass reads this level's points before the subsampling below may reuse their scratch half (same stream)
+        if (d->conv_on[l] &&
+            (rc = ws_radius_neighbors_histogram(nws, pts, d->n[l], pts, d->n[l], d->lens[l], d->lens[l], nb, d->r_conv[l],
+                                                hists + (int64_t)l * hist_n, hist_n, st)))
+            return rc;
+        if (!d->pool_on[l]) break;
+        const float* next = nullptr;
+        if ((rc = pyr_subsample_level(sws, d, l, pts, tmp_a, tmp_b, [](int64_t) -> float* { return nullptr; }, &next, st))) return rc;
+        pts = next;
+    }
     return WS_OK;
 }

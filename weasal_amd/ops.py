@@ -963,6 +963,27 @@ def radius_neighbors(queries, supports, q_lens, s_lens, radius, limit=None, dtyp
     return res[0] if len(res) == 1 else tuple(res)
 
 
+def radius_neighbors_histogram(queries, supports, q_lens, s_lens, radius, hist):
+    """Count-only radius search (ws_radius_neighbors_histogram): ADDS to hist[c] (device int64 [hist_n], contiguous) the
+    number of queries with exactly c supports inside `radius`; counts of hist_n or more are dropped
+    (datasets/DALES_PseudoLabel.py:1238-1240).  No row is written and nothing is read back.  -> hist"""
+    import ctypes as C
+    lib = _lib.lib()
+    _need_cuda(queries, supports, hist)
+    q = _f32c(queries)
+    s = _f32c(supports)
+    ql, sl = _host_lens(q_lens), _host_lens(s_lens)
+    if ql.shape[0] != sl.shape[0]:
+        raise RuntimeError("Wrong number of batch elements: different for queries and supports ")
+    if hist.dtype != torch.int64 or hist.dim() != 1 or not hist.is_contiguous():
+        raise ValueError("hist must be a contiguous int64 [hist_n] tensor")
+    with torch.cuda.device(q.device):
+        check(lib.ws_radius_neighbors_histogram(_ws.neighbors(q.device), ptr(q), q.shape[0], ptr(s), s.shape[0],
+                                                C.c_void_p(ql.ctypes.data), C.c_void_p(sl.ctypes.data), ql.shape[0],
+                                                float(np.float32(radius)), ptr(hist), hist.shape[0], current_stream()))
+    return hist
+
+
 def widen_async_slabs(max_count):
     """a row overflowed the width-sized slab of the asynchronous search (ws_radius_neighbors_async_cap: 5/4 of the limit): this
     data has longer tails than that -- from now on the process uses the full 1024-entry slab for wide rows, so that the

@@ -246,19 +246,8 @@ def segmentation_inputs_native(config, stacked_points, stacked_features, labels,
         d.lens[0][b] = int(lens0[b])
     rots = None
     if random_grid_orient:
-        # the reference's draws, level by level (theta, phi, alpha per call: datasets/common.py:99-121)
-        rand = np.random.rand if rng is None else rng.rand
-        mats = []
-        for lv in levels:
-            if not lv["pool_on"]:
-                continue
-            theta = rand(B) * 2 * np.pi
-            phi = (rand(B) - 0.5) * np.pi
-            u = np.vstack([np.cos(theta) * np.cos(phi), np.sin(theta) * np.cos(phi), np.sin(phi)])
-            alpha = rand(B) * 2 * np.pi
-            mats.append(create_3D_rotations(u.T, alpha).astype(np.float32))
-        if mats:
-            rots = np.ascontiguousarray(np.stack(mats), dtype=np.float32)
+        rots = _draw_grid_orientations(levels, B, rng)
+        if rots is not None:
             d.h_rot = rots.ctypes.data
     al = lambda v: (int(v) + 255) // 256 * 256
     # temporaries: two point buffers; the largest matrix (cropped copy) / the largest table's scratch (both <= n0 * widest row)
@@ -368,6 +357,61 @@ def segmentation_inputs_native(config, stacked_points, stacked_features, labels,
         tables["full"], tables["col0"] = full, col0
     _last_host_lengths.value = lens_host
     return points + neighbors + pools + upsamples + [lens_all[l] for l in range(L)] + [stacked_features, labels]
+
+
+def _draw_grid_orientations(levels, B, rng):
+    """the reference's draws for one batch, level by level (theta, phi, alpha per call: datasets/common.py:99-121), in the
+    calls and order of segmentation_inputs_native -> float32 [pooling levels, B, 3, 3] or None"""
+    rand = np.random.rand if rng is None else rng.rand
+    mats = []
+    for lv in levels:
+        if not lv["pool_on"]:
+            continue
+        theta = rand(B) * 2 * np.pi
+        phi = (rand(B) - 0.5) * np.pi
+        u = np.vstack([np.cos(theta) * np.cos(phi), np.sin(theta) * np.cos(phi), np.sin(phi)])
+        alpha = rand(B) * 2 * np.pi
+        mats.append(create_3D_rotations(u.T, alpha).astype(np.float32))
+    return np.ascontiguousarray(np.stack(mats), dtype=np.float32) if mats else None
+
+
+def neighbor_histograms(config, points, lengths, hists, random_grid_orient=True, rng=None):
+    """The un-limited pyramid of one calibration batch, count-only (ws_pyramid_histograms): per level the number of points
+    with c supports inside the convolution radius is ADDED to hists[level, c] (device int64 [levels, hist_n], contiguous;
+    counts of hist_n or more are dropped), the grid subsampling gives the next level, nothing else runs -- no index matrix.
+    The levels are those of `_schedule(config, ())`; the grid orientations come from `np.random` (or `rng`) in the calls
+    and order of segmentation_inputs_native, so a seeded batch sees the subsampled levels `build_batch` gives it under that
+    seed.  Nothing is read back but the level sizes (one wait per pooling level).  -> host int32 lengths per level"""
+    lib = _lib.lib()
+    if not points.is_cuda:
+        raise _lib.WeasalHipError("neighbor_histograms needs device tensors (there is no CPU fallback)")
+    dev = points.device
+    P0 = points.detach().to(torch.float32).contiguous()
+    lens0 = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int32)
+    levels = _schedule(config, ())
+    L, B, n0 = len(levels), len(lens0), int(P0.shape[0])
+    if not (1 <= L <= _ML and 1 <= B <= _MB):
+        raise _lib.WeasalHipError("neighbor_histograms: %d levels / %d batch elements (at most %d / %d)" % (L, B, _ML, _MB))
+    if (hists.dtype != torch.int64 or hists.device != dev or hists.dim() != 2 or hists.shape[0] != L
+            or not hists.is_contiguous()):
+        raise ValueError("hists must be a contiguous int64 [%d, hist_n] tensor on %s" % (L, dev))
+    d = PyramidDesc()
+    d.n_levels, d.nb = L, B
+    d.points, d.n0 = P0.data_ptr(), n0
+    for l, lv in enumerate(levels):
+        d.conv_on[l], d.pool_on[l] = int(lv["conv_on"]), int(lv["pool_on"])
+        d.r_conv[l], d.dl[l] = lv["r_conv"], lv["dl"]
+    for b in range(B):
+        d.lens[0][b] = int(lens0[b])
+    rots = _draw_grid_orientations(levels, B, rng) if random_grid_orient else None
+    if rots is not None:
+        d.h_rot = rots.ctypes.data
+    scratch = torch.empty(max(int(lib.ws_pyramid_histograms_scratch_bytes(n0)), 256), dtype=torch.uint8, device=dev)
+    d.scratch, d.scratch_bytes = scratch.data_ptr(), scratch.numel()
+    with torch.cuda.device(dev):
+        _lib.check(lib.ws_pyramid_histograms(ops._ws.neighbors(dev), ops._ws.subsample(dev), _C.byref(d), hists.data_ptr(),
+                                             int(hists.shape[1]), _lib.current_stream()))
+    return [np.array(d.lens[l][:B], dtype=np.int32) for l in range(L)]
 
 
 class _TLS(__import__("threading").local):

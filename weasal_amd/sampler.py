@@ -305,8 +305,13 @@ class SphereSampler:
         slots = words[8:].reshape(MAX_SPHERES, 8)
         return head, slots
 
+    def _limit(self):
+        """the point budget ws_sampler_batch gets: int(batch_limit), with a negative one (the calibration's unstable start)
+        at 0 -- both give one sphere per batch (DALES_PseudoLabel.py:407) and the library refuses a negative budget"""
+        return max(int(self.batch_limit), 0)
+
     def _capacity(self):
-        return int(self.batch_limit) + max(2 * self._max_n, 4096)
+        return self._limit() + max(2 * self._max_n, 4096)
 
     def sample(self, draws=None, capacity_rows=None, augment_noise=None):
         """One batch (DALES_PseudoLabel.py:287-456).  draws: a DRAW_DTYPE array (or a dict with 'noise' [S,3], 'R' [S,3,3],
@@ -362,18 +367,18 @@ class SphereSampler:
             rows = new
             if self.ncol or not self.use_potentials or self.through_items:
                 self.handle.batch_items(host.ctypes.data, self._h_keep.data_ptr() if self.ncol else None, S, resume,
-                                        int(self.batch_limit), float(self.config.in_radius), augment_noise, self.noise_seed, self.seq,
+                                        self._limit(), float(self.config.in_radius), augment_noise, self.noise_seed, self.seq,
                                         fd, self.lut, self.labels_zero, self.set != 'ERF', rows + per_sphere, cap, state,
                                         None if self.use_potentials else self.epoch_inds, self.epoch_i)
             else:
-                self.handle.batch(host.ctypes.data, S, resume, int(self.batch_limit), float(self.config.in_radius), augment_noise,
+                self.handle.batch(host.ctypes.data, S, resume, self._limit(), float(self.config.in_radius), augment_noise,
                                   self.noise_seed, self.seq, fd, self.lut, self.labels_zero, self.set != 'ERF',
                                   rows + per_sphere, cap, state)
             head, slots = self._read_state(state)
             if not head['overflow']:
                 break
             need = int(slots[head['attempts'], 0])                      # the sphere that did not fit
-            cap = max(2 * cap, head['row_off'] + need + int(self.batch_limit))
+            cap = max(2 * cap, head['row_off'] + need + self._limit())
             resume = 1
         B, total = head['n_spheres'], head['row_off']
         self.seq += head['attempts']

@@ -1158,6 +1158,17 @@ enum {
 int ws_kpconv_gather_variant(int32_t op, int64_t nq, int64_t ns, int32_t ci, const void* rows_a, const void* rows_b, int32_t deformed,
                              int32_t modulated, int32_t influence, int32_t aggregation, int32_t rows_bf16, int32_t rows_sorted,
                              int32_t ordered, char* out, int32_t cap);
+/* Kernel sizes.  The gather entries are built for num_kernel_points k in {9, 13, 15}: 15 in every form; 9 and 13 with f32 rows
+ * through the generic forms (MODE 0 rigid / linear / sum and MODE 1, deformable layers included).  bf16 rows, the deformable
+ * fast path with packed kernel points (MODE 2: the _def entries, ws_kpconv_gather_bwd_x_grid_wide with kp4) and
+ * ws_kpconv_layer_fwd_fused are 15 only; everything else is WS_ERR_UNSUPPORTED with the built sizes in the message.
+ * ws_kpconv_supported_k: 1 where the entries run k with these rows in this mode (0, 1, 2 as above), else 0.
+ * ws_kpconv_gather_variant_k: ws_kpconv_gather_variant (which answers for k = 15) for k kernel points; the text names the size
+ * ("K=13" in the kernels that have a K argument, a leading "K=13, " in the matrix-core forward's list) unless it is 15. */
+int ws_kpconv_supported_k(int32_t k, int32_t rows_bf16, int32_t mode);
+int ws_kpconv_gather_variant_k(int32_t op, int64_t nq, int64_t ns, int32_t ci, const void* rows_a, const void* rows_b, int32_t deformed,
+                               int32_t modulated, int32_t influence, int32_t aggregation, int32_t rows_bf16, int32_t rows_sorted,
+                               int32_t ordered, int32_t k, char* out, int32_t cap);
 /* the launches the dense products make for these arguments (the dispatchers' own plan functions; pointers are only tested
  * for alignment, nothing is read or launched): "kernel<template arguments> key=value ..." into out[cap].
  * ws_gemm_xb_variant: any ws_gemm_xb* entry (b_row_stride < 0 = row-major [K, N]; gate_y / mask NULL when absent);

@@ -36,7 +36,7 @@ def p2p_fitting_regularizer(net):
         layers = [m for m in net.modules() if isinstance(m, KPConv) and m.deformable]
         net._deformable_layers = layers
     for m in layers:
-        if REGULARIZER_KERNEL and m.min_d2.is_cuda and net.K == 15 and ops.kpconv_gather is ops._KPCONV_GATHER_SELF:
+        if REGULARIZER_KERNEL and m.min_d2.is_cuda and ops.kernel_size_supported(net.K, mode=1) and ops.kpconv_gather is ops._KPCONV_GATHER_SELF:
             # both terms and their gradients in one kernel each way (ws_p2p_regularizer_fwd / _bwd)
             fr = ops.p2p_regularizer(m.deformed_KP, m.min_d2, m.KP_extent, net.repulse_extent)
             fitting_loss = fitting_loss + fr[0]

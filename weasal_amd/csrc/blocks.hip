@@ -147,7 +147,9 @@ int check_kpblock(const ws_kpblock* d)
 {
     WS_REQUIRE(d, "NULL descriptor");
     WS_REQUIRE(d->nq >= 0 && d->ns >= 0 && d->h >= 1, "bad sizes nq=%lld ns=%lld h=%d", (long long)d->nq, (long long)d->ns, d->h);
-    if (d->k != 15) return ws_fail(WS_ERR_UNSUPPORTED, "num_kernel_points=%d: K=15 only", d->k);
+    if (!ws_kpconv_supported_k(d->k, 0, 0))
+        return ws_fail(WS_ERR_UNSUPPORTED, "num_kernel_points=%d: this build instantiates K=9, K=13 and K=15", d->k);
+    WS_REQUIRE(d->k == 15 || d->wf, "wf buffer missing (the one-launch forward layer is built for K = 15 only)");
     WS_REQUIRE(d->in_dim >= 1 && d->conv_in >= 1 && d->conv_out >= 1 && d->out_dim >= 1, "bad widths");
     WS_REQUIRE(d->q_pts && d->s_pts && d->inds && d->kernel_points && d->feat && d->wk && (d->wf || d->infer) && d->out, "NULL argument");
     WS_REQUIRE(d->w1 ? (d->x1 != nullptr) : (d->conv_in == d->in_dim), "unary1: x1 buffer missing or conv_in != in_dim");
@@ -209,7 +211,7 @@ int kpblock_fwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
     }
     float* x2 = d->w2 ? d->x2 : d->out;
     // forward only and a layer the one-launch kernel covers: the contraction runs inside the gather, no `wf`
-    const bool one_launch = d->infer && d->conv_in == 32 && d->conv_out == 32 && !d->rows_sorted && ((uintptr_t)x1 & 15u) == 0 &&
+    const bool one_launch = d->infer && d->k == 15 && d->conv_in == 32 && d->conv_out == 32 && !d->rows_sorted && ((uintptr_t)x1 & 15u) == 0 &&
                             ((uintptr_t)d->wk & 15u) == 0 && ((uintptr_t)x2 & 15u) == 0 && ws_block_fused_infer;
     if (one_launch) {
         WS_TRY(ws_kpconv_layer_fwd_fused(d->q_pts, nq, d->s_pts, ns, d->inds, d->h, x1, d->conv_in, d->kernel_points, d->k, d->extent,

@@ -5,14 +5,17 @@
 // as many autograd nodes; its regulariser materialises 15 x [N, 14, 3] difference tensors per layer.  Here:
 //   ws_kpconv_deform_prepare / _bwd   offset features [N, 3K (+K)] -> deformed_kp [N,K,3], modulations [N,K] and the packed
 //                                     operand kp4 [N,K] float4 = (x, y, z, modulation) the MODE-2 gather kernels read
-//   ws_p2p_regularizer_fwd / _bwd     fitting + repulsive loss of one layer and their gradients, thread = point, the 15
+//   ws_p2p_regularizer_fwd / _bwd     fitting + repulsive loss of one layer and their gradients, thread = point, the K
 //                                     kernel points of the point in registers, fixed-order reduction (bit-reproducible)
 #include "ws_common.h"
+#include "ws_dispatch.h"
 
 namespace {
 
-constexpr int KP = 15;
+// KP: kernel points per point; the sizes of the gather kernels (kpconv_launch.h: WS_KP_SIZES)
+#define WS_DEFORM_SIZES 9, 13, 15
 
+template <int KP>
 __global__ __launch_bounds__(256) void deform_prepare_kernel(const float* __restrict__ off, int64_t n, int32_t od,
                                                              const float* __restrict__ kernel_points, float extent, int modulated,
                                                              float* __restrict__ deformed_kp, float* __restrict__ modulations,
@@ -51,6 +54,7 @@ __global__ __launch_bounds__(256) void deform_prepare_kernel(const float* __rest
 
 // d offset_features from d kp4 (the gather kernels' geometry gradient: xyz and modulation) and, optionally, a second
 // gradient of the kernel-point positions (the regulariser's)
+template <int KP>
 __global__ __launch_bounds__(256) void deform_prepare_bwd_kernel(const float4* __restrict__ d_kp4, const float* __restrict__ d_dkp,
                                                                  const float4* __restrict__ kp4, int64_t n, int32_t od, float extent,
                                                                  int modulated, float* __restrict__ d_off)
@@ -76,6 +80,7 @@ __global__ __launch_bounds__(256) void deform_prepare_bwd_kernel(const float4* _
 // repulsive = sum_i mean_n | sum_{j != i} min(|loc_i - loc_j| - repulse_extent, 0)^2 | / K,  loc = deformed_kp / extent,
 //             the other points detached (:45-51)
 // one thread per point; per-workgroup partial sums, added in a fixed order by ws_p2p_regularizer_fwd's final kernel.
+template <int KP>
 __device__ __forceinline__ void load_locs(const float* __restrict__ dkp, const float4* __restrict__ kp4, int64_t p, float inv_extent,
                                           float (&lx)[KP], float (&ly)[KP], float (&lz)[KP])
 {
@@ -91,6 +96,7 @@ __device__ __forceinline__ void load_locs(const float* __restrict__ dkp, const f
     }
 }
 
+template <int KP>
 __global__ __launch_bounds__(256) void p2p_reg_fwd_kernel(const float* __restrict__ dkp, const float4* __restrict__ kp4,
                                                           const float* __restrict__ min_d2, int64_t n, float extent,
                                                           float repulse_extent, float* __restrict__ partial /*[blocks][2]*/)
@@ -100,7 +106,7 @@ __global__ __launch_bounds__(256) void p2p_reg_fwd_kernel(const float* __restric
     float fit = 0.0f, rep = 0.0f;
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
         float lx[KP], ly[KP], lz[KP];
-        load_locs(dkp, kp4, p, inv_extent, lx, ly, lz);
+        load_locs<KP>(dkp, kp4, p, inv_extent, lx, ly, lz);
 #pragma unroll
         for (int k = 0; k < KP; ++k) fit += fabsf(min_d2[p * KP + k] * inv_e2);
 #pragma unroll
@@ -128,6 +134,7 @@ __global__ __launch_bounds__(256) void p2p_reg_fwd_kernel(const float* __restric
     }
 }
 
+template <int KP>
 __global__ __launch_bounds__(256) void p2p_reg_final_kernel(const float* __restrict__ partial, int blocks, int64_t n,
                                                             float* __restrict__ out /*[2]: fitting, repulsive*/)
 {
@@ -149,6 +156,7 @@ __global__ __launch_bounds__(256) void p2p_reg_final_kernel(const float* __restr
 // gradients: d fitting / d min_d2 = sign(min_d2) / (extent^2 N K) * g_fit;
 //            d repulsive / d deformed_kp[n,i] = g_rep / (N K extent) * sign(rep_i) * sum_{j != i} 2 c_ij (loc_i - loc_j) / d_ij
 // g = (g_fit, g_rep) are DEVICE scalars (the upstream gradient times the loss weights): no host synchronisation.
+template <int KP>
 __global__ __launch_bounds__(256) void p2p_reg_bwd_kernel(const float* __restrict__ dkp, const float4* __restrict__ kp4,
                                                           const float* __restrict__ min_d2, int64_t n, float extent,
                                                           float repulse_extent, const float* __restrict__ g,
@@ -159,7 +167,7 @@ __global__ __launch_bounds__(256) void p2p_reg_bwd_kernel(const float* __restric
     const float g_fit = g[0] * inv_e2 / nk, g_rep = g[1] * inv_extent / nk;
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
         float lx[KP], ly[KP], lz[KP];
-        load_locs(dkp, kp4, p, inv_extent, lx, ly, lz);
+        load_locs<KP>(dkp, kp4, p, inv_extent, lx, ly, lz);
 #pragma unroll
         for (int k = 0; k < KP; ++k) {
             const float v = min_d2[p * KP + k];
@@ -184,6 +192,12 @@ __global__ __launch_bounds__(256) void p2p_reg_bwd_kernel(const float* __restric
     }
 }
 
+int check_k(int k)
+{
+    for (int v : {WS_DEFORM_SIZES}) if (k == v) return WS_OK;
+    return ws_fail(WS_ERR_UNSUPPORTED, "num_kernel_points=%d: this build instantiates K=9, K=13 and K=15", k);
+}
+
 }  // namespace
 
 extern "C" {
@@ -192,14 +206,16 @@ int ws_kpconv_deform_prepare(const float* offset_features, int64_t n, int32_t od
                              float extent, int32_t modulated, float* deformed_kp, float* modulations, float* kp4, float* kp_rmax,
                              void* stream)
 {
-    if (k != KP) return ws_fail(WS_ERR_UNSUPPORTED, "num_kernel_points=%d: this build instantiates K=15 only", k);
-    WS_REQUIRE(n >= 0 && od == (modulated ? 4 : 3) * KP, "offset features must have %d columns (got %d)", (modulated ? 4 : 3) * KP, od);
+    if (int rc = check_k(k)) return rc;
+    WS_REQUIRE(n >= 0 && od == (modulated ? 4 : 3) * k, "offset features must have %d columns (got %d)", (modulated ? 4 : 3) * k, od);
     if (n == 0) return WS_OK;
     WS_REQUIRE(offset_features && kernel_points && kp4 && ((uintptr_t)kp4 & 15u) == 0, "NULL / unaligned argument");
     if (kp_rmax) WS_HIP(hipMemsetAsync(kp_rmax, 0, sizeof(float), (hipStream_t)stream));
-    deform_prepare_kernel<<<(unsigned)ws_ceil_div(n * KP, 256), 256, 0, (hipStream_t)stream>>>(
-        offset_features, n, od, kernel_points, extent, modulated, deformed_kp, modulations, reinterpret_cast<float4*>(kp4),
-        reinterpret_cast<int*>(kp_rmax));
+    dispatch([&](auto kn) {
+        deform_prepare_kernel<kn.value><<<(unsigned)ws_ceil_div(n * k, 256), 256, 0, (hipStream_t)stream>>>(
+            offset_features, n, od, kernel_points, extent, modulated, deformed_kp, modulations, reinterpret_cast<float4*>(kp4),
+            reinterpret_cast<int*>(kp_rmax));
+    }, Pick<WS_DEFORM_SIZES>{k});
     WS_LAUNCH_CHECK();
     return WS_OK;
 }
@@ -207,13 +223,15 @@ int ws_kpconv_deform_prepare(const float* offset_features, int64_t n, int32_t od
 int ws_kpconv_deform_prepare_bwd(const float* d_kp4, const float* d_deformed_kp, const float* kp4, int64_t n, int32_t od, int32_t k,
                                  float extent, int32_t modulated, float* d_offset_features, void* stream)
 {
-    if (k != KP) return ws_fail(WS_ERR_UNSUPPORTED, "num_kernel_points=%d: this build instantiates K=15 only", k);
-    WS_REQUIRE(n >= 0 && od == (modulated ? 4 : 3) * KP, "offset features must have %d columns (got %d)", (modulated ? 4 : 3) * KP, od);
+    if (int rc = check_k(k)) return rc;
+    WS_REQUIRE(n >= 0 && od == (modulated ? 4 : 3) * k, "offset features must have %d columns (got %d)", (modulated ? 4 : 3) * k, od);
     if (n == 0) return WS_OK;
     WS_REQUIRE(kp4 && d_offset_features && (d_kp4 || d_deformed_kp), "NULL argument");
-    deform_prepare_bwd_kernel<<<(unsigned)ws_ceil_div(n * KP, 256), 256, 0, (hipStream_t)stream>>>(
-        reinterpret_cast<const float4*>(d_kp4), d_deformed_kp, reinterpret_cast<const float4*>(kp4), n, od, extent, modulated,
-        d_offset_features);
+    dispatch([&](auto kn) {
+        deform_prepare_bwd_kernel<kn.value><<<(unsigned)ws_ceil_div(n * k, 256), 256, 0, (hipStream_t)stream>>>(
+            reinterpret_cast<const float4*>(d_kp4), d_deformed_kp, reinterpret_cast<const float4*>(kp4), n, od, extent, modulated,
+            d_offset_features);
+    }, Pick<WS_DEFORM_SIZES>{k});
     WS_LAUNCH_CHECK();
     return WS_OK;
 }
@@ -225,14 +243,17 @@ int64_t ws_p2p_regularizer_scratch_bytes(int64_t n) { return (int64_t)reg_blocks
 int ws_p2p_regularizer_fwd(const float* deformed_kp, const float* kp4, const float* min_d2, int64_t n, int32_t k, float extent,
                            float repulse_extent, float* out2, void* scratch, void* stream)
 {
-    if (k != KP) return ws_fail(WS_ERR_UNSUPPORTED, "num_kernel_points=%d: this build instantiates K=15 only", k);
+    if (int rc = check_k(k)) return rc;
     WS_REQUIRE(n >= 1 && (deformed_kp || kp4) && min_d2 && out2 && scratch && extent > 0.0f, "NULL argument / empty layer");
     const int blocks = reg_blocks(n);
     hipStream_t st = (hipStream_t)stream;
-    p2p_reg_fwd_kernel<<<blocks, 256, 0, st>>>(deformed_kp, reinterpret_cast<const float4*>(kp4), min_d2, n, extent, repulse_extent,
-                                               (float*)scratch);
+    dispatch([&](auto kn) {
+        p2p_reg_fwd_kernel<kn.value><<<blocks, 256, 0, st>>>(deformed_kp, reinterpret_cast<const float4*>(kp4), min_d2, n, extent,
+                                                             repulse_extent, (float*)scratch);
+    }, Pick<WS_DEFORM_SIZES>{k});
     WS_LAUNCH_CHECK();
-    p2p_reg_final_kernel<<<1, 256, 0, st>>>((const float*)scratch, blocks, n, out2);
+    dispatch([&](auto kn) { p2p_reg_final_kernel<kn.value><<<1, 256, 0, st>>>((const float*)scratch, blocks, n, out2); },
+             Pick<WS_DEFORM_SIZES>{k});
     WS_LAUNCH_CHECK();
     return WS_OK;
 }
@@ -240,10 +261,12 @@ int ws_p2p_regularizer_fwd(const float* deformed_kp, const float* kp4, const flo
 int ws_p2p_regularizer_bwd(const float* deformed_kp, const float* kp4, const float* min_d2, int64_t n, int32_t k, float extent,
                            float repulse_extent, const float* g2, float* d_min_d2, float* d_deformed_kp, void* stream)
 {
-    if (k != KP) return ws_fail(WS_ERR_UNSUPPORTED, "num_kernel_points=%d: this build instantiates K=15 only", k);
+    if (int rc = check_k(k)) return rc;
     WS_REQUIRE(n >= 1 && (deformed_kp || kp4) && min_d2 && g2 && d_min_d2 && d_deformed_kp && extent > 0.0f, "NULL argument / empty layer");
-    p2p_reg_bwd_kernel<<<reg_blocks(n), 256, 0, (hipStream_t)stream>>>(deformed_kp, reinterpret_cast<const float4*>(kp4), min_d2, n, extent,
-                                                                       repulse_extent, g2, d_min_d2, d_deformed_kp);
+    dispatch([&](auto kn) {
+        p2p_reg_bwd_kernel<kn.value><<<reg_blocks(n), 256, 0, (hipStream_t)stream>>>(deformed_kp, reinterpret_cast<const float4*>(kp4), min_d2,
+                                                                                 n, extent, repulse_extent, g2, d_min_d2, d_deformed_kp);
+    }, Pick<WS_DEFORM_SIZES>{k});
     WS_LAUNCH_CHECK();
     return WS_OK;
 }

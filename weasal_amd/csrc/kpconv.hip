@@ -22,6 +22,23 @@ constexpr int GRID_INTERLEAVE = 512;   // K4G and the wide-row K4G of config 5: 
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// the kernel sizes of this build (WS_KP_SIZES): 15 in every form; 9 and 13 with f32 rows through the generic forms (MODE 0 / 1).
+// bf16 rows, the deformable fast path (MODE 2: the _def entries, packed kernel points) and the fused forward layer are 15 only.
+bool built_k(int k)
+{
+    for (int v : {WS_KP_SIZES}) if (k == v) return true;
+    return false;
+}
+bool supported_k(int k, bool bf16, int mode) { return built_k(k) && (k == 15 || (!bf16 && mode != 2)); }
+int check_k(int k, bool bf16, int mode)
+{
+    if (!built_k(k)) return ws_fail(WS_ERR_UNSUPPORTED, "num_kernel_points=%d: this build instantiates K=9, K=13 and K=15", k);
+    if (!supported_k(k, bf16, mode))
+        return ws_fail(WS_ERR_UNSUPPORTED, "num_kernel_points=%d with %s: this build instantiates K=9, K=13 and K=15, and %s for K=15 only", k,
+                       mode == 2 ? "packed kernel points" : "bf16 rows", mode == 2 ? "the deformable fast path (MODE 2)" : "bf16 rows");
+    return WS_OK;
+}
+
 int check_common(const void* q_pts, int64_t nq, const void* s_pts, int64_t ns, int32_t h, int32_t ci,
                  int32_t k, float extent, int32_t influence, int32_t aggregation)
 {
@@ -33,8 +50,7 @@ int check_common(const void* q_pts, int64_t nq, const void* s_pts, int64_t ns, i
     WS_REQUIRE(influence >= 0 && influence <= 2, "unknown influence %d", influence);
     WS_REQUIRE(aggregation >= 0 && aggregation <= 1, "unknown aggregation %d", aggregation);
     WS_REQUIRE(ns < (1ll << 31) && nq * (int64_t)k < (1ll << 31), "index range exceeds int32");
-    if (k != 15) return ws_fail(WS_ERR_UNSUPPORTED, "num_kernel_points=%d: this build instantiates K=15 only", k);
-    return WS_OK;
+    return check_k(k, false, 0);
 }
 
 // ---- plans (GatherPlan, kpconv_launch.h): what a launcher launches, from its arguments alone (pointers only for their alignment).
@@ -76,7 +92,7 @@ void grid_walk_plan(int64_t ns, bool ordered, GatherPlan& p)
 GatherPlan new_plan(int kernel, bool bf16, int64_t items)
 {
     GatherPlan p{};
-    p.kernel = kernel; p.bf16 = bf16; p.csplit = 1; p.grid = ws_grid(items, 4);
+    p.kernel = kernel; p.bf16 = bf16; p.k = 15; p.csplit = 1; p.grid = ws_grid(items, 4);
     return p;
 }
 
@@ -185,30 +201,32 @@ void plan_text(const GatherPlan& p, char* out, size_t n)
 {
     const char* t = p.bf16 ? "bf16" : "float";
     auto b = [](bool v) { return v ? "true" : "false"; };
+    char ks[16] = "";                        // the matrix-core forward names its size only where it is not 15
+    if (p.k != 15) snprintf(ks, sizeof ks, "K=%d, ", p.k);
     switch (p.kernel) {
     case GK_FWD_MFMA:
-        snprintf(out, n, "kpconv_gather_fwd_mfma_kernel<NT=%d, MODE=%d, DEF=%s, VECROW=%s, T=%s, CUT=%s> grid=%d csplit=%d", p.n, p.mode,
+        snprintf(out, n, "kpconv_gather_fwd_mfma_kernel<%sNT=%d, MODE=%d, DEF=%s, VECROW=%s, T=%s, CUT=%s> grid=%d csplit=%d", ks, p.n, p.mode,
                  b(p.def), b(p.vec), t, b(p.cut), p.grid, p.csplit);
         break;
     case GK_FWD_POOL:
-        snprintf(out, n, "kpconv_gather_fwd_kernel<K=15, G=%d, MODE=%d, DEF=%s, VEC=%s, PW=%d, T=%s> grid=%d csplit=%d cut=%d", p.n, p.mode,
+        snprintf(out, n, "kpconv_gather_fwd_kernel<K=%d, G=%d, MODE=%d, DEF=%s, VEC=%s, PW=%d, T=%s> grid=%d csplit=%d cut=%d", p.k, p.n, p.mode,
                  b(p.def), b(p.vec), p.pw, t, p.grid, p.csplit, p.rows_sorted);
         break;
     case GK_BWD_X:
-        snprintf(out, n, "kpconv_gather_bwd_x_kernel<K=15, G=%d, MODE=%d, VEC=%s, T=%s> grid=%d", p.n, p.mode, b(p.vec), t, p.grid);
+        snprintf(out, n, "kpconv_gather_bwd_x_kernel<K=%d, G=%d, MODE=%d, VEC=%s, T=%s> grid=%d", p.k, p.n, p.mode, b(p.vec), t, p.grid);
         break;
     case GK_BWD_X_PACKED:
-        snprintf(out, n, "kpconv_gather_bwd_x_packed_kernel<K=15, G=%d, VEC=%s, T=%s> grid=%d", p.n, b(p.vec), t, p.grid);
+        snprintf(out, n, "kpconv_gather_bwd_x_packed_kernel<K=%d, G=%d, VEC=%s, T=%s> grid=%d", p.k, p.n, b(p.vec), t, p.grid);
         break;
     case GK_BWD_GEOM:
-        snprintf(out, n, "kpconv_gather_bwd_geom_kernel<K=15, T=%s> grid=%d vec4=%d", t, p.grid, p.vec ? 1 : 0);
+        snprintf(out, n, "kpconv_gather_bwd_geom_kernel<K=%d, T=%s> grid=%d vec4=%d", p.k, t, p.grid, p.vec ? 1 : 0);
         break;
     case GK_BWD_X_GRID:
-        snprintf(out, n, "kpconv_gather_bwd_x_grid_kernel<K=15, G=%d, MODE=%d, VEC=%s, T=%s, SORT=%s> grid=%d ilv=%d", p.n, p.mode, b(p.vec),
+        snprintf(out, n, "kpconv_gather_bwd_x_grid_kernel<K=%d, G=%d, MODE=%d, VEC=%s, T=%s, SORT=%s> grid=%d ilv=%d", p.k, p.n, p.mode, b(p.vec),
                  t, b(p.sort), p.grid, p.ilv);
         break;
     case GK_BWD_X_GRIDW:
-        snprintf(out, n, "kpconv_gather_bwd_x_gridw_kernel<K=15, G=%d, MODE=%d, VEC=%s, NCH=%d, T=%s> grid=%d ilv=%d", p.n, p.mode,
+        snprintf(out, n, "kpconv_gather_bwd_x_gridw_kernel<K=%d, G=%d, MODE=%d, VEC=%s, NCH=%d, T=%s> grid=%d ilv=%d", p.k, p.n, p.mode,
                  b(p.vec), p.nch, t, p.grid, p.ilv);
         break;
     default:
@@ -232,8 +250,10 @@ int gather_bwd_x_impl(bool bf16, const float* q_pts, int64_t nq, const float* s_
     WS_REQUIRE(nq * (int64_t)k * ci < (1ll << 31), "nq*k*ci exceeds the 32-bit row offsets of the gather");
     GatherPlan p;
     const int mode = rigid_fast(deformed_kp, modulations, influence, aggregation) ? 0 : 1;
+    if (int rc = check_k(k, bf16, mode)) return rc;
     if (int rc = packed ? bwd_x_packed_plan(bf16, nq, ns, h, ci, dwf, dx, mode, order != nullptr, p) : bwd_x_plan(bf16, ns, ci, dwf, dx, mode, p))
         return rc;
+    p.k = k;
     GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, gate, gate_slope, nullptr, 0};
     if (p.kernel == GK_BWD_X_PACKED) {
         launch_bwd_x_packed(p, stream, q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, (const float*)dwf, ci, kernel_points, g, (float*)dx, order);
@@ -252,7 +272,9 @@ int gather_bwd_geom_impl(bool bf16, const float* q_pts, int64_t nq, const float*
     if (nq == 0) return WS_OK;
     WS_REQUIRE(inds && x && dwf && deformed_kp && d_deformed_kp, "NULL argument");
     GatherPlan p;
+    if (int rc = check_k(k, bf16, 1)) return rc;
     if (int rc = bwd_geom_plan(bf16, nq, ci, x, dwf, p)) return rc;
+    p.k = k;
     GeomParams g{extent, influence, aggregation, 1, nullptr, 0.0f, nullptr, 0};
     launch_bwd_geom(p, stream, q_pts, nq, s_pts, ns, inds, h, x, ci, dwf, deformed_kp, modulations, d_min_d2, g, d_deformed_kp, d_modulations);
     return launched();
@@ -272,7 +294,9 @@ int gather_bwd_x_grid_impl(bool bf16, const float* s_pts, int64_t ns, const void
     WS_REQUIRE(!rows || rows_h >= 1, "index rows given without their width");
     GatherPlan p;
     const int mode = rigid_fast(deformed_kp, modulations, influence, aggregation) ? 0 : 1;
+    if (int rc = check_k(k, bf16, mode)) return rc;
     if (int rc = bwd_x_grid_plan(bf16, ns, ci, dwf, dx, mode, order != nullptr, p)) return rc;
+    p.k = k;
     GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, gate, gate_slope, rows, rows_h, nullptr, nullptr, 0, p.ilv};
     const GridView v = grid_view(grid_blob, nb, cells, key_last, radius);
     launch_bwd_x_grid(p, stream, s_pts, ns, v, nb, dwf, ci, kernel_points, deformed_kp, modulations, g, dx, order, overflow);
@@ -296,7 +320,9 @@ int ws_kpconv_gather_fwd_ex(const float* q_pts, int64_t nq, const float* s_pts, 
     WS_REQUIRE(inds && x && wf && (kernel_points || deformed_kp), "NULL argument");
     WS_REQUIRE(ns * (int64_t)ci < (1ll << 31), "ns*ci exceeds the 32-bit row offsets of the gather");
     GatherPlan p;
+    if (int rc = check_k(k, rows_bf16 != 0, 0)) return rc;
     if (int rc = fwd_plan(rows_bf16 != 0, nq, ci, x, wf, deformed_kp, modulations, influence, aggregation, rows_sorted != 0, p)) return rc;
+    p.k = k;
     GeomParams g{extent, influence, aggregation, deformed_kp ? 1 : 0, nullptr, 0.0f, nullptr, 0, nullptr, nullptr, p.rows_sorted, 0, p.csplit};
     if (p.kernel == GK_FWD_MFMA)
         launch_fwd_mfma(p, stream, q_pts, nq, s_pts, ns, inds, h, x, ci, kernel_points, deformed_kp, modulations, g, wf, min_d2, order);
@@ -338,6 +364,7 @@ int ws_kpconv_gather_fwd_def(const float* q_pts, int64_t nq, const float* s_pts,
     WS_REQUIRE(aligned16(kp4), "kp4 must be 16-byte aligned");
     WS_REQUIRE(ns * (int64_t)ci < (1ll << 31), "ns*ci exceeds the 32-bit row offsets of the gather");
     GatherPlan p;
+    if (int rc = check_k(k, rows_bf16 != 0, 2)) return rc;
     if (int rc = fwd_def_plan(rows_bf16 != 0, nq, ci, x, wf, rows_sorted != 0, p)) return rc;
     GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 1, nullptr, 0.0f, nullptr, 0, reinterpret_cast<const float4*>(kp4)};
     launch_fwd_mfma(p, stream, q_pts, nq, s_pts, ns, inds, h, x, ci, nullptr, nullptr, nullptr, g, wf, min_d2, order);
@@ -354,6 +381,7 @@ int ws_kpconv_gather_bwd_x_def(const float* q_pts, int64_t nq, const float* s_pt
     WS_REQUIRE(nq * (int64_t)h < (1ll << 31), "nq*h exceeds int32");
     WS_REQUIRE(nq * (int64_t)k * ci < (1ll << 31), "nq*k*ci exceeds the 32-bit row offsets of the gather");
     GatherPlan p;
+    if (int rc = check_k(k, rows_bf16 != 0, 2)) return rc;
     if (int rc = bwd_x_plan(rows_bf16 != 0, ns, ci, dwf, dx, 2, p)) return rc;
     GeomParams g{extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM, 1, nullptr, 0.0f, nullptr, 0, reinterpret_cast<const float4*>(kp4)};
     launch_bwd_x(p, stream, q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, dwf, ci, nullptr, nullptr, nullptr, g, dx, order);
@@ -375,7 +403,9 @@ int ws_kpconv_gather_bwd_x_grid_wide(const float* s_pts, int64_t ns, const void*
     WS_REQUIRE(ns * (int64_t)k * ci < (1ll << 31), "ns*k*ci exceeds the 32-bit row offsets of the gather");
     WS_REQUIRE(!rows || rows_h >= 1, "index rows given without their width");
     GatherPlan p;
+    if (int rc = check_k(k, rows_bf16 != 0, kp4 ? 2 : 0)) return rc;
     if (int rc = bwd_x_gridw_plan(rows_bf16 != 0, ns, ci, dwf, dx, kp4 != nullptr, order != nullptr, p)) return rc;
+    p.k = k;
     // no kp_rmax from the caller: the entry takes the maximum itself, so the candidates -- and with them the 64-pair batches and
     // the association of the sums -- do not depend on whether the caller kept the scalar.  The word is stream-ordered memory of
     // this call (freed on every way out); not under a stream capture, where the allocation would become a node of the graph:
@@ -413,6 +443,7 @@ int ws_kpconv_gather_bwd_geom_def(const float* q_pts, int64_t nq, const float* s
     WS_REQUIRE(inds && x && dwf && kp4 && d_kp4 && aligned16(kp4) && aligned16(d_kp4), "NULL / unaligned argument");
     WS_REQUIRE(ns * (int64_t)ci < (1ll << 31) && nq * (int64_t)k * ci < (1ll << 31), "row offsets exceed 32 bits");
     GatherPlan p;
+    if (int rc = check_k(k, rows_bf16 != 0, 2)) return rc;
     if (int rc = bwd_geom_def_plan(rows_bf16 != 0, nq, ci, x, dwf, rows_sorted != 0, p)) return rc;
     launch_bwd_geom_def(p, stream, q_pts, nq, s_pts, ns, inds, h, x, ci, dwf, kp4, d_min_d2, extent, d_kp4, order);
     return launched();
@@ -429,6 +460,7 @@ int ws_kpconv_layer_fwd_fused(const float* q_pts, int64_t nq, const float* s_pts
 {
     int rc = check_common(q_pts, nq, s_pts, ns, h, ci, k, extent, WS_INFLUENCE_LINEAR, WS_AGGREGATION_SUM);
     if (rc) return rc;
+    if (k != 15) return ws_fail(WS_ERR_UNSUPPORTED, "num_kernel_points=%d: the fused forward layer is built for K=15 only (of K=9, K=13 and K=15)", k);
     if (ci != 32 || co != 32 || !aligned16(x) || !aligned16(weights) || !aligned16(out))
         return ws_fail(WS_ERR_UNSUPPORTED, "fused forward layer: 32 -> 32 channels, 16-byte aligned rows (got %d -> %d)", ci, co);
     if (nq == 0) return WS_OK;
@@ -448,6 +480,24 @@ int ws_kpconv_gather_variant(int32_t op, int64_t nq, int64_t ns, int32_t ci, con
                              int32_t modulated, int32_t influence, int32_t aggregation, int32_t rows_bf16, int32_t rows_sorted,
                              int32_t ordered, char* out, int32_t cap)
 {
+    return ws_kpconv_gather_variant_k(op, nq, ns, ci, rows_a, rows_b, deformed, modulated, influence, aggregation, rows_bf16, rows_sorted,
+                                      ordered, 15, out, cap);
+}
+
+// 1 where the gather entries run k kernel points with these rows (rows_bf16) in this MODE (0 rigid / linear / sum, 1 the generic
+// form, 2 the deformable fast path with packed kernel points), else 0: what the Python layers ask instead of comparing with 15
+int ws_kpconv_supported_k(int32_t k, int32_t rows_bf16, int32_t mode)
+{
+    return (mode >= 0 && mode <= 2 && supported_k(k, rows_bf16 != 0, mode)) ? 1 : 0;
+}
+
+// ws_kpconv_gather_variant for k kernel points: the same text with the size in it (K=13 where the kernel has a K field, a
+// leading "K=13, " in the matrix-core forward's list; k = 15 prints what ws_kpconv_gather_variant always printed); a size
+// or form this build does not have is refused like the entry refuses it
+int ws_kpconv_gather_variant_k(int32_t op, int64_t nq, int64_t ns, int32_t ci, const void* rows_a, const void* rows_b, int32_t deformed,
+                               int32_t modulated, int32_t influence, int32_t aggregation, int32_t rows_bf16, int32_t rows_sorted,
+                               int32_t ordered, int32_t k, char* out, int32_t cap)
+{
     WS_REQUIRE(out && cap > 0 && ci >= 1 && nq >= 0 && ns >= 0, "bad argument");
     const bool bf = rows_bf16 != 0, def = deformed != 0, mod = modulated != 0, srt = rows_sorted != 0, ord = ordered != 0;
     const int mode = rigid_fast(def, mod, influence, aggregation) ? 0 : 1;
@@ -464,8 +514,11 @@ int ws_kpconv_gather_variant(int32_t op, int64_t nq, int64_t ns, int32_t ci, con
     case WS_GATHER_BWD_GEOM_DEF: rc = bwd_geom_def_plan(bf, nq, ci, rows_a, rows_b, srt, p); break;
     default: return ws_fail(WS_ERR_INVALID, "unknown gather operation %d", op);
     }
-    if (rc == WS_OK) plan_text(p, out, (size_t)cap);
-    return rc;
+    if (rc != WS_OK) return rc;
+    if (int rk = check_k(k, bf, p.mode)) return rk;
+    p.k = k;
+    plan_text(p, out, (size_t)cap);
+    return WS_OK;
 }
 
 // Name of the forward gather kernel a layer launches (bench.py's roofline.kernel): the forward plan for 16-byte aligned rows at

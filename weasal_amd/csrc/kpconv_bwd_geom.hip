@@ -341,12 +341,13 @@ void launch_bwd_geom(const GatherPlan& p, void* stream, const float* q_pts, int6
                      int32_t h, const void* x, int32_t ci, const void* dwf, const float* deformed_kp, const float* modulations,
                      const float* d_min_d2, const GeomParams& g, float* d_deformed_kp, float* d_modulations)
 {
-    dispatch([&](auto bf) {
+    dispatch([&](auto bf, auto kn) {
         using T = Row<bf.value>;
-        kpconv_gather_bwd_geom_kernel<15, T><<<p.grid, 256, 0, (hipStream_t)stream>>>(
-            q_pts, nq, s_pts, ns, inds, h, (const T*)x, ci, (const T*)dwf, deformed_kp, modulations, d_min_d2, g, d_deformed_kp, d_modulations,
-            p.vec);
-    }, Flag{p.bf16});
+        if constexpr (kn.value == 15 || !bf.value)
+            kpconv_gather_bwd_geom_kernel<kn.value, T><<<p.grid, 256, 0, (hipStream_t)stream>>>(
+                q_pts, nq, s_pts, ns, inds, h, (const T*)x, ci, (const T*)dwf, deformed_kp, modulations, d_min_d2, g, d_deformed_kp,
+                d_modulations, p.vec);
+    }, Flag{p.bf16}, Pick<WS_KP_SIZES>{p.k});
 }
 
 // kpconv_gather_bwd_geom_def_kernel for ws_kpconv_gather_bwd_geom_def

@@ -336,13 +336,14 @@ namespace kpconv {
 void launch_bwd_x_gridw(const GatherPlan& p, void* stream, const float* s_pts, int64_t ns, const GridView& v, int32_t nb, const void* dwf,
                         int32_t ci, const float* kernel_points, const GeomParams& g, void* dx, const int32_t* order)
 {
-    dispatch([&](auto bf, auto gr, auto mode, auto vec, auto nch) {
+    dispatch([&](auto bf, auto gr, auto mode, auto vec, auto nch, auto kn) {
         using T = Row<bf.value>;
-        if constexpr ((!bf.value || vec.value) && (nch.value == 1 || gr.value == 16))
-            kpconv_gather_bwd_x_gridw_kernel<15, gr.value, mode.value, vec.value != 0, nch.value, T><<<p.grid, 256, 0, (hipStream_t)stream>>>(
+        if constexpr ((!bf.value || vec.value) && (nch.value == 1 || gr.value == 16) && (kn.value == 15 || (!bf.value && mode.value == 0)))
+            kpconv_gather_bwd_x_gridw_kernel<kn.value, gr.value, mode.value, vec.value != 0, nch.value, T>
+                <<<p.grid, 256, 0, (hipStream_t)stream>>>(
                 s_pts, ns, v.grids, nb, v.cell_start, v.sorted, v.key_last, v.r2, (const T*)dwf, ci, kernel_points, nullptr, nullptr, g, (T*)dx,
                 order);
-    }, Flag{p.bf16}, Pick<1, 2, 4, 8, 16>{p.n}, Pick<0, 2>{p.mode}, Flag{p.vec}, Pick<1, 2, 4>{p.nch});
+    }, Flag{p.bf16}, Pick<1, 2, 4, 8, 16>{p.n}, Pick<0, 2>{p.mode}, Flag{p.vec}, Pick<1, 2, 4>{p.nch}, Pick<WS_KP_SIZES>{p.k});
 }
 
 void launch_kp4_rmax(void* stream, const float* kp4, int64_t n, float* rmax)

@@ -248,8 +248,8 @@ __global__ __launch_bounds__(256) void kpconv_gather_bwd_x_packed_kernel(
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const float ex = nx - kpr[3 * k + 0], ey = ny - kpr[3 * k + 1], ez = nz - kpr[3 * k + 2];
-            const float d = (ex * ex + ey * ey) + ez * ez;
-            float w = fmaxf(1.0f - __builtin_amdgcn_sqrtf(d) * inv_extent, 0.0f);
+            const float d = list_d2<K>(ex, ey, ez);                // (the expressions of kp_list: the same bits as the single-support form)
+            float w = list_linear<K>(d, inv_extent);
             w = real ? w : 0.0f;
             const unsigned long long m = __ballot(w != 0.0f);
             const unsigned half = grp >= 2 ? (unsigned)(m >> 32) : (unsigned)m;
@@ -358,12 +358,12 @@ void launch_bwd_x(const GatherPlan& p, void* stream, const float* q_pts, int64_t
                   const int32_t* t_offsets, const int32_t* t_pairs, const void* dwf, int32_t ci, const float* kernel_points,
                   const float* deformed_kp, const float* modulations, const GeomParams& g, void* dx, const int32_t* order)
 {
-    dispatch([&](auto bf, auto gr, auto mode, auto vec) {
+    dispatch([&](auto bf, auto gr, auto mode, auto vec, auto kn) {
         using T = Row<bf.value>;
-        if constexpr (!bf.value || vec.value)
-            kpconv_gather_bwd_x_kernel<15, gr.value, mode.value, vec.value != 0, T><<<p.grid, 256, 0, (hipStream_t)stream>>>(
+        if constexpr ((!bf.value || vec.value) && (kn.value == 15 || (!bf.value && mode.value != 2)))
+            kpconv_gather_bwd_x_kernel<kn.value, gr.value, mode.value, vec.value != 0, T><<<p.grid, 256, 0, (hipStream_t)stream>>>(
                 q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, (const T*)dwf, ci, kernel_points, deformed_kp, modulations, g, (T*)dx, order);
-    }, Flag{p.bf16}, Pick<1, 2, 4, 8, 16>{p.n}, Pick<0, 1, 2>{p.mode}, Flag{p.vec});
+    }, Flag{p.bf16}, Pick<1, 2, 4, 8, 16>{p.n}, Pick<0, 1, 2>{p.mode}, Flag{p.vec}, Pick<WS_KP_SIZES>{p.k});
 }
 
 // kpconv_gather_bwd_x_packed_kernel for ws_kpconv_gather_bwd_x_packed: f32 float4 rows, MODE 0
@@ -371,10 +371,10 @@ void launch_bwd_x_packed(const GatherPlan& p, void* stream, const float* q_pts, 
                          const int32_t* t_offsets, const int32_t* t_pairs, const float* dwf, int32_t ci, const float* kernel_points,
                          const GeomParams& g, float* dx, const int32_t* order)
 {
-    dispatch([&](auto gr) {
-        kpconv_gather_bwd_x_packed_kernel<15, gr.value, true, float><<<p.grid, 256, 0, (hipStream_t)stream>>>(
+    dispatch([&](auto gr, auto kn) {
+        kpconv_gather_bwd_x_packed_kernel<kn.value, gr.value, true, float><<<p.grid, 256, 0, (hipStream_t)stream>>>(
             q_pts, nq, s_pts, ns, h, t_offsets, t_pairs, dwf, ci, kernel_points, nullptr, nullptr, g, dx, order);
-    }, Pick<1, 2, 4, 8, 16>{p.n});
+    }, Pick<1, 2, 4, 8, 16>{p.n}, Pick<WS_KP_SIZES>{p.k});
 }
 
 }  // namespace kpconv

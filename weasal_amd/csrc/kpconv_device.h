@@ -177,6 +177,29 @@ __device__ __forceinline__ float4 load_row_piece(const T* __restrict__ base, uns
 // exec-mask branch (s_and_saveexec + s_cbranch per entry -- the scalar unit is the bottleneck here)
 __device__ __forceinline__ void keep_unconditional(uint2& e) { asm volatile("" : "+v"(e.x), "+v"(e.y)); }
 
+// Squared distance and influence of the list phase.  Which of the products of (dx dx + dy dy) + dz dz the compiler fuses is its
+// choice per instantiation, and K4G summed in index order has to give the bits of K4 (kpconv_bwd_grid_kernels.h): two kernels
+// that round a weight differently do not.  K = 15 keeps the plain expressions, whose contraction is part of the code it has
+// always had (and agrees between its families); the other sizes spell the fused form out, one rounding sequence everywhere.
+template <int K>
+__device__ __forceinline__ float list_d2(float dx, float dy, float dz)
+{
+    if constexpr (K == 15) return (dx * dx + dy * dy) + dz * dz;
+    else return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+}
+template <int K>
+__device__ __forceinline__ float list_linear(float d2, float inv_extent)
+{
+    if constexpr (K == 15) return fmaxf(1.0f - __builtin_amdgcn_sqrtf(d2) * inv_extent, 0.0f);
+    else return fmaxf(__builtin_fmaf(-__builtin_amdgcn_sqrtf(d2), inv_extent, 1.0f), 0.0f);
+}
+template <int K>
+__device__ __forceinline__ float list_weight(float d2, const GeomParams& g, float inv_extent)
+{
+    if (K != 15 && g.influence == WS_INFLUENCE_LINEAR) return list_linear<K>(d2, inv_extent);
+    return kp_weight(d2, g, inv_extent);
+}
+
 // List phase for one 64-lane chunk.  KPF: kp(k, c) -> coordinate c of kernel point k (SGPR array,
 // wave-uniform pointer or per-lane pointer).  Entry row = row_base + k * row_step.
 // MINF: optional per-kernel-point hook (k, d2) used by the deformable forward for min_d2.
@@ -200,14 +223,13 @@ __device__ __forceinline__ void kp_list(float nx, float ny, float nz, bool live,
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const float dx = nx - kp(k, 0), dy = ny - kp(k, 1), dz = nz - kp(k, 2);
-            const float d = (dx * dx + dy * dy) + dz * dz;
-            float w = fmaxf(1.0f - __builtin_amdgcn_sqrtf(d) * inv_extent, 0.0f);
+            const float d = list_d2<K>(dx, dy, dz);
+            float w = list_linear<K>(d, inv_extent);
             w = live ? w : 0.0f;
             emit(k, w);
         }
     } else {
-        constexpr int KU = 3;
-        static_assert(K % KU == 0, "K must be a multiple of 3");
+        constexpr int KU = K % 3 == 0 ? 3 : 1;      // kernel points per trip of the rolled loops
         const float e2 = g.extent * g.extent;
         int arg = 0;
         if (g.deformable || g.aggregation == WS_AGGREGATION_CLOSEST) {
@@ -219,7 +241,7 @@ __device__ __forceinline__ void kp_list(float nx, float ny, float nz, bool live,
                 for (int u = 0; u < KU; ++u) {
                     const int k = kb + u;
                     const float dx = nx - kp(k, 0), dy = ny - kp(k, 1), dz = nz - kp(k, 2);
-                    const float d = (dx * dx + dy * dy) + dz * dz;
+                    const float d = list_d2<K>(dx, dy, dz);
                     if (d < best) { best = d; arg = k; }
                     inrange |= d < e2;
                 }
@@ -232,9 +254,9 @@ __device__ __forceinline__ void kp_list(float nx, float ny, float nz, bool live,
             for (int u = 0; u < KU; ++u) {
                 const int k = kb + u;
                 const float dx = nx - kp(k, 0), dy = ny - kp(k, 1), dz = nz - kp(k, 2);
-                const float d = (dx * dx + dy * dy) + dz * dz;
+                const float d = list_d2<K>(dx, dy, dz);
                 minf(k, d);
-                float w = kp_weight(d, g, inv_extent);
+                float w = list_weight<K>(d, g, inv_extent);
                 if (g.aggregation == WS_AGGREGATION_CLOSEST && k != arg) w = 0.0f;
                 w = live ? w : 0.0f;
                 if (lane_mod && w != 0.0f) w *= lane_mod[k];

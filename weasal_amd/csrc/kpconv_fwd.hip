@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void kpconv_gather_fwd_kernel(
 // W[120 w + 4 s + kk][16 n + j]) -- on v_mfma_f32_16x16x4_f32, the four partial [16 x 32] tiles are added through LDS
 // with the bias / LeakyReLU epilogue and stored as 16 output rows.  Tile rows are 484 floats apart: the A-operand reads
 // (lane (query, kk)) fall on 64 different banks.
-template <int NT, int MODE, bool DEF, bool VECROW, typename T, int GSV = 0, bool CUT = false, bool FUSE = false>
+template <int NT, int MODE, bool DEF, bool VECROW, typename T, int GSV = 0, bool CUT = false, bool FUSE = false, int K = 15>
 __global__ __launch_bounds__(256) void kpconv_gather_fwd_mfma_kernel(
     const float* __restrict__ q_pts, int64_t nq, const float* __restrict__ s_pts, int64_t ns,
     const int64_t* __restrict__ inds, int h, const T* __restrict__ x, int ci,
@@ -313,9 +313,9 @@ __global__ __launch_bounds__(256) void kpconv_gather_fwd_mfma_kernel(
     const float* __restrict__ modulations, GeomParams g, T* __restrict__ wf,
     float* __restrict__ min_d2, const int32_t* __restrict__ order, FuseArgs fz = FuseArgs{})
 {
-    static_assert(!FUSE || (MODE == 0 && NT == 2 && sizeof(T) == 4 && VECROW), "the fused contraction covers rigid 32 -> 32 f32 layers");
+    static_assert(!FUSE || (MODE == 0 && NT == 2 && sizeof(T) == 4 && VECROW && K == 15), "the fused contraction covers rigid 32 -> 32 f32 layers of 15 kernel points");
+    static_assert(K >= 1 && K <= 16, "the kernel points are the rows of ONE 16-row A tile; rows >= K are masked");
     constexpr int TILE_LD = 484;
-    constexpr int K = 15;
     constexpr int CB = 16 * NT;                                   // channels per block
     // steps whose loads are in flight together (per buffer; two buffers): more = deeper memory pipelining per wave,
     // fewer = fewer registers = more waves per SIMD.  The kernel is bound by instruction latency x occupancy (with every
@@ -728,12 +728,13 @@ void launch_fwd_mfma(const GatherPlan& p, void* stream, const float* q_pts, int6
                      int32_t h, const void* x, int32_t ci, const float* kernel_points, const float* deformed_kp, const float* modulations,
                      const GeomParams& g, void* wf, float* min_d2, const int32_t* order)
 {
-    dispatch([&](auto bf, auto nt, auto mode, auto def, auto cut) {
+    dispatch([&](auto bf, auto nt, auto mode, auto def, auto cut, auto kn) {
         using T = Row<bf.value>;
-        if constexpr (mode.value == 1 ? !cut.value : def.value == (mode.value == 2))
-            kpconv_gather_fwd_mfma_kernel<nt.value, mode.value, def.value != 0, true, T, 0, cut.value != 0><<<p.grid, 256, 0, (hipStream_t)stream>>>(
+        if constexpr ((mode.value == 1 ? !cut.value : def.value == (mode.value == 2)) && (kn.value == 15 || (!bf.value && mode.value != 2)))
+            kpconv_gather_fwd_mfma_kernel<nt.value, mode.value, def.value != 0, true, T, 0, cut.value != 0, false, kn.value>
+                <<<p.grid, 256, 0, (hipStream_t)stream>>>(
                 q_pts, nq, s_pts, ns, inds, h, (const T*)x, ci, kernel_points, deformed_kp, modulations, g, (T*)wf, min_d2, order);
-    }, Flag{p.bf16}, Pick<1, 2, 4, 8, 16>{p.n}, Pick<0, 1, 2>{p.mode}, Flag{p.def}, Flag{p.cut});
+    }, Flag{p.bf16}, Pick<1, 2, 4, 8, 16>{p.n}, Pick<0, 1, 2>{p.mode}, Flag{p.def}, Flag{p.cut}, Pick<WS_KP_SIZES>{p.k});
 }
 
 // kpconv_gather_fwd_kernel for ws_kpconv_gather_fwd* on the 3..4-channel input layer: float4 rows with one lane group, other rows in
@@ -742,13 +743,13 @@ void launch_fwd_pool(const GatherPlan& p, void* stream, const float* q_pts, int6
                      int32_t h, const void* x, int32_t ci, const float* kernel_points, const float* deformed_kp, const float* modulations,
                      const GeomParams& g, void* wf, float* min_d2, const int32_t* order)
 {
-    dispatch([&](auto bf, auto vec, auto mode, auto def) {
+    dispatch([&](auto bf, auto vec, auto mode, auto def, auto kn) {
         using T = Row<bf.value>;
-        if constexpr ((!bf.value || vec.value) && (mode.value == 1 || !def.value))
-            kpconv_gather_fwd_kernel<15, vec.value ? 1 : 4, mode.value, def.value != 0, vec.value != 0, vec.value ? 4 : 1, T>
+        if constexpr ((!bf.value || vec.value) && (mode.value == 1 || !def.value) && (kn.value == 15 || !bf.value))
+            kpconv_gather_fwd_kernel<kn.value, vec.value ? 1 : 4, mode.value, def.value != 0, vec.value != 0, vec.value ? 4 : 1, T>
                 <<<p.grid, 256, 0, (hipStream_t)stream>>>(
                 q_pts, nq, s_pts, ns, inds, h, (const T*)x, ci, kernel_points, deformed_kp, modulations, g, (T*)wf, min_d2, order);
-    }, Flag{p.bf16}, Flag{p.vec}, Pick<0, 1>{p.mode}, Flag{p.def});
+    }, Flag{p.bf16}, Flag{p.vec}, Pick<0, 1>{p.mode}, Flag{p.def}, Pick<WS_KP_SIZES>{p.k});
 }
 
 // kpconv_gather_fwd_mfma_kernel<..., FUSE> for ws_kpconv_layer_fwd_fused: rigid / linear / sum, 32 -> 32 f32 channels

@@ -9,9 +9,11 @@ namespace kpconv {
 
 // what a launcher launches; filled by the plan functions of kpconv.hip, read by launch_* and plan_text
 enum { GK_FWD_MFMA, GK_FWD_POOL, GK_BWD_X, GK_BWD_GEOM, GK_BWD_X_GRID, GK_BWD_X_GRIDW, GK_BWD_GEOM_DEF, GK_BWD_X_PACKED };
+#define WS_KP_SIZES 9, 13, 15     // the kernel sizes K the gather families instantiate
 struct GatherPlan {
     int kernel;         // GK_*: the kernel family
     bool bf16;          // row type T: bf16_t instead of float
+    int k;              // K: kernel points (WS_KP_SIZES; f32 rows and MODE 0 / 1 for the sizes other than 15)
     int n;              // NT (GK_FWD_MFMA), CK (GK_BWD_GEOM_DEF), G (the others; GK_BWD_GEOM has none)
     int mode;           // MODE
     bool def;           // DEF (the forward kernels)
@@ -67,7 +69,11 @@ void launch_bwd_geom(const GatherPlan& p, void* stream, const float* q_pts, int6
 void launch_bwd_geom_def(const GatherPlan& p, void* stream, const float* q_pts, int64_t nq, const float* s_pts, int64_t ns,
                          const int64_t* inds, int32_t h, const void* x, int32_t ci, const void* dwf, const float* kp4, const float* d_min_d2,
                          float extent, float* d_kp4, const int32_t* order);
-// kpconv_bwd_grid.hip
+// kpconv_bwd_grid.hip; launch_bwd_x_grid_k<KN>: kpconv_bwd_grid_kernels.h, one unit per kernel size
+template <int KN>
+void launch_bwd_x_grid_k(const GatherPlan& p, void* stream, const float* s_pts, int64_t ns, const GridView& v, int32_t nb, const void* dwf,
+                         int32_t ci, const float* kernel_points, const float* deformed_kp, const float* modulations, const GeomParams& g,
+                         void* dx, const int32_t* order, int32_t* overflow);
 void launch_bwd_x_grid(const GatherPlan& p, void* stream, const float* s_pts, int64_t ns, const GridView& v, int32_t nb, const void* dwf,
                        int32_t ci, const float* kernel_points, const float* deformed_kp, const float* modulations, const GeomParams& g,
                        void* dx, const int32_t* order, int32_t* overflow);

@@ -220,7 +220,7 @@ class _KPBlockFn(torch.autograd.Function):
         nq, ns = g.q_pts.shape[0], g.s_pts.shape[0]
         k = g.kp.shape[0]
         # saved activations in ONE arena: x1 | wf | x2 | pooled | arg
-        fused_layer = g.infer and g.conv_in == 32 and g.conv_out == 32 and not g.rows_sorted and FUSED_INFER
+        fused_layer = g.infer and k == 15 and g.conv_in == 32 and g.conv_out == 32 and not g.rows_sorted and FUSED_INFER
         sizes = [ns * g.conv_in if w1 is not None else 0, 0 if fused_layer else nq * k * g.conv_in, nq * g.conv_out if w2 is not None else 0,
                  nq * g.in_dim if (g.strided and w2 is not None) else 0, nq * g.in_dim if (g.strided and w2 is not None) else 0]
         offs, tot = [], 0
@@ -314,7 +314,7 @@ SKIP_SLOTS = os.environ.get("WEASAL_SKIP_SLOTS", "1") != "0"      # A/B switch: 
 
 
 def _conv_ok(conv, x):
-    return (FUSED_BLOCKS and x.is_cuda and x.dtype == torch.float32 and not conv.deformable and conv.K == 15
+    return (FUSED_BLOCKS and x.is_cuda and x.dtype == torch.float32 and not conv.deformable and ops.kernel_size_supported(conv.K)
             and conv.KP_influence == 'linear' and conv.aggregation_mode == 'sum' and ops.kpconv_gather is _KPCONV_GATHER)
 
 

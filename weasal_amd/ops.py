@@ -367,10 +367,18 @@ def deform_prepare(offset_features, kernel_points, extent, modulated):
     return _DeformPrepare.apply(offset_features, _f32c(kernel_points), float(extent), bool(modulated))
 
 
+def kernel_size_supported(k, bf16=False, mode=0):
+    """whether the gather entries run `k` kernel points with f32 / bf16 rows in this mode (0 rigid linear / sum, 1 generic,
+    2 the deformable fast path with packed kernel points): the library's own answer (ws_kpconv_supported_k)"""
+    return bool(_lib.lib().ws_kpconv_supported_k(int(k), 1 if bf16 else 0, int(mode)))
+
+
 def deform_fast_path_ok(x, k, influence, aggregation):
-    """the packed-kernel-point kernels cover: K = 15, linear influence, sum aggregation, GPU rows of a multiple of 16 channels"""
-    return (x.is_cuda and k == 15 and influence == "linear" and aggregation == "sum" and x.dim() == 2 and x.shape[1] % 16 == 0
-            and x.dtype in (torch.float32, torch.bfloat16) and kpconv_gather is _KPCONV_GATHER_SELF)
+    """the packed-kernel-point kernels cover: the kernel sizes built for MODE 2 (K = 15), linear influence, sum aggregation, GPU
+    rows of a multiple of 16 channels"""
+    return (x.is_cuda and influence == "linear" and aggregation == "sum" and x.dim() == 2 and x.shape[1] % 16 == 0
+            and x.dtype in (torch.float32, torch.bfloat16) and kernel_size_supported(k, x.dtype == torch.bfloat16, 2)
+            and kpconv_gather is _KPCONV_GATHER_SELF)
 
 
 class _KPConvGatherDef(torch.autograd.Function):

@@ -91,3 +91,119 @@ def test_ignored_labels_and_unvisited_points(gpu):
             assert np.array_equal(preds.cpu().numpy(), s["%s/%s/preds" % (tag, name)]), (tag, name)
             assert np.array_equal(conf.cpu().numpy(), s["%s/%s/conf" % (tag, name)]), (tag, name)
             assert np.array_equal(tester.IoU_from_confusions(conf.cpu().numpy()), s["%s/%s/iou" % (tag, name)])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# above the grid caps of csrc/tester.hip: argmin_partial_kernel and project_confusion_kernel get at most 1024 workgroups
+# of 256 threads and stride beyond 262 144 items; argmin_final_kernel strides beyond 256 partials (65 536 items)
+# ---------------------------------------------------------------------------------------------------------------
+TESTER_GRID = 1024 * 256
+
+
+def _tukey_reference(pot_points, pots, centre, radius):
+    """the Tukey update of tests/sampler_ref.py (RefSampler.batch), float64, on a copy"""
+    from sklearn.neighbors import KDTree
+    out = np.array(pots, dtype=np.float64)
+    inds, dists = KDTree(np.asarray(pot_points), leaf_size=10).query_radius(np.asarray(centre, np.float64).reshape(1, 3), r=radius,
+                                                                            return_distance=True)
+    d2s = np.square(dists[0])
+    tukeys = np.square(1 - d2s / np.square(radius))
+    tukeys[d2s > np.square(radius)] = 0
+    out[inds[0]] += tukeys
+    return out, inds[0]
+
+
+@pytest.fixture(scope="module")
+def capped_pot_points():
+    import sampler_capped_scene as cs
+    return cs.scene().pot_points[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("start", ["random", "constant", "last", "one_point", "whole_cloud"])
+def test_potentials_update_above_the_grid_caps(gpu, capped_pot_points, start):
+    """start potentials as the sampler draws them (below 1e-3), so the updated ones stay O(1) and the bound of
+    test_projection_votes_confusion_potentials_on_the_gpu, 4e-16 absolute, applies as it stands.
+    random: no ties; constant: the arg-min is the first index outside the ball, among equal values in every workgroup and
+    trip; last: a unique minimum at index p - 1 (the last item of the second trip); one_point: n = 1; whole_cloud: a ball
+    that holds every point, so every potential changes."""
+    from weasal_amd import tester
+    pp = capped_pot_points
+    p = len(pp)
+    assert p > TESTER_GRID
+    radius = 1.0
+    centre = pp[0].astype(np.float64) + np.array([0.03, -0.02, 0.01])
+    rs = np.random.RandomState(4140)
+    pots0 = rs.rand(p) * 1e-3
+    if start in ("constant", "last"):
+        pots0 = np.full(p, 5e-4)
+    if start == "last":
+        pots0[p - 1] = 1e-4
+    if start == "one_point":
+        pp, pots0 = pp[:1], pots0[:1]
+    if start == "whole_cloud":
+        centre, radius = np.array([0.5, -0.25, 0.0]), 40.0
+    want, ball = _tukey_reference(pp, pots0, centre, radius)
+    n = len(pp)
+    if start == "whole_cloud":
+        assert len(ball) == n
+    elif start == "one_point":
+        assert len(ball) == 1
+    else:
+        assert 100 < len(ball) < n // 100 and 0 in ball and n - 1 not in ball
+    pots = torch.from_numpy(pots0).to(gpu)
+    mn, am = tester.update_potentials(torch.from_numpy(pp).to(gpu), pots, centre, radius)
+    got = pots.cpu().numpy()
+    err = np.abs(got - want).max()
+    print("potentials %s: n = %d, %d workgroups, %d partials for the final step, items visited in a second trip %d, "
+          "%d in the ball, max |diff| = %.3g" % (start, n, min(-(-n // 256), 1024), min(-(-n // 256), 1024),
+                                                 max(n - TESTER_GRID, 0), len(ball), err))
+    assert err <= 4e-16
+    outside = np.setdiff1d(np.arange(n), ball)
+    assert np.array_equal(got[outside], pots0[outside])                              # untouched: the same bits
+    assert int(am.item()) == int(np.argmin(want)) == int(np.argmin(got))
+    assert float(mn.item()) == float(got.min())
+    if start == "constant":
+        assert int(am.item()) == outside[0] and (got[outside] == 5e-4).all()
+    if start == "last":
+        assert int(am.item()) == n - 1 >= TESTER_GRID
+
+
+@pytest.mark.gpu
+def test_predictions_and_confusion_above_the_grid_cap(gpu):
+    """300 000 rows re-projected onto a vote table of 5 000 rows, c = 9: project_confusion_kernel strides.  Labels outside
+    the table are not counted; a row of all-zero votes and a row with two equal maxima take the first maximum."""
+    from weasal_amd import tester
+    rows, m, c = 5000, 300000, 9
+    assert m > TESTER_GRID
+    rs = np.random.RandomState(4150)
+    probs = rs.rand(rows, c).astype(np.float32)
+    probs[rs.choice(rows, size=400, replace=False)] = 0                             # never voted on
+    tied = rs.choice(rows, size=400, replace=False)
+    probs[tied, 6] = probs[tied, 2] = probs[tied].max(axis=1)                       # two equal maxima: column 2 wins
+    proj = rs.randint(0, rows, size=m).astype(np.int32)
+    labels = rs.randint(0, c, size=m).astype(np.int32)
+    outside = rs.choice(m - 1, size=3000, replace=False)
+    labels[outside] = rs.choice([9, 11, 40], size=3000)
+    labels[m - 1], proj[m - 1] = 3, rows - 1                                        # the last row of the second trip is counted
+    votes = tester.VoteAccumulator([rows], c, gpu)
+    votes.probs[0].copy_(torch.from_numpy(probs))
+    preds, conf = votes.predictions(0, proj=torch.from_numpy(proj).to(gpu), labels=torch.from_numpy(labels).to(gpu))
+    preds, conf = preds.cpu().numpy(), conf.cpu().numpy()
+    want = np.argmax(probs[proj], axis=1)
+    assert preds.dtype == np.int32 and np.array_equal(preds, want)
+    zero, two = (probs[proj] == 0).all(axis=1), np.isin(proj, tied)
+    assert zero[TESTER_GRID:].any() and two[TESTER_GRID:].any() and (want[zero] == 0).all() and (want[two & ~zero] <= 2).all()
+    counted = labels < c
+    assert counted.sum() == m - 3000 and (~counted[TESTER_GRID:]).any()
+    assert conf.dtype == np.int64 and np.array_equal(conf, tester.fast_confusion(labels[counted], want[counted].astype(np.int32),
+                                                                                   np.arange(c)))
+    assert conf.sum() == m - 3000
+    # the sub-cloud path (no projection) on the same number of rows
+    big = tester.VoteAccumulator([m], c, gpu)
+    big.probs[0].copy_(torch.from_numpy(probs[proj]))
+    preds2, conf2 = big.predictions(0, labels=torch.from_numpy(labels).to(gpu))
+    assert np.array_equal(preds2.cpu().numpy(), want) and np.array_equal(conf2.cpu().numpy(), conf)
+    print("project_confusion: m = %d rows, 1024 workgroups, rows visited in a second trip %d (%d of them all-zero, %d tied, "
+          "%d with a label outside the table)" % (m, m - TESTER_GRID, zero[TESTER_GRID:].sum(), two[TESTER_GRID:].sum(),
+                                                  (~counted[TESTER_GRID:]).sum()))

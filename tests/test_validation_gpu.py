@@ -90,9 +90,92 @@ def _loop_and_batch(gpu, c, smooth, lengths, inds, tiles, sizes, logits, points=
     return start, [p.cpu().numpy() for p in loop.probs], [p.cpu().numpy() for p in one.probs]
 
 
-@pytest.mark.parametrize("smooth", [0.95, 0.5])
-@pytest.mark.parametrize("c", [4, 9])
-def test_one_launch_equals_the_loop_over_spheres(gpu, c, smooth):
+VAL_GRID = 1024 * 256                                              # csrc/validation.hip: ws_grid(n, 256, 1024) rows per trip
+
+
+def _capped_batch(rng, in_radius=1.0):
+    """eight spheres of 40 000 rows, 320 000 in all (validation_kernel strides beyond 262 144), on two tiles of 70 000
+    points: every sphere lists more than half of its tile, so every pair on a tile shares thousands of points and the
+    owner of a point sits up to seven spheres after its first member.  The last two spheres are on the same tile and the
+    second trip of the grid starts inside the first of them: it holds rows that own their point and rows that do not.
+    Points centred on the sphere, uniform in the ball of radius in_radius: the radius mask 0.7 keeps about a third"""
+    nb, rows, size = 8, 40000, 70000
+    tiles = np.array([0, 1, 0, 1, 0, 1, 0, 0], np.int32)
+    inds = np.concatenate([np.sort(rng.choice(size, size=rows, replace=False)) for _ in range(nb)]).astype(np.int64)
+    u = rng.standard_normal((nb * rows, 3))
+    pts = (u / np.linalg.norm(u, axis=1, keepdims=True) * (in_radius * rng.random((nb * rows, 1)) ** (1 / 3))).astype(np.float32)
+    return np.full(nb, rows, np.int32), inds, tiles, pts, [size, size]
+
+
+def _assert_capped_batch(gpu, c, smooth):
+    """the cases above the grid cap, by the criterion of the small ones: votes within BOUND of the loop over spheres (the
+    two kernels are separate compilations and may contract smooth * p + (1 - smooth) * q differently: one ulp of a product
+    per update; the identity of the bits is printed), status words zero, and the confusion of the
+    same launch equal to the numpy count.  At smooth = 0.5 both products are exact whatever the contraction, one rounding
+    is left, and the bits must be the loop's: an update applied out of sphere order or by two rows would change them."""
+    from weasal_amd import tester, validation
+    dev = _dev(gpu)
+    rng = np.random.default_rng(12)
+    rm = 0.7
+    lengths, inds, tiles, pts, sizes = _capped_batch(rng)
+    n = len(inds)
+    assert n > VAL_GRID
+    logits = (rng.standard_normal((n, c)) * 2).astype(np.float32)
+    start, loop, one = _loop_and_batch(gpu, c, smooth, lengths, inds, tiles, sizes, logits, points=pts, radius_mask=rm)
+    inside = (pts[:, 0] * pts[:, 0] + pts[:, 1] * pts[:, 1]) + pts[:, 2] * pts[:, 2] < np.float32(rm) ** 2
+    offs = np.cumsum(lengths) - lengths
+    late_rows = 0
+    for t, (s, a, b) in enumerate(zip(start, loop, one)):
+        rows = np.concatenate([np.arange(o, o + k) for o, k, tl in zip(offs, lengths, tiles) if tl == t])
+        rows = rows[inside[rows]]
+        listed = np.unique(inds[rows])
+        rest = np.setdiff1d(np.arange(len(s)), listed)
+        assert len(rest) > 1000 and np.array_equal(b[rest], s[rest])            # untouched rows: the same bits
+        assert (b[listed] != s[listed]).any(axis=1).all()
+        shared = len(rows) - len(listed)
+        late_rows += int((rows >= VAL_GRID).sum())
+        err = np.abs(a - b).max()
+        print("capped batch c=%d smooth=%g tile %d: n = %d rows, 1024 workgroups, rows visited in a second trip %d, %d points voted on, "
+              "%d further listings of them, one launch against the loop: max |diff| = %.3g, bit-identical: %s"
+              % (c, smooth, t, n, n - VAL_GRID, len(listed), shared, err, np.array_equal(a, b)))
+        assert shared > 5000
+        assert err <= BOUND
+        if smooth == 0.5:
+            assert np.array_equal(a, b)
+    assert late_rows > 1000                                                    # unmasked rows of the second trip
+    s6, s7 = (np.arange(offs[b], offs[b] + lengths[b]) for b in (6, 7))
+    s6, s7 = s6[inside[s6] & (s6 >= VAL_GRID)], s7[inside[s7]]
+    passed_on = int(np.isin(inds[s6], inds[s7]).sum())                          # second-trip rows whose point the last sphere owns
+    assert 100 < passed_on < len(s6) - 100
+    want = ref.vote_batch([s.astype(np.float64) for s in start], logits, lengths, inds, tiles, smooth=smooth, points=pts, radius_mask=rm)
+    for w, b in zip(want, one):
+        assert np.abs(w - b).max() <= BOUND
+    # the confusion of such a launch: every row counts, masked or not, labels outside the table go to the status word
+    lv = np.arange(c)
+    labels = rng.integers(0, c, size=n).astype(np.int64)
+    bad = rng.choice(n, size=500, replace=False)
+    good = np.setdiff1d(np.arange(n), bad)
+    labels[bad] = rng.choice([-1, c, c + 7], size=500)
+    true_row, pred_row, _ = validation.confusion_tables(lv, [])
+    acc = tester.VoteAccumulator(sizes, c, gpu, test_smooth=smooth)
+    for p, s in zip(acc.probs, start):
+        p.copy_(dev(s))
+    conf = torch.zeros((c, c), dtype=torch.int64, device=gpu)
+    acc.update_batch(dev(logits), lengths, dev(inds), tiles, points0=dev(pts), radius_mask=rm, labels=dev(labels),
+                     true_row=dev(true_row), pred_row=dev(pred_row), confusion=conf)
+    assert acc.batch_status.cpu().tolist() == [0, 0, 500] and (bad >= VAL_GRID).any()
+    assert np.array_equal(conf.cpu().numpy(), ref.batch_confusion(logits[good], labels[good], lv, []))
+    for p, b in zip(acc.probs, one):
+        assert np.array_equal(p.cpu().numpy(), b)                               # the votes do not depend on the labels
+
+
+@pytest.mark.parametrize("c,smooth,capped", [(4, 0.95, False), (9, 0.95, False), (4, 0.5, False), (9, 0.5, False), (4, 0.95, True),
+                                             (4, 0.5, True)],
+                         ids=["4-0.95", "9-0.95", "4-0.5", "9-0.5", "4-0.95-capped", "4-0.5-capped"])
+def test_one_launch_equals_the_loop_over_spheres(gpu, c, smooth, capped):
+    if capped:
+        _assert_capped_batch(gpu, c, smooth)
+        return
     rng = np.random.default_rng(11)
     lengths, inds, tiles, sizes = _constructed_batch(rng)
     logits = (rng.standard_normal((len(inds), c)) * 2).astype(np.float32)

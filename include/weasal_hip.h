@@ -1075,6 +1075,25 @@ int ws_sgd_step(float* const* h_params, const float* const* h_grads, float* cons
                 float lr, float momentum, float weight_decay, float clip_value, int32_t first, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Clip by norm inside the update: utils/trainer_WeakLabel.py:216 (torch.nn.utils.clip_grad_norm_) followed by
+ * optimizer.step() (the optimizer of :72-82), weasal_amd/csrc/optim.hip.
+ * ws_grad_norm: out[0] = total 2-norm of the `count` gradient tensors (HOST arrays of device pointers / element counts, all
+ *   parameter groups in one call), out[1] = coef = min(1, max_norm / (out[0] + 1e-6)); out is device memory, nothing is read
+ *   back.  Every workgroup writes the sum of squares of its WS_SGD_CHUNK elements into a slot of its own, a finishing launch
+ *   adds the slots in index order: no float atomic, run-to-run bit-identical.  slots: device scratch of nslots >=
+ *   ws_grad_norm_slots(h_sizes, count) floats.  The tensor table travels in the kernel arguments, WS_SGD_MAX tensors per launch.
+ * ws_sgd_step_scaled: ws_sgd_step with g = g * coef[0] (the device word ws_grad_norm wrote) in front of weight decay and
+ *   momentum instead of the clamp; the scaled gradient is written back to h_grads (what clip_grad_norm_ leaves in p.grad).
+ * ------------------------------------------------------------------------------------------ */
+#define WS_SGD_MAX 96
+#define WS_SGD_CHUNK 4096
+int64_t ws_grad_norm_slots(const int64_t* h_sizes, int32_t count);
+int ws_grad_norm(const float* const* h_grads, const int64_t* h_sizes, int32_t count, float max_norm, float* slots, int64_t nslots,
+                 float* out, void* stream);
+int ws_sgd_step_scaled(float* const* h_params, float* const* h_grads, float* const* h_bufs, const int64_t* h_sizes, int32_t count,
+                       float lr, float momentum, float weight_decay, const float* coef, int32_t first, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Deformable KPConv, the fast path of BASELINE config 5 (models/blocks.py:244-325, 366-367 with KP_influence = 'linear',
  * aggregation_mode = 'sum'; neighbour rows of several hundred columns: datasets/common.py:500-502).
  *
@@ -1226,6 +1245,40 @@ int ws_channel_attention_fwd(const float* x1, const float* x2, const float* valu
 int ws_channel_attention_bwd(const float* x1, const float* x2, const float* value, const float* a, const float* d_out, int64_t n,
                              int32_t c, const int64_t* lengths, int32_t nspheres, int32_t max_minus, float* d_x1, float* d_x2,
                              float* d_value, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * What follows the attention blocks in the weak-label step of KPFCNN_mprm, weasal_amd/csrc/mprm_head.hip.  The four paths lie
+ * side by side in one [rows, heads * c] tensor (row pitch ldx >= heads * c).  float32 throughout, no float atomics, every sum
+ * in an order fixed by the shapes: run-to-run bit-identical.  Nothing is read back.
+ *
+ * ws_segment_mean_fwd (global_average, models/blocks.py:114-134: split / mean / stack): out [nspheres, w] = per sphere the sum
+ *   of its rows of x [n, w] (row pitch ldx >= w: a column view works) in a fixed order, divided by the length; a sphere of
+ *   length 0 gives nan as torch.mean does.  `lengths`: HOST vector as in the attention entries (offsets in the kernel
+ *   arguments, more than WS_ATT_MAX_SPHERES spheres is WS_ERR_UNSUPPORTED); 1 <= w <= WS_SEGMENT_MAX_WIDTH.
+ * ws_segment_mean_bwd: dx [n, w] contiguous, dx[row, :] = d_out[sphere(row), :] / length (d_out row pitch ldd).
+ * ws_max_heads_fwd (models/architectures.py:700-702: torch.max(torch.max(torch.max(h0, h1), h2), h3)): out [n, c] contiguous =
+ *   the maximum over the `heads` column blocks of x, nested from the left, nan propagating; heads <= WS_HEADS_MAX.
+ * ws_max_heads_bwd: dx [n, heads * c] contiguous = the backward of that nested expression as autograd runs it: per
+ *   maximum(a, b) both sides get (a == b ? g / 2 : g), a's zeroed where a < b and b's where a > b, outermost first.
+ * ws_bce_heads_fwd (models/architectures.py:709-733 and :778-783: BCEWithLogitsLoss(weight = class_w) per path, summed):
+ *   out[k] = mean over r rows and c columns of weight[col] * (max(x, 0) - x y + log1p(exp(-|x|))) for column block k of x
+ *   against target [r, c] (contiguous), out[heads] = out[0] + out[1] + ... in that order; weight NULL = ones; r >= 1.
+ * ws_bce_heads_bwd: dx [r, heads * c] contiguous = (g_heads[k] + g_sum[0]) * weight[col] * (sigmoid(x) - y) / (r c); g_heads
+ *   [heads] and g_sum [1] are device floats (either may be NULL = zero, not both): nothing synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define WS_SEGMENT_MAX_WIDTH 1024
+#define WS_HEADS_MAX 8
+int ws_segment_mean_fwd(const float* x, int64_t n, int32_t w, int64_t ldx, const int64_t* lengths, int32_t nspheres, float* out,
+                        void* stream);
+int ws_segment_mean_bwd(const float* d_out, int64_t ldd, int64_t n, int32_t w, const int64_t* lengths, int32_t nspheres, float* dx,
+                        void* stream);
+int ws_max_heads_fwd(const float* x, int64_t n, int32_t c, int32_t heads, int64_t ldx, float* out, void* stream);
+int ws_max_heads_bwd(const float* x, int64_t n, int32_t c, int32_t heads, int64_t ldx, const float* d_out, int64_t ldd, float* dx,
+                     void* stream);
+int ws_bce_heads_fwd(const float* x, int64_t r, int32_t c, int32_t heads, int64_t ldx, const float* target, const float* weight,
+                     float* out, void* stream);
+int ws_bce_heads_bwd(const float* x, int64_t r, int32_t c, int32_t heads, int64_t ldx, const float* target, const float* weight,
+                     const float* g_heads, const float* g_sum, float* dx, void* stream);
 
 #ifdef __cplusplus
 }

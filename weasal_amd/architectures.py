@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import fused, ops
+from . import blocks as _blocks, fused, ops
 from .blocks import KPConv, NearestUpsampleBlock, UnaryBlock, block_decider, closest_pool
 from .regions import SphereRegions
 
@@ -433,6 +433,8 @@ class KPFCNN_mprm(nn.Module):
             x = block_op(x, batch)
         x = self.ele_head(x, ele_down, batch)
         spa_att, cha_att, no_att, poi_att = self.multi_att(x, batch)
+        if _blocks.wl_ends(no_att, poi_att, spa_att, cha_att):
+            return self._forward_side_by_side(batch, no_att, poi_att, spa_att, cha_att)
         cla_logits = [self.no_ga(no_att, batch), self.da_ga(poi_att, batch), self.spa_ga(spa_att, batch),
                       self.cha_ga(cha_att, batch)]
         for block_op in self.decoder_blocks:
@@ -443,19 +445,56 @@ class KPFCNN_mprm(nn.Module):
         x = torch.max(torch.max(torch.max(no_att, poi_att), spa_att), cha_att)
         return x, cla_logits, [no_att, poi_att, spa_att, cha_att]
 
+    def _forward_side_by_side(self, batch, *paths):
+        """the rest of forward() with the class maps of the paths (no, point-wise, spatial, channel attention) as the column
+        blocks of ONE [N, 4 C] tensor: one per-sphere mean (the four global_average_blocks are parameter-free and share the
+        attention level), one pass through a decoder of nearest upsamplings (row copies: every column keeps its bits) and
+        one maximum over the heads.  The class logits and the CAMs returned are column views of the wide tensors, which the
+        loss methods recognise (ops.side_by_side).  Any other decoder block runs per path as before."""
+        from .blocks import global_average
+        k = len(paths)
+        c = int(paths[0].shape[1])
+        wide = torch.cat(paths, dim=1)
+        means = global_average(wide, _blocks._layer_lengths(batch, self.no_ga.layer_ind))      # (__init__: one level for all four)
+        cla_logits = [means[:, i * c:(i + 1) * c] for i in range(k)]
+        if all(isinstance(b, NearestUpsampleBlock) for b in self.decoder_blocks):
+            for block_op in self.decoder_blocks:
+                wide = block_op(wide, batch)
+            cam = [wide[:, i * c:(i + 1) * c] for i in range(k)]
+            return ops.max_heads(wide, k), cla_logits, cam
+        cam = list(paths)
+        for block_op in self.decoder_blocks:
+            cam = [block_op(p, batch) for p in cam]
+        x = cam[0]
+        for p in cam[1:]:
+            x = torch.max(x, p)
+        return x, cla_logits, cam
+
+    def _bce_heads(self, wide, target, heads):
+        """(per-path losses [heads], their sum) of criterion_multi on the column blocks of `wide`: one launch each way"""
+        return ops.bce_with_logits_heads(wide, target, self.criterion_multi.weight, heads)
+
     def class_logits_loss(self, class_logits, cloud_lb):
         """BCE-with-logits of the four per-sphere class logits against one weak label vector per sphere, plus the
         deformable regulariser (architectures.py:709-733)"""
-        self.output_loss1 = self.criterion_multi(class_logits[0], cloud_lb)
-        self.output_loss2 = self.criterion_multi(class_logits[1], cloud_lb)
-        self.output_loss3 = self.criterion_multi(class_logits[2], cloud_lb)
-        self.output_loss4 = self.criterion_multi(class_logits[3], cloud_lb)
+        wide = ops.side_by_side(class_logits) if len(class_logits) == 4 else None
+        if wide is not None and _blocks.wl_ends(wide, cloud_lb):
+            per_path, total = self._bce_heads(wide, cloud_lb, 4)
+            self.output_loss1, self.output_loss2, self.output_loss3, self.output_loss4 = per_path.unbind(0)
+        else:
+            total = None
+            self.output_loss1 = self.criterion_multi(class_logits[0], cloud_lb)
+            self.output_loss2 = self.criterion_multi(class_logits[1], cloud_lb)
+            self.output_loss3 = self.criterion_multi(class_logits[2], cloud_lb)
+            self.output_loss4 = self.criterion_multi(class_logits[3], cloud_lb)
         if self.deform_fitting_mode == 'point2point':
             self.reg_loss = p2p_fitting_regularizer(self)
         elif self.deform_fitting_mode == 'point2plane':
             raise ValueError('point2plane fitting mode not implemented yet.')
         else:
             raise ValueError('Unknown fitting mode: ' + self.deform_fitting_mode)
+        if total is not None:
+            return total + self.reg_loss
         return self.output_loss1 + self.output_loss2 + self.output_loss3 + self.output_loss4 + self.reg_loss
 
     def region_mprm_loss(self, cam, regions_all, regions_lb, batch_lengths):
@@ -464,6 +503,11 @@ class KPFCNN_mprm(nn.Module):
         per-sphere lists, or a regions.SphereRegions (device CSR): then the maps go side by side through ops.region_mean, no
         host array is built, nothing is uploaded, and regions_lb / batch_lengths are not looked at"""
         if isinstance(regions_all, SphereRegions):
+            wide = ops.side_by_side(cam)
+            if wide is not None and _blocks.wl_ends(wide, regions_all.lb):
+                # the maps already lie side by side (forward): no torch.cat, and the four losses are one launch each way
+                _, self.output_loss = self._bce_heads(ops.region_mean(wide, regions_all), regions_all.lb, len(cam))
+                return self.output_loss
             c = int(cam[0].shape[1])
             averaged = ops.region_mean(torch.cat(list(cam), dim=1), regions_all)      # [R, K * C]
             self.output_loss = 0

@@ -29,6 +29,7 @@ from .kernel_points import load_kernels
 
 DEFORM_FAST_PATH = os.environ.get("WEASAL_DEFORM_FAST", "1") != "0"      # A/B switch (diagnostics, tests): 0 = generic kernels
 ATT_KERNELS = os.environ.get("WEASAL_ATT_KERNELS", "1") != "0"           # A/B switch: 0 = the attention blocks loop over spheres with torch.matmul
+WL_ENDS = os.environ.get("WEASAL_WL_ENDS", "1") != "0"                   # A/B switch: 0 = the weak-label step ends in framework operators (mean loop, per-path decoder, nested max, four BCE losses, clip_grad_norm_)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -64,8 +65,19 @@ def _layer_lengths(batch, layer_ind):
     return lh[layer_ind] if lh is not None else batch.lengths[layer_ind]
 
 
+def wl_ends(*tensors):
+    """whether the weak-label step's ends run as kernels of mprm_head.hip on these tensors: WEASAL_WL_ENDS is not 0 and all are
+    float32 device tensors (CPU tensors -- oracle.kpconv_ref.cpu_reference_mode -- and other dtypes keep the framework path)"""
+    return WL_ENDS and all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
 def global_average(x, batch_lengths):
-    """per-cloud mean of the stacked features (blocks.py:114-134)"""
+    """per-cloud mean of the stacked features (blocks.py:114-134): ONE launch of ops.segment_mean for float32 device features
+    and host lengths of at most 64 spheres; CPU tensors, other dtypes, a length vector that lives on the device only
+    (reading it would synchronise) and more spheres take the reference's split / mean / stack loop"""
+    host_lengths = not (isinstance(batch_lengths, torch.Tensor) and batch_lengths.is_cuda)
+    if host_lengths and x.dim() == 2 and wl_ends(x) and ops.segment_mean_supported(x.shape[1], len(batch_lengths)):
+        return ops.segment_mean(x, batch_lengths.tolist() if hasattr(batch_lengths, "tolist") else batch_lengths)
     lengths = [int(v) for v in batch_lengths]
     return torch.stack([chunk.mean(dim=0) for chunk in torch.split(x, lengths, dim=0)])
 

@@ -1664,3 +1664,150 @@ def channel_attention(x1, x2, value, lengths, max_minus):
     if x1.dim() != 2 or x2.shape != x1.shape or value.shape != x1.shape:
         raise ValueError("channel_attention: x1, x2 and value must share one [N, c] shape")
     return _ChannelAttention.apply(x1, x2, value, lengths, max_minus)
+
+
+# ------------------------------------------------------------------------------------------------
+# what follows the attention blocks in the weak-label step (weasal_amd/csrc/mprm_head.hip): per-sphere mean, maximum over
+# heads, multi-head BCE with logits.  The heads lie side by side in one [rows, heads * C] tensor.
+# ------------------------------------------------------------------------------------------------
+SEGMENT_MAX_WIDTH = 1024         # WS_SEGMENT_MAX_WIDTH
+HEADS_MAX = 8                    # WS_HEADS_MAX
+
+
+def _rows_f32(t):
+    """`t` [N, W] as the kernels read it -- float32 rows of unit column stride at a pitch of at least W: a column view
+    passes as it is -- and its row pitch"""
+    t = t.detach()
+    if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.to(torch.float32).contiguous()
+    return t, int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))
+
+
+def segment_mean_supported(w, nspheres):
+    """the shapes ws_segment_mean_* take: 1 to 1024 columns, at most 64 spheres"""
+    return 1 <= int(w) <= SEGMENT_MAX_WIDTH and int(nspheres) <= ATT_MAX_SPHERES
+
+
+class _SegmentMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, lengths):
+        xc, ldx = _rows_f32(x)
+        n, w = int(xc.shape[0]), int(xc.shape[1])
+        lens, ns = _att_lengths(lengths, n)
+        out = torch.empty((ns, w), dtype=torch.float32, device=x.device)
+        check(_lib.lib().ws_segment_mean_fwd(ptr(xc), n, w, ldx, lens, ns, ptr(out), current_stream()))
+        ctx.lengths, ctx.n = lengths, n
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        g, ldd = _rows_f32(d_out)                  # (a copy of an expanded gradient: alive until the call is queued)
+        w = int(g.shape[1])
+        lens, ns = _att_lengths(ctx.lengths, ctx.n)
+        dx = torch.empty((ctx.n, w), dtype=torch.float32, device=g.device)
+        check(_lib.lib().ws_segment_mean_bwd(ptr(g), ldd, ctx.n, w, lens, ns, ptr(dx), current_stream()))
+        return dx, None
+
+
+def segment_mean(x, lengths):
+    """out [B, W]: the mean of the rows of every sphere of x [N, W] (global_average, models/blocks.py:114-134); float32 on the
+    device, `lengths` a HOST sequence of B <= 64 sphere sizes summing to N, 1 <= W <= 1024, rows of unit column stride at
+    any pitch (a column view is read in place).  A sphere of length 0 gives a nan row, as torch.mean does.  Differentiable
+    in x; both directions are run-to-run bit-identical."""
+    _need_cuda(x)
+    if x.dim() != 2:
+        raise ValueError("segment_mean: x must be [N, W]")
+    return _SegmentMean.apply(x, [int(v) for v in lengths])
+
+
+class _MaxHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, heads):
+        xc, ldx = _rows_f32(x)
+        n, c = int(xc.shape[0]), int(xc.shape[1]) // heads
+        out = torch.empty((n, c), dtype=torch.float32, device=x.device)
+        check(_lib.lib().ws_max_heads_fwd(ptr(xc), n, c, heads, ldx, ptr(out), current_stream()))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(xc)
+        ctx.heads, ctx.ldx = heads, ldx
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        xc, = ctx.saved_tensors
+        g, ldd = _rows_f32(d_out)
+        n, c = int(g.shape[0]), int(g.shape[1])
+        dx = torch.empty((n, ctx.heads * c), dtype=torch.float32, device=g.device)
+        check(_lib.lib().ws_max_heads_bwd(ptr(xc), n, c, ctx.heads, ctx.ldx, ptr(g), ldd, ptr(dx), current_stream()))
+        return dx, None
+
+
+def max_heads(x, heads):
+    """out [N, C] = torch.max(torch.max(torch.max(h0, h1), h2), ...) over the `heads` column blocks of x [N, heads * C]
+    (models/architectures.py:700-702), bit-identical to the nested form; the backward is the nested expression's as autograd
+    defines it, ties included (each maximum halves the gradient between equal operands).  One launch each way."""
+    _need_cuda(x)
+    heads = int(heads)
+    if x.dim() != 2 or heads < 1 or x.shape[1] % heads != 0 or x.shape[1] == 0:
+        raise ValueError("max_heads: x must be [N, heads * C]")
+    return _MaxHeads.apply(x, heads)
+
+
+class _BceHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, target, weight, heads):
+        xc, ldx = _rows_f32(x)
+        tc, wc = _f32c(target), _f32c(weight)
+        r, c = int(tc.shape[0]), int(tc.shape[1])
+        out = torch.empty((heads + 1,), dtype=torch.float32, device=x.device)
+        check(_lib.lib().ws_bce_heads_fwd(ptr(xc), r, c, heads, ldx, ptr(tc), ptr(wc), ptr(out), current_stream()))
+        ctx.save_for_backward(xc, tc, wc)
+        ctx.heads, ctx.ldx = heads, ldx
+        ctx.set_materialize_grads(False)
+        return out[:heads], out[heads]
+
+    @staticmethod
+    def backward(ctx, g_heads, g_sum):
+        xc, tc, wc = ctx.saved_tensors
+        r, c = int(tc.shape[0]), int(tc.shape[1])
+        dx = torch.empty((r, ctx.heads * c), dtype=torch.float32, device=xc.device)
+        if g_heads is None and g_sum is None:
+            return dx.zero_(), None, None, None
+        gh, gs = _f32c(g_heads), _f32c(g_sum)
+        check(_lib.lib().ws_bce_heads_bwd(ptr(xc), r, c, ctx.heads, ctx.ldx, ptr(tc), ptr(wc), ptr(gh), ptr(gs), ptr(dx),
+                                          current_stream()))
+        return dx, None, None, None
+
+
+def bce_with_logits_heads(x, target, weight, heads):
+    """(per_head [heads], total): per_head[k] = BCEWithLogitsLoss(weight)(x[:, k C:(k + 1) C], target), total = their sum in
+    head order (models/architectures.py:709-733, 778-783); x [R, heads * C] float32 on the device, target [R, C], weight [C]
+    or None.  One launch forward, one backward (the incoming gradients stay on the device); stable for any |x|.  R = 0 is
+    refused: the mean of nothing."""
+    _need_cuda(x, target, weight)
+    heads = int(heads)
+    if x.dim() != 2 or target.dim() != 2 or heads < 1 or x.shape[0] != target.shape[0] or x.shape[1] != heads * target.shape[1]:
+        raise ValueError("bce_with_logits_heads: x must be [R, heads * C] and target [R, C]")
+    if x.shape[0] == 0 or target.shape[1] == 0:
+        raise ValueError("bce_with_logits_heads: empty input (R = 0): skip the batch before the loss")
+    if weight is not None and tuple(weight.shape) != (target.shape[1],):
+        raise ValueError("bce_with_logits_heads: weight must be [C]")
+    return _BceHeads.apply(x, target, weight, heads)
+
+
+def side_by_side(tensors):
+    """the [N, K * C] tensor whose K column blocks the given tensors are, in order (each `base[:, k C:(k + 1) C]`), or None"""
+    if not isinstance(tensors, (list, tuple)) or not tensors:
+        return None
+    base = getattr(tensors[0], "_base", None)
+    if base is None or base.dim() != 2 or not base.is_contiguous():
+        return None
+    c = int(tensors[0].shape[1]) if tensors[0].dim() == 2 else 0
+    if c == 0 or base.shape[1] != c * len(tensors):
+        return None
+    for k, t in enumerate(tensors):
+        b = getattr(t, "_base", None)
+        if (b is None or b.data_ptr() != base.data_ptr() or b.shape != base.shape or t.dim() != 2 or t.shape != (base.shape[0], c)
+                or t.stride() != base.stride() or t.storage_offset() != base.storage_offset() + k * c or t.dtype != base.dtype):
+            return None
+    return base

@@ -10,6 +10,7 @@ and are deliberately not reproduced.
 """
 import torch
 
+from . import blocks as _blocks
 from .regions import SphereRegions
 
 
@@ -31,16 +32,51 @@ class FusedSGD(torch.optim.SGD):
                 return False
         return True
 
-    @torch.no_grad()
-    def step(self, closure=None, clip_value=0.0):
+    def fusable(self):
+        """whether step() would run the kernels now: every group with gradients is one the kernel covers"""
+        return all(self._fusable(g, ps) for g, ps in ((g, [p for p in g['params'] if p.grad is not None]) for g in self.param_groups) if ps)
+
+    def _grad_norm(self, lib, params, max_norm):
+        """ws_grad_norm over the gradients of all groups -> device floats [total_norm, coef]; no synchronisation"""
         import ctypes
         from . import _lib
+        n = len(params)
+        sizes = (ctypes.c_int64 * n)(*[p.numel() for p in params])
+        dev = params[0].device
+        with torch.cuda.device(dev):
+            nslots = int(lib.ws_grad_norm_slots(sizes, n))
+            slots = torch.empty((max(nslots, 1),), dtype=torch.float32, device=dev)
+            out = torch.empty((2,), dtype=torch.float32, device=dev)
+            _lib.check(lib.ws_grad_norm((ctypes.c_void_p * n)(*[p.grad.data_ptr() for p in params]), sizes, n, float(max_norm),
+                                        _lib.ptr(slots), nslots, _lib.ptr(out), _lib.current_stream()))
+        return out
+
+    @torch.no_grad()
+    def step(self, closure=None, clip_value=0.0, clip_norm=0.0):
+        """clip_value: torch.nn.utils.clip_grad_value_ inside the update (trainer_PseudoLabel.py:216).  clip_norm:
+        torch.nn.utils.clip_grad_norm_ over ALL groups inside the update (trainer_WeakLabel.py:216): ws_grad_norm leaves the
+        total norm and the coefficient on the device, ws_sgd_step_scaled multiplies every gradient by it on the way (and
+        writes it back, so p.grad holds what clip_grad_norm_ leaves); `self.grad_norm` is the norm, a device scalar."""
+        import ctypes
+        from . import _lib
+        if clip_value and clip_value > 0 and clip_norm and clip_norm > 0:
+            raise ValueError("FusedSGD.step: clip_value and clip_norm exclude each other")
         groups = [(g, [p for p in g['params'] if p.grad is not None]) for g in self.param_groups]
-        if closure is not None or not all(self._fusable(g, ps) for g, ps in groups if ps):
+        every = [p for _, ps in groups for p in ps]
+        scaled = bool(clip_norm and clip_norm > 0 and every)
+        if clip_norm and clip_norm > 0 and not every:
+            self.grad_norm = torch.zeros(())                     # (clip_grad_norm_ of no gradient)
+        if closure is not None or not all(self._fusable(g, ps) for g, ps in groups if ps) or (scaled and len({p.device for p in every}) > 1):
             if clip_value and clip_value > 0:
-                torch.nn.utils.clip_grad_value_([p for _, ps in groups for p in ps], clip_value)
+                torch.nn.utils.clip_grad_value_(every, clip_value)
+            if scaled:
+                self.grad_norm = torch.nn.utils.clip_grad_norm_(every, clip_norm)
             return super().step(closure)
         lib = _lib.lib()
+        coef = None
+        if scaled:
+            norm = self._grad_norm(lib, every, clip_norm)
+            self.grad_norm, coef = norm[0], _lib._vp(norm.data_ptr() + 4)
         for group, params in groups:
             momentum = float(group['momentum'])
             # parameters without a momentum buffer yet take torch's first step (buf = g): normally all of them or none
@@ -59,6 +95,12 @@ class FusedSGD(torch.optim.SGD):
                         bufs = arr(*[self.state[p]['momentum_buffer'].data_ptr() for p in sel])
                     else:
                         bufs = None
+                    if coef is not None:
+                        _lib.check(lib.ws_sgd_step_scaled(arr(*[p.data_ptr() for p in sel]), arr(*[p.grad.data_ptr() for p in sel]),
+                                                          bufs, (ctypes.c_int64 * n)(*[p.numel() for p in sel]), n,
+                                                          float(group['lr']), momentum, float(group['weight_decay']), coef,
+                                                          int(first), _lib.current_stream()))
+                        continue
                     _lib.check(lib.ws_sgd_step(arr(*[p.data_ptr() for p in sel]), arr(*[p.grad.data_ptr() for p in sel]), bufs,
                                                (ctypes.c_int64 * n)(*[p.numel() for p in sel]), n, float(group['lr']), momentum,
                                                float(group['weight_decay']), float(clip_value or 0.0), int(first),
@@ -134,6 +176,11 @@ def train_step_weak(net, optimizer, batch, config, grad_sync=None):
     loss.backward()
     if grad_sync is not None:
         grad_sync(net)
+    if config.grad_clip_norm > 0 and _blocks.WL_ENDS and isinstance(optimizer, FusedSGD) and optimizer.fusable():
+        # norm, coefficient, scaling and the update as kernels of optim.hip: the norm stays a device scalar
+        optimizer.step(clip_norm=config.grad_clip_norm)
+        net.grad_norm = optimizer.grad_norm
+        return loss, (logits, class_logits, cam)
     if config.grad_clip_norm > 0:
         params = getattr(net, "_param_list", None)
         if params is None:

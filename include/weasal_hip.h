@@ -1094,6 +1094,30 @@ int ws_sgd_step_scaled(float* const* h_params, float* const* h_grads, float* con
                        float lr, float momentum, float weight_decay, const float* coef, int32_t first, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The log line of a training step, kept on the device: utils/trainer_PseudoLabel.py:209,244-253 and
+ * utils/trainer_WeakLabel.py:208,243-252 (net.output_loss, net.reg_loss or the gradient norm, KPFCNN.accuracy of
+ * models/architectures.py:386-399, :786-799), weasal_amd/csrc/stats.hip.
+ * ws_step_stats: writes record `row` of `ring` [cap] (device memory): the three floats are bit copies of the device scalars
+ *   out_loss[0], reg_loss[0], extra[0] (each may be NULL: 0), correct = #{i < n : argmax_c logits[i, :] == target_i} with
+ *   torch.argmax's rules (the first maximum on ties, a row with NaN predicts its first NaN) and the label mapping of
+ *   ws_softmax_ce_fwd (lut [lut_n], last entry the spare -1; lut NULL = labels are positions, < 0 ignored).  Ignored rows
+ *   never count: the caller divides by all n rows as KPFCNN.accuracy does.  logits float32 [n, c], row pitch ldl >= c,
+ *   c <= WS_STEP_STATS_MAX_C (what ws_softmax_ce_fwd accepts), n < 2^31.  The record is zeroed by the call; the count is one
+ *   ballot + popcount per wave and one int32 atomic per workgroup of a grid-stride launch of at most WS_STEP_STATS_BLOCKS
+ *   workgroups of 256 rows: no float atomic, run-to-run identical.  n = 0 writes correct = 0 and launches nothing else.
+ *   Nothing is read back; the other records of the ring are not touched.
+ * ------------------------------------------------------------------------------------------ */
+#define WS_STEP_STATS_MAX_C 64
+#define WS_STEP_STATS_BLOCKS 256
+typedef struct ws_step_record {
+    float out_loss, reg_loss, extra;
+    int32_t correct;
+} ws_step_record;
+int ws_step_stats(const float* logits, int64_t n, int32_t c, int64_t ldl, const int64_t* labels, const int64_t* lut,
+                  int32_t lut_n, const float* out_loss, const float* reg_loss, const float* extra, ws_step_record* ring,
+                  int64_t cap, int64_t row, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Deformable KPConv, the fast path of BASELINE config 5 (models/blocks.py:244-325, 366-367 with KP_influence = 'linear',
  * aggregation_mode = 'sum'; neighbour rows of several hundred columns: datasets/common.py:500-502).
  *

@@ -4,10 +4,84 @@ The hot-path code reads ``config.<name>`` exactly like the reference's blocks / 
 (models/blocks.py:523-544, datasets/common.py:468,501,518), so a reference ``Config`` subclass
 (e.g. train_DALES_PseudoLabel.py:44-201) can be passed in unchanged; this class exists so that
 the package is usable without the reference tree.  Defaults follow utils/config.py:35-189; the
-derived fields follow Config.__init__ (:191-233).  parameters.txt save/load (:235-445) is file
-I/O outside the hot path and is not provided.
+derived fields follow Config.__init__ (:191-233).  `save()` / `load(path)` write and read the reference's
+parameters.txt (:235-445): the same keys, order, sections and number formats, so a file of either side loads in the
+other and load followed by save reproduces it.
 """
+import os
+
 import numpy as np
+
+# parameters.txt as a table: sections of (attribute, kind, blank lines after).  Kinds: s string, d integer, b boolean
+# written 0 / 1, f float with six decimals, f3 with three, bs / fs / ss lists, D integer or None, N integer or list of
+# integers (num_classes), L the {epoch: factor} dictionary.  num_layers is derived: written, not read.
+_SECTIONS = (
+    ('Input parameters', '****************', (
+        ('dataset', 's', 0), ('dataset_task', 's', 0), ('num_classes', 'N', 0), ('in_points_dim', 'd', 0),
+        ('in_features_dim', 'd', 0), ('in_radius', 'f', 0), ('input_threads', 'd', 1))),
+    ('Model parameters', '****************', (
+        ('architecture', 'ss', 0), ('equivar_mode', 's', 0), ('invar_mode', 's', 0), ('num_layers', 'd', 0),
+        ('first_features_dim', 'd', 0), ('use_batch_norm', 'b', 0), ('batch_norm_momentum', 'f', 1),
+        ('segmentation_ratio', 'f', 1))),
+    ('KPConv parameters', '*****************', (
+        ('first_subsampling_dl', 'f', 0), ('num_kernel_points', 'd', 0), ('conv_radius', 'f', 0), ('deform_radius', 'f', 0),
+        ('fixed_kernel_points', 's', 0), ('KP_extent', 'f', 0), ('KP_influence', 's', 0), ('aggregation_mode', 's', 0),
+        ('modulated', 'b', 0), ('n_frames', 'd', 0), ('max_in_points', 'd', 1), ('max_val_points', 'd', 1),
+        ('val_radius', 'f', 1))),
+    ('Training parameters', '*******************', (
+        ('learning_rate', 'f', 0), ('momentum', 'f', 0), ('lr_decays', 'L', 0), ('grad_clip_norm', 'f', 1),
+        ('augment_symmetries', 'bs', 0), ('augment_rotation', 's', 0), ('augment_noise', 'f', 0),
+        ('augment_occlusion', 's', 0), ('augment_occlusion_ratio', 'f', 0), ('augment_occlusion_num', 'd', 0),
+        ('augment_scale_anisotropic', 'b', 0), ('augment_scale_min', 'f', 0), ('augment_scale_max', 'f', 0),
+        ('augment_color', 'f', 1),
+        ('weight_decay', 'f', 0), ('segloss_balance', 's', 0), ('class_w', 'fs', 0), ('deform_fitting_mode', 's', 0),
+        ('deform_fitting_power', 'f', 0), ('deform_lr_factor', 'f', 0), ('repulse_extent', 'f', 0), ('batch_num', 'd', 0),
+        ('val_batch_num', 'd', 0), ('max_epoch', 'd', 0), ('epoch_steps', 'D', 0), ('validation_size', 'd', 0),
+        ('checkpoint_gap', 'd', 1))),
+)
+# the last section: a line only when the configuration has the attribute (:420-445)
+_OTHER = (('sub_radius', 'f'), ('model_name', 's'), ('loss_type', 's'), ('contrast_start', 'f'), ('contrast_thd', 'f'),
+          ('anchor_method', 's'), ('active_learning_iterations', 'd'), ('subsample_labels', 'b'),
+          ('initial_labels_per_file', 'd'), ('subsample_method', 's'), ('added_labels_per_epoch', 'd'),
+          ('weak_label_log', 's'), ('dropout', 'f3'))
+_FILE_KEY = {'lr_decays': 'lr_decay_epochs', 'contrast_thd': 'contrast_thd[%]'}        # attribute -> its key in the file
+_DERIVED = ('num_layers',)
+_ONE = {'s': '{:s}', 'd': '{:d}', 'f': '{:.6f}', 'f3': '{:.3f}'}
+
+
+def _write_value(kind, v):
+    """the text behind `key =`, leading blank included (a list without members leaves the bare `key =`)"""
+    if kind == 'b':
+        return ' {:d}'.format(int(v))
+    if kind in _ONE:
+        return ' ' + _ONE[kind].format(v)
+    if kind == 'D':
+        return ' None' if v is None else ' {:d}'.format(v)
+    if kind == 'N':
+        return ''.join(' {:d}'.format(n) for n in v) if type(v) is list else ' {:d}'.format(v)
+    if kind == 'L':
+        return ''.join(' {:d}:{:f}'.format(e, d) for e, d in v.items())
+    if kind == 'bs':
+        return ''.join(' {:d}'.format(int(a)) for a in v)
+    return ''.join(' ' + _ONE[kind[0]].format(a) for a in v)             # ss, fs
+
+
+def _read_value(kind, words):
+    """words: what follows `key =`, at least one"""
+    if kind == 'N':
+        return [int(c) for c in words] if len(words) > 1 else int(words[0])
+    if kind == 'L':
+        return {int(b.split(':')[0]): float(b.split(':')[1]) for b in words}
+    if kind == 'bs':
+        return [bool(int(b)) for b in words]
+    if kind in ('ss', 'fs'):
+        return [{'s': str, 'f': float}[kind[0]](w) for w in words]
+    w = words[0]
+    if kind == 'b':
+        return bool(int(w))
+    if kind in ('d', 'D'):
+        return float(w) if len(w.split('.')) == 2 else int(w)           # (the reference's rule: one dot makes a float)
+    return float(w) if kind in ('f', 'f3') else w
 
 
 class Config:
@@ -90,6 +164,60 @@ class Config:
             layer_blocks = []
             if 'global' in block or 'upsample' in block:
                 break
+
+    def save(self):
+        """write `saving_path`/parameters.txt (utils/config.py:311-445)"""
+        out = ['# -----------------------------------#\n', '# Parameters of the training session #\n',
+               '# -----------------------------------#\n\n']
+        for title, rule, entries in _SECTIONS:
+            out.append('# %s\n# %s\n\n' % (title, rule))
+            for attr, kind, blanks in entries:
+                out.append(_FILE_KEY.get(attr, attr) + ' =' + _write_value(kind, getattr(self, attr)) + '\n' * (1 + blanks))
+        out.append('# Other parameters\n# *******************\n\n')
+        absent = getattr(self, '_absent_when_loaded', {})
+        for attr, kind in _OTHER:
+            if hasattr(self, attr) and not (attr in absent and absent[attr] == getattr(self, attr)):
+                out.append(_FILE_KEY.get(attr, attr) + ' =' + _write_value(kind, getattr(self, attr)) + '\n')
+        with open(os.path.join(self.saving_path, 'parameters.txt'), 'w') as f:
+            f.write(''.join(out))
+
+    def load(self, path):
+        """read parameters.txt (utils/config.py:235-309).  path: the log directory, or the file itself.  Every key of the
+        table is read with its own type, whether or not this object had the attribute (the reference drops the optional
+        keys of a class that does not declare them, and `contrast_thd[%]` always); any other key is taken only when the
+        attribute exists, with the reference's typing.  `key = None` gives None; a bare `key =` empties a list or the decay dictionary
+        (the reference keeps the class default there) and leaves a string alone.
+        As there: saving = True, saving_path = the directory, and the derived fields are computed again.  -> self"""
+        filename = os.path.join(path, 'parameters.txt') if os.path.isdir(path) else path
+        kinds = {_FILE_KEY.get(a, a): (a, k) for _, _, entries in _SECTIONS for a, k, _ in entries}
+        kinds.update({_FILE_KEY.get(a, a): (a, k) for a, k in _OTHER})
+        with open(filename, 'r') as f:
+            lines = f.readlines()
+        seen = set()
+        for line in lines:
+            words = line.split()
+            if len(words) < 2 or words[0] == '#' or words[1] != '=':
+                continue
+            seen.add(words[0])
+            if len(words) == 2 and kinds.get(words[0], ('', ''))[1] in ('ss', 'fs', 'bs', 'L'):
+                setattr(self, kinds[words[0]][0], {} if kinds[words[0]][1] == 'L' else [])      # a list without members
+            if len(words) < 3 or words[0] in _DERIVED:
+                continue
+            key, values = words[0], words[2:]
+            if values[0] == 'None':
+                setattr(self, kinds[key][0] if key in kinds else key, None)
+            elif key in kinds:
+                setattr(self, kinds[key][0], _read_value(kinds[key][1], values))
+            elif hasattr(self, key):
+                kind = float if len(values[0].split('.')) == 2 else type(getattr(self, key))
+                setattr(self, key, bool(int(values[0])) if kind is bool else kind(values[0]))
+        # an optional attribute this class declares (`dropout`) but the file does not name: save() leaves its line out for
+        # as long as the value stays what it is now, so that load followed by save reproduces the file
+        self._absent_when_loaded = {a: getattr(self, a) for a, _ in _OTHER if hasattr(self, a) and _FILE_KEY.get(a, a) not in seen}
+        self.saving = True
+        self.saving_path = os.path.dirname(os.path.abspath(filename))
+        Config.__init__(self)
+        return self
 
 
 _PL_ARCH = ['simple', 'resnetb', 'resnetb_strided', 'resnetb', 'resnetb_strided', 'resnetb',

@@ -1262,6 +1262,41 @@ def cross_entropy(logits, labels, lut=None, weight=None):
     return _SoftmaxCE.apply(logits, labels, lut, weight)
 
 
+def _step_scalar(name, v, dev):
+    if v is None:
+        return None
+    if not isinstance(v, torch.Tensor) or v.device != dev or v.dtype != torch.float32 or v.numel() != 1:
+        raise _lib.WeasalHipError("step_stats: %s must be a float32 scalar on %s or None" % (name, dev))
+    return v.detach()
+
+
+def step_stats(ring, row, logits, labels, lut=None, out_loss=None, reg_loss=None, extra=None):
+    """The log line of a training step into record `row` of `ring` (ws_step_stats): ring int32 [cap, 4] on the device, a
+    record being {float out_loss, float reg_loss, float extra, int32 correct}.  The floats are bit copies of the three device
+    scalars (None: 0); correct = #{i : argmax(logits[i]) == lut(labels[i])} by torch.argmax's rules with the label mapping of
+    cross_entropy -- KPFCNN.accuracy's numerator; its denominator, all rows, is known to the host.  Nothing is read back,
+    no autograd, no CPU path."""
+    _need_cuda(ring, logits, labels)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise _lib.WeasalHipError("step_stats takes float32 logits [N, C] (got %s %s)" % (logits.dtype, tuple(logits.shape)))
+    if ring.dtype != torch.int32 or ring.dim() != 2 or ring.shape[1] != 4 or not ring.is_contiguous():
+        raise _lib.WeasalHipError("step_stats takes a contiguous int32 ring [cap, 4] (got %s %s)" % (ring.dtype, tuple(ring.shape)))
+    dev = logits.device
+    x = logits.detach()
+    n, c = x.shape
+    if n and not (x.stride(1) == 1 and x.stride(0) >= c):
+        x = x.contiguous()
+    labels = labels.detach().to(torch.int64).contiguous()
+    if labels.shape != (n,):
+        raise _lib.WeasalHipError("step_stats: %d label rows for %d logits rows" % (labels.numel(), n))
+    lut = None if lut is None else lut.to(device=dev, dtype=torch.int64).contiguous()
+    scalars = [_step_scalar(k, v, dev) for k, v in (("out_loss", out_loss), ("reg_loss", reg_loss), ("extra", extra))]
+    with torch.cuda.device(dev):
+        check(_lib.lib().ws_step_stats(ptr(x), n, c, x.stride(0) if n else c, ptr(labels), ptr(lut), 0 if lut is None else lut.shape[0],
+                                       ptr(scalars[0]), ptr(scalars[1]), ptr(scalars[2]), ptr(ring), ring.shape[0], int(row),
+                                       current_stream()))
+
+
 class _ContrastLoss(torch.autograd.Function):
     """the WHOLE of KPFCNN.contrast_loss (architectures.py:405-504) as one node: ws_contrast_head_fwd (softmax statistics,
     pseudo labels, normalisation, device-side slice draw) -> ws_contrast_rows_fwd -> ws_contrast_tail_fwd; five launches
@@ -1447,7 +1482,9 @@ class SamplerHandle:
 
     def __init__(self):
         import ctypes as C
+        import os
         self.h = C.c_void_p()
+        self.pid = os.getpid()            # the process whose HIP runtime owns the table (close())
         check(_lib.lib().ws_sampler_create(C.byref(self.h)))
         self.keep = []
         self.keep_colors = {}
@@ -1535,6 +1572,12 @@ class SamplerHandle:
                                                  ptr(out_points), current_stream()))
 
     def close(self):
+        import os
+        if self.h and getattr(self, "pid", None) != os.getpid():
+            # a forked child (multiprocessing's fork start method) that collects a handle it inherited: the table's device
+            # memory belongs to the parent's runtime, and ws_sampler_destroy's hipFree calls crash in a child of a process
+            # that has initialised the GPU.  The parent frees it.
+            self.h = None
         if self.h:
             _lib.lib().ws_sampler_destroy(self.h)
             self.h = None

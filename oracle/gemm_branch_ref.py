@@ -3,7 +3,7 @@
 Float64 references and per-element error bounds for the dense products (tests/test_gemm_branches_*.py): the xb
 products with their whole epilogue menu, dW = X^T dY, and the activation backward with column sums.
 
-Reference epilogue (the kernels' order; weasal_amd/csrc/gemm.hip)
+Reference epilogue (the kernels' order; weasal_amd/csrc/gemm_xb.hip)
   1. v = X @ B, + bias[col], + residual: residual[r] or, gathered, residual[rrows[r * rld]] (indices outside [0, rn):
      the shadow row, adds nothing);
   2. LeakyReLU(slope);

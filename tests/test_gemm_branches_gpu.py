@@ -1,4 +1,5 @@
-"""Every launch branch of the dense products (weasal_amd/csrc/gemm.hip, gemm_bf16.hip) held to a float64 reference, per
+"""Every launch branch of the dense products (weasal_amd/csrc/gemm.hip and its family units gemm_xb.hip / gemm_xty.hip /
+gemm_colsum.hip, gemm_bf16.hip) held to a float64 reference, per
 element.
 
 `BRANCHES` names, row by row, the entry, the launch plan it must reach and the shape, operand layout and epilogue menu

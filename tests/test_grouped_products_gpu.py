@@ -1,4 +1,5 @@
-"""GPU: the grouped dense-product launches (ws_priv_gemm_xb_group / ws_priv_gemm_xty_group, weasal_amd/csrc/gemm.hip).
+"""GPU: the grouped dense-product launches (ws_priv_gemm_xb_group / ws_priv_gemm_xty_group, weasal_amd/csrc/gemm.hip;
+grouped kernels and their launchers in gemm_xb.hip / gemm_xty.hip).
 
 A grouped launch puts several mutually independent products of one kernel instantiation behind one grid and their
 reductions behind one more; every member keeps the plan it gets alone.  So for every case here

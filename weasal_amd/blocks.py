@@ -7,7 +7,7 @@ What differs is the implementation: ``KPConv.forward`` never materialises the
 [N,H,3] / [N,H,K,3] / [N,H,K] / [N,H,Ci] tensors of blocks.py:278-363 -- the gather, the
 kernel-point influence and the feature aggregate run fused in one HIP kernel
 (weasal_amd/csrc/kpconv.hip); the remaining dense contraction [N, K*Ci] x [K*Ci, Co] and the unary
-MLPs run on the f32 MFMA (weasal_amd/csrc/gemm.hip) with the bias / residual / LeakyReLU that follow
+MLPs run on the f32 MFMA (weasal_amd/csrc/gemm.hip, kernels in gemm_xb.hip / gemm_xty.hip) with the bias / residual / LeakyReLU that follow
 them in the blocks applied in the GEMM epilogue.
 
 Quirks of the reference that are preserved on purpose:

@@ -15,7 +15,7 @@
 // so that the 16-byte fragment reads are bank-conflict free).  With bf16 MFMA at 16x the f32 rate these products are
 // bound by streaming X once: 2*M*K bytes.
 //
-// dW = X^T dY stays on the exact-f32 MFMA (gemm.hip: gemm_xty2 with 2-byte operand loads; bf16 -> f32 is exact, the
+// dW = X^T dY stays on the exact-f32 MFMA (gemm_xty.hip: gemm_xty2 with 2-byte operand loads; bf16 -> f32 is exact, the
 // products and the running sums are fp32, the result is the fp32 master gradient).
 #include "ws_common.h"
 #include "ws_dispatch.h"
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void gemm_xbt_bf16_kernel(
     }
 
     if (vecout && (n & 3) == 0 && ws_bf16_staged_flag(staged)) {
-        // the wave's 32 x 32 tile turned through LDS (see gemm.hip, xb_rows_epilogue_staged): lane (r = lane / 8, c = lane % 8)
+        // the wave's 32 x 32 tile turned through LDS (see gemm_xb.hip, xb_rows_epilogue_staged): lane (r = lane / 8, c = lane % 8)
         // stores columns 4 c .. 4 c + 3 of rows r + 8 p -- 8 row segments of 64 (bf16) / 128 (f32) contiguous bytes per
         // instruction instead of 8 / 16 bytes to each of 32 rows.  Same arithmetic in the same order.
         float* stage = reinterpret_cast<float*>(Bs_raw) + wave * (32 * STAGE_LD);
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void gemm_xbt_bf16_kernel(
 
 // ---------------------------------------------------------------------------------------------------------------
 // dz = LeakyReLU'(y) * dy (bf16 rows) and the fp32 column sums of dz (the bias gradient), one pass: the bf16 form of
-// gemm.hip's act_bwd_colsum_kernel<4>.  dy may be f32 (the logits' gradient) or bf16.
+// gemm_colsum.hip's act_bwd_colsum_kernel<4>.  dy may be f32 (the logits' gradient) or bf16.
 // ---------------------------------------------------------------------------------------------------------------
 template <typename TG>
 __global__ __launch_bounds__(256) void act_bwd_colsum_bf16_kernel(const TG* __restrict__ dy, const bf16_t* __restrict__ yact,

@@ -490,6 +490,19 @@ def p2p_regularizer(deformed_kp, min_d2, extent, repulse_extent):
 # ------------------------------------------------------------------------------------------------
 
 
+def _rowmajor(t):
+    return t if (t.stride(1) == 1 and t.stride(0) >= t.shape[1]) else t.contiguous()
+
+
+def _act_args(slope):
+    """(act, slope) as the entries take them: LeakyReLU(slope), or no activation"""
+    return (0, 0.0) if slope is None else (1, float(slope))
+
+
+def _scratch(nbytes, device):
+    return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
+
+
 def _gemm_xb(x, b):
     lib = _lib.lib()
     m, k = x.shape
@@ -502,7 +515,7 @@ def _gemm_xb(x, b):
 def _xb_launch(lib, x, m, k, b, n, bias, residual, slope, y):
     """ws_gemm_xb_epilogue, or its split-K form when the product is short and deep (scratch_bytes > 0)"""
     sb = lib.ws_gemm_xb_scratch_bytes(m, k, n)
-    act, sl = (0, 0.0) if slope is None else (1, float(slope))
+    act, sl = _act_args(slope)
     ldr = residual.stride(0) if residual is not None else 0
     if sb > 0:
         scratch = torch.empty(sb, dtype=torch.uint8, device=x.device)
@@ -519,7 +532,7 @@ def _gemm_xty(lib, x, dy):
     m, k = x.shape
     n = dy.shape[1]
     db = torch.empty((k, n), dtype=torch.float32, device=x.device)
-    scratch = torch.empty(max(lib.ws_gemm_xty_scratch_bytes(m, k, n), 16), dtype=torch.uint8, device=x.device)
+    scratch = _scratch(lib.ws_gemm_xty_scratch_bytes(m, k, n), x.device)
     check(lib.ws_gemm_xty(ptr(x), m, k, x.stride(0), ptr(dy), n, dy.stride(0), ptr(db), ptr(scratch), current_stream()))
     return db
 
@@ -529,7 +542,7 @@ class _MatmulXB(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, b):
-        xc = x if (x.stride(1) == 1 and x.stride(0) >= x.shape[1]) else x.contiguous()
+        xc = _rowmajor(x)
         bc = b.contiguous()
         ctx.save_for_backward(xc, bc)
         return _gemm_xb(xc, bc)
@@ -538,7 +551,7 @@ class _MatmulXB(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.lib()
         x, b = ctx.saved_tensors
-        dy = dy if (dy.stride(1) == 1 and dy.stride(0) >= dy.shape[1]) else dy.contiguous()
+        dy = _rowmajor(dy)
         dx = db = None
         if ctx.needs_input_grad[0]:
             dx = _gemm_xb(dy, b.t().contiguous())
@@ -564,7 +577,7 @@ def _xbt16(lib, x, bt, bias, residual, slope, out_f32):
     m, k = x.shape
     n = bt.shape[0]
     y = torch.empty((m, n), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
-    act, sl = (0, 0.0) if slope is None else (1, float(slope))
+    act, sl = _act_args(slope)
     check(lib.ws_gemm_xbt_bf16(ptr(x), m, k, x.stride(0), ptr(bt), n, bt.stride(0), ptr(bias), ptr(residual),
                                residual.stride(0) if residual is not None else 0, act, sl, ptr(y), n, 1 if out_f32 else 0,
                                current_stream()))
@@ -576,7 +589,7 @@ def _xty16(lib, x, dz):
     m, k = x.shape
     n = dz.shape[1]
     db = torch.empty((k, n), dtype=torch.float32, device=x.device)
-    scratch = torch.empty(max(lib.ws_gemm_xty_scratch_bytes(m, k, n), 16), dtype=torch.uint8, device=x.device)
+    scratch = _scratch(lib.ws_gemm_xty_scratch_bytes(m, k, n), x.device)
     check(lib.ws_gemm_xty_bf16(ptr(x), m, k, x.stride(0), ptr(dz), n, dz.stride(0), ptr(db), ptr(scratch), current_stream()))
     return db
 
@@ -593,11 +606,11 @@ class _MatmulEpilogueBF16(torch.autograd.Function):
         lib = _lib.lib()
         m, k = x.shape
         n = b.shape[1]
-        xc = x if (x.stride(1) == 1 and x.stride(0) >= k) else x.contiguous()
+        xc = _rowmajor(x)
         rc = None
         if residual is not None:
             rc = residual if residual.dtype == torch.bfloat16 else residual.to(torch.bfloat16)
-            rc = rc if (rc.stride(1) == 1 and rc.stride(0) >= n) else rc.contiguous()
+            rc = _rowmajor(rc)
         biasc = bias.float().contiguous() if bias is not None else None
         if _bf16_ok(xc, k):
             y = _xbt16(lib, xc, _bt16(b), biasc, rc, slope, out_f32)
@@ -648,7 +661,7 @@ def _act_bwd_colsum16(lib, dy, y, slope, want_colsum):
     colsum = scratch = None
     if want_colsum:
         colsum = torch.empty((n,), dtype=torch.float32, device=dy.device)
-        scratch = torch.empty(max(lib.ws_act_bwd_colsum_bf16_scratch_bytes(m, n), 16), dtype=torch.uint8, device=dy.device)
+        scratch = _scratch(lib.ws_act_bwd_colsum_bf16_scratch_bytes(m, n), dy.device)
     yb = None
     if y is not None:
         yb = y if y.dtype == torch.bfloat16 else y.to(torch.bfloat16)      # only the sign is used
@@ -656,10 +669,6 @@ def _act_bwd_colsum16(lib, dy, y, slope, want_colsum):
                                      0.0 if slope is None else float(slope), ptr(dz), n if dz is not None else 0, ptr(colsum),
                                      ptr(scratch), current_stream()))
     return (dz if need_dz else dy), colsum
-
-
-def _rowmajor(t):
-    return t if (t.stride(1) == 1 and t.stride(0) >= t.shape[1]) else t.contiguous()
 
 
 def _act_bwd_colsum(dy, y, slope, want_colsum):
@@ -673,7 +682,7 @@ def _act_bwd_colsum(dy, y, slope, want_colsum):
     colsum = scratch = None
     if want_colsum:
         colsum = torch.empty((n,), dtype=torch.float32, device=dy.device)
-        scratch = torch.empty(max(lib.ws_act_bwd_colsum_scratch_bytes(m, n), 16), dtype=torch.uint8, device=dy.device)
+        scratch = _scratch(lib.ws_act_bwd_colsum_scratch_bytes(m, n), dy.device)
     check(lib.ws_act_bwd_colsum(ptr(dy), m, n, dy.stride(0), ptr(y), y.stride(0) if y is not None else 0,
                                 0.0 if slope is None else float(slope), ptr(dz) if y is not None else None, n,
                                 ptr(colsum), ptr(scratch), current_stream()))
@@ -1615,10 +1624,6 @@ def _att_lengths(lengths, n):
     import ctypes as C
     ls = [int(v) for v in lengths]
     return (C.c_int64 * max(len(ls), 1))(*ls), len(ls)
-
-
-def _scratch(nbytes, device):
-    return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
 
 
 class _SphereAttention(torch.autograd.Function):

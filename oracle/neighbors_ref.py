@@ -83,7 +83,7 @@ def nearest(keys, counts, ns):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# the launcher's rules (neighbors.hip: nb_fill_slab, ws_radius_neighbors_search, ws_radius_neighbors_async_cap)
+# the launcher's rules (neighbors.hip: nb_fill_plan, ws_radius_neighbors_search, ws_radius_neighbors_async_cap)
 # ------------------------------------------------------------------------------------------------------------------
 def fill_slab(cap):
     for s in SLABS:

@@ -452,6 +452,37 @@ def test_async_entry_rows(gpu, name, r, width, wide, t):
 
 
 @pytest.mark.parametrize("t", list(DT))
+def test_key_last_of_truncated_rows_on_the_2048_slab(gpu, t):
+    """nb_fill_kernel<2048> is reached through the synchronous entries only (the asynchronous slabs end at 1024): a one-pass
+    search at width 128 over rows of up to 1025 neighbours re-runs into the 2048 slab, and the key_last it leaves is the
+    (distance, index) key of column 127 of every truncated row, all ones elsewhere"""
+    name, r, width = "clump1025", RADIUS, 128
+    keys, counts = reference(name, r)
+    d = dataset(name)
+    ns = len(d["s"])
+    assert int(counts.max()) == 1025 and (counts > width).any() and (counts <= width).any()
+    lib = _lib.lib()
+    qd, sd = _dev(gpu, name)
+    ws = ops._ws.neighbors(gpu)
+    out = torch.empty((qd.shape[0], width), dtype=DT[t], device=gpu)
+    kl = torch.empty((qd.shape[0],), dtype=torch.int64, device=gpu)
+    o32, o64 = (ptr(out), None) if t == "i32" else (None, ptr(out))
+    mc = C.c_int32(0)
+    with torch.cuda.device(gpu):
+        check(lib.ws_radius_neighbors_set_key_last(ws, ptr(kl)))
+        check(lib.ws_radius_neighbors_search(ws, ptr(qd), qd.shape[0], ptr(sd), sd.shape[0], C.c_void_p(d["ql"].ctypes.data),
+                                             C.c_void_p(d["sl"].ctypes.data), len(d["ql"]), float(np.float32(r)), width, o32, o64,
+                                             C.byref(mc), current_stream()))
+    torch.cuda.synchronize()
+    names = ran(gpu, t == "i32")
+    print(name, r, width, t, names)
+    assert names == R.fill_plan("search", width, 1025, 1, t == "i32") and "nb_fill_kernel<2048," in names[-1]
+    assert mc.value == 1025
+    assert np.array_equal(_np(out), R.rows(keys, counts, width, ns))
+    assert np.array_equal(_np(kl).view(np.uint64), R.key_last(keys, counts, width))
+
+
+@pytest.mark.parametrize("t", list(DT))
 @pytest.mark.parametrize("name,r", NEAREST, ids=["%s-r%g" % c for c in NEAREST])
 def test_nearest(gpu, name, r, t):
     keys, counts = reference(name, r)

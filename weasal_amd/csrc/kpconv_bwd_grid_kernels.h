@@ -71,13 +71,12 @@ __global__ __launch_bounds__(256) void kpconv_gather_bwd_x_grid_kernel(
         auto take = [&](const float4& c, bool active) {
             // K1 evaluated this pair with c as the query and s as the support: diff = query - support
             const float d2 = ref_d2(c.x, c.y, c.z, make_float4(sx, sy, sz, 0.0f));
-            const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)s;
+            const unsigned long long key = nb_key(d2, (unsigned)s);
             bool hit = active && d2 < r2;
             hit = hit && key <= key_last[hit ? __float_as_int(c.w) : 0];          // unconditional gather
-            const unsigned long long m = __ballot(hit);
-            const int pos = cnt + lane_rank(m);
-            slab[(hit && pos < GRID_SLAB) ? pos : GRID_SLAB + lane] = c;      // branch free (dummy slot per lane)
-            cnt += __builtin_popcountll(m);
+            const int2 put = slab_compact(hit, GRID_SLAB, lane, cnt);
+            slab[put.x] = c;
+            cnt = put.y;
         };
         // a support with an untruncated row of its own: every point within the radius is in that row (the distance is
         // symmetric bit for bit), so the queries that kept s are among its entries -- ~60 candidates instead of the ~700 of
@@ -92,33 +91,21 @@ __global__ __launch_bounds__(256) void kpconv_gather_bwd_x_grid_kernel(
                 take(make_float4(s_pts[3 * qq + 0], s_pts[3 * qq + 1], s_pts[3 * qq + 2], __int_as_float((int)qq)), active);
             }
         } else if (gr.s_len > 0) {
-            const int cx = cell_coord(sx, gr.lo[0], gr.inv_cell);
-            const int cy = cell_coord(sy, gr.lo[1], gr.inv_cell);
-            const int cz = cell_coord(sz, gr.lo[2], gr.inv_cell);
-            const int x0 = max(cx - 1, 0), x1 = min(cx + 1, gr.nx - 1);
-            int rb[9], re[9];
-#pragma unroll
-            for (int r = 0; r < 9; ++r) {
-                const int z = cz + r / 3 - 1, y = cy + r % 3 - 1;
-                const bool ok = x0 <= x1 && z >= 0 && z < gr.nz && y >= 0 && y < gr.ny;
-                const int row = gr.cell_base + ((ok ? z : 0) * gr.ny + (ok ? y : 0)) * gr.nx;
-                rb[r] = ok ? cell_start[row + x0] : 0;
-                re[r] = ok ? cell_start[row + x1 + 1] : 0;
-            }
+            const CellRuns u = grid_cell_runs(gr, sx, sy, sz, cell_start);      // grid_walk (ws_grid.h) spelt out: see there
             float4 c[9];
 #pragma unroll
             for (int r = 0; r < 9; ++r) {
-                const int p = rb[r] + lane;
-                c[r] = sorted[p < re[r] ? p : 0];          // unconditional, masked by `active`
+                const int p = u.rb[r] + lane;
+                c[r] = sorted[p < u.re[r] ? p : 0];          // unconditional, masked by `active`
             }
 #pragma unroll
             for (int r = 0; r < 9; ++r) {
-                take(c[r], rb[r] + lane < re[r]);
-                for (int p0 = rb[r] + 64; p0 < re[r]; p0 += 64) {
+                take(c[r], u.rb[r] + lane < u.re[r]);
+                for (int p0 = u.rb[r] + 64; p0 < u.re[r]; p0 += 64) {
                     const int p = p0 + lane;
                     float4 cc = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (p < re[r]) cc = sorted[p];
-                    take(cc, p < re[r]);
+                    if (p < u.re[r]) cc = sorted[p];
+                    take(cc, p < u.re[r]);
                 }
             }
         }

@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void kpconv_gather_bwd_x_gridw_kernel(
             // membership of candidate c (the query) for this support: inside the radius and not cut off q's row
             auto member = [&](const float4& c, bool active, unsigned long long kl) -> bool {
                 const float d2 = ref_d2(c.x, c.y, c.z, make_float4(sx, sy, sz, 0.0f));
-                const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)s;
+                const unsigned long long key = nb_key(d2, (unsigned)s);
                 return active && d2 < r2 && d2 <= cut2 && key <= kl;
             };
             // ONE loop hands 64-pair batches to ONE inlined copy of the list / flush phases (a lambda that is called from
@@ -176,15 +176,12 @@ __global__ __launch_bounds__(256) void kpconv_gather_bwd_x_gridw_kernel(
             }
             int run = 0, rp = 0, re = 0;                       // walk state: next run, position / end inside the current run
             if (!from_row && gr.s_len > 0) {
-                const int cx = cell_coord(sx, gr.lo[0], gr.inv_cell);
-                const int cy = cell_coord(sy, gr.lo[1], gr.inv_cell);
-                const int cz = cell_coord(sz, gr.lo[2], gr.inv_cell);
-                const int x0 = max(cx - 1, 0), x1 = min(cx + 1, gr.nx - 1);
-                if (lane < 9) {
-                    const int z = cz + lane / 3 - 1, y = cy + lane % 3 - 1;
-                    const bool ok = x0 <= x1 && z >= 0 && z < gr.nz && y >= 0 && y < gr.ny;
+                const CellBlock k = grid_cell_block(gr, sx, sy, sz);
+                if (lane < 9) {     // grid_cell_run (ws_grid.h) for run `lane`, spelt out: through it the deformable instantiations change
+                    const int z = k.cz + lane / 3 - 1, y = k.cy + lane % 3 - 1;
+                    const bool ok = k.x0 <= k.x1 && z >= 0 && z < gr.nz && y >= 0 && y < gr.ny;
                     const int row = gr.cell_base + ((ok ? z : 0) * gr.ny + (ok ? y : 0)) * gr.nx;
-                    runs[lane] = make_int2(ok ? cell_start[row + x0] : 0, ok ? cell_start[row + x1 + 1] : 0);
+                    runs[lane] = make_int2(ok ? cell_start[row + k.x0] : 0, ok ? cell_start[row + k.x1 + 1] : 0);
                 }
                 wave_lds_order();
             } else {

@@ -92,15 +92,7 @@ __device__ __forceinline__ void kp_influence(float nx, float ny, float nz, const
     }
 }
 
-__device__ __forceinline__ void wave_lds_sync()
-{
-    // the slab is private to one wave: order the wave's own LDS writes before its reads
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// LDS-only ordering inside one wave: the wavefront-scope release/acquire fences above make the compiler drain EVERY
+// LDS-only ordering inside one wave: the wavefront-scope release/acquire fences of wave_lds_sync (ws_grid.h) make the compiler drain EVERY
 // outstanding vector-memory load (s_waitcnt vmcnt(0)), i.e. they expose the full latency of loads that were issued on
 // purpose ahead of their use.  A wave's own LDS writes and reads are ordered by the LDS queue; what is needed is that the
 // compiler keeps them in program order and that the wave's earlier LDS operations have completed.
@@ -139,11 +131,6 @@ __device__ __forceinline__ void wave_lds_order()
 // ---------------------------------------------------------------------------------------------
 constexpr int POOL = 256;                 // real entries per wave (8 B each), >= 16 * 15
 constexpr int POOL_ALLOC = POOL + 8 + 128; // + read-past slack of the flush + two dummy slots per lane
-
-__device__ __forceinline__ int lane_rank(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
 
 // influence of ONE kernel point (same formulas as kp_influence)
 __device__ __forceinline__ float kp_weight(float d2, const GeomParams& g, float inv_extent)

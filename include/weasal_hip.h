@@ -766,6 +766,34 @@ int ws_validation_update(const float* logits, int64_t n, int32_t c, int64_t ld, 
                          const int32_t* pred_row, int32_t nc, int64_t* confusion, int64_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The end of a test run (csrc/testrun.hip; weasal_amd/testrun.py): utils/tester_PseudoLabel.py:270-348, the same lines
+ * of utils/tester_WeakLabel.py, and the sub-cloud form of :225-244.
+ * ws_test_outputs: ONE launch per cloud, no [m, c] intermediate.  votes [n_sub, c] float32 (a VoteAccumulator buffer),
+ *   proj int32 [m]: the sub-cloud row of every full-resolution point (:277); NULL = identity (the sub-cloud itself, m
+ *   rows of votes).  col_of int32 [c], ascending, and label_values int32 [c_all], both on the device: the expanded row
+ *   [c_all] of point i holds votes[proj[i], k] at position col_of[k] and zeros at the ignored positions (np.insert,
+ *   :297-300); it is stored to proj_probs [m, c_all] float32 when that pointer is given.  k* = the first maximum of the
+ *   expanded row (np.argmax: strict >), preds[i] = label_values[k*] (:303) -- a row nobody voted on is all zeros and gets
+ *   label_values[0], ignored or not, as the reference does.  targets int32 [m] (label VALUES) and error int8 [m]:
+ *   error[i] = preds[i] != targets[i] (:345-348).  confusion int64 [c_all, c_all], ACCUMULATED:
+ *   confusion[true_row[targets[i]] * c_all + k*] += 1, true_row int32 [n_true] on the device = fast_confusion's label_map
+ *   indexed by the label value (utils/metrics.py:35-110; testrun.value_rows); it needs targets and true_row.
+ *   proj_probs, preds, targets, error and confusion are optional (NULL), each on its own.
+ *   status: WS_TEST_STATUS_WORDS int64 on the device, accumulated, never a fault: [WS_TEST_BAD_PROJ] += 1 per proj[i]
+ *   outside [0, n_sub) (the row takes no part: zeros, preds[i] = label_values[0], left out of the confusion);
+ *   [WS_TEST_BAD_TARGET] += 1, when a confusion is asked for, per target outside [0, n_true) or whose table entry is
+ *   outside [0, c_all) (left out of the confusion).  A col_of entry outside [0, c_all) drops its column.
+ *   c_all <= 64 and c <= c_all, else WS_ERR_UNSUPPORTED; other bad sizes or a NULL required pointer (votes, col_of,
+ *   label_values, status; targets for error; targets and true_row for confusion): WS_ERR_INVALID; m == 0: WS_OK and
+ *   nothing is queued; all found before the device is touched.  The launch is queued on `stream`; nothing synchronises,
+ *   no float is added, every run gives the same bits.
+ * ------------------------------------------------------------------------------------------ */
+enum { WS_TEST_BAD_PROJ = 0, WS_TEST_BAD_TARGET = 1, WS_TEST_STATUS_WORDS = 2 };
+int ws_test_outputs(const float* votes, int64_t n_sub, int32_t c, const int32_t* proj, int64_t m, const int32_t* col_of,
+                    const int32_t* label_values, int32_t c_all, const int32_t* targets, const int32_t* true_row, int32_t n_true,
+                    float* proj_probs, int32_t* preds, int8_t* error, int64_t* confusion, int64_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Active-learning selection on the votes of a pass over the training clouds (csrc/active.hip).
  * ws_al_point_scores: utils/tester_PseudoLabel.py:400-414 -- per row of probs [n,c] (float32 votes, c <= 32, else
  *   WS_ERR_UNSUPPORTED): entropy = -sum_k p_k * log2f(p_k + 1e-12f), float32, summed in column order; preds = the first

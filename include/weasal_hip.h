@@ -575,6 +575,8 @@ int ws_act_bwd_colsum_bf16(const void* dy, int32_t dy_f32, int64_t m, int32_t n,
  * Biases may be NULL (BatchNormBlock with use_bn is an identity, blocks.py:453-463).
  * Requirements (WS_ERR_UNSUPPORTED otherwise; the caller then runs the operators one by one): in_dim, conv_out,
  * out_dim multiples of 4 and conv_in a multiple of 4 (or the 3..4-channel input layer without unary1), k = 15.
+ * Empty sides: nq = 0 (with or without supports) is an empty call whose backward clears every gradient; queries without
+ * a single support (ns = 0, nq > 0) are WS_ERR_UNSUPPORTED in both entries and both size queries.
  * All buffers are caller-owned; `scratch` must hold ws_kpblock_*_scratch_bytes(desc) bytes.
  * ------------------------------------------------------------------------------------------ */
 typedef struct ws_kpblock {
@@ -631,7 +633,8 @@ int ws_kpblock_bwd(const ws_kpblock* d, void* scratch, int64_t scratch_bytes, vo
  *   out = lrelu(skip @ wsk^T + b + yc[ups[:,0]])          (closest_pool = nearest upsampling, blocks.py:80-92)
  * identical in exact arithmetic to upsample -> concat -> unary (a row gather commutes with a per-row linear map).
  * Backward: dw [out, c_up + c_skip] (same layout as w), db, dxc [nc,c_up], dskip [nf,c_skip]; t_offsets / t_pairs =
- * transposed table of column 0 of `ups`. */
+ * transposed table of column 0 of `ups`.  nf = 0 is an empty call (the backward clears every gradient); fine rows without
+ * a single coarse row (nc = 0, nf > 0) are WS_ERR_UNSUPPORTED in both entries and both size queries. */
 typedef struct ws_upunary {
     const float* xc; int64_t nc; int32_t c_up;
     const float* skip; int64_t nf; int32_t c_skip;

@@ -252,3 +252,39 @@ def test_empty_blocks(gpu):
             sw.value = default
     for k in res[0]:
         assert bool((res[0][k] == 0).all()) and torch.equal(res[0][k], res[default][k]), k
+
+
+def test_rows_on_one_side_only_are_refused(gpu):
+    """supports without queries / coarse rows without fine rows are the empty calls above; the other way round the forward
+    is act(bias) rows (kpblock: ns = 0, nq > 0) or act(skip @ Ws^T + b) (upunary: nc = 0, nf > 0) with live bias, weight and
+    skip gradients, which a zero-gradient exit would contradict.  No caller sends either: both entries and both scratch
+    queries say WS_ERR_UNSUPPORTED and name the sizes"""
+    from weasal_amd import fused
+    lib = fused._bind()
+    dummy = torch.zeros(4096, device=gpu)
+    scr = torch.empty(1 << 20, dtype=torch.uint8, device=gpu)
+    d = fused.KPBlockDesc()
+    for f in ("q_pts", "s_pts", "inds", "kernel_points", "feat", "wk", "wf", "out", "w1", "w2", "ws", "x1", "x2", "dout", "pooled", "arg",
+              "dw1", "dwk", "dw2", "dws", "t_offsets", "t_pairs"):
+        setattr(d, f, dummy.data_ptr())
+    d.nq, d.ns, d.strided = 5, 0, 1
+    d.h, d.k, d.extent, d.slope = 3, 15, 1.0, 0.1
+    d.in_dim, d.conv_in, d.conv_out, d.out_dim = 64, 32, 32, 128
+    for query in (lib.ws_kpblock_fwd_scratch_bytes, lib.ws_kpblock_bwd_scratch_bytes):
+        assert query(C.byref(d)) == -1 and b"nq=5 ns=0" in lib.ws_last_error()
+    for call in (lib.ws_kpblock_fwd, lib.ws_kpblock_bwd):
+        assert call(C.byref(d), scr.data_ptr(), scr.numel(), None) == 2 and b"nq=5 ns=0" in lib.ws_last_error()
+    d.nq, d.ns = 0, 5                                # supports without queries stay an empty call: zero gradients
+    assert lib.ws_kpblock_bwd_scratch_bytes(C.byref(d)) >= 256
+    u = fused.UpUnaryDesc()
+    for f in ("xc", "skip", "ups", "w", "out", "yc", "dout", "dxc", "dskip", "t_offsets", "t_pairs", "dw"):
+        setattr(u, f, dummy.data_ptr())
+    u.nc, u.nf = 0, 7
+    u.c_up, u.c_skip, u.out_dim, u.ldw, u.h_up, u.relu, u.slope = 64, 32, 32, 96, 1, 1, 0.1
+    for query in (lib.ws_upunary_fwd_scratch_bytes, lib.ws_upunary_bwd_scratch_bytes):
+        assert query(C.byref(u)) == -1 and b"nc=0 nf=7" in lib.ws_last_error()
+    for call in (lib.ws_upunary_fwd, lib.ws_upunary_bwd):
+        assert call(C.byref(u), scr.data_ptr(), scr.numel(), None) == 2 and b"nc=0 nf=7" in lib.ws_last_error()
+    u.nc, u.nf = 7, 0
+    assert lib.ws_upunary_bwd_scratch_bytes(C.byref(u)) >= 256
+    torch.cuda.synchronize()

@@ -157,6 +157,9 @@ int check_kpblock(const ws_kpblock* d)
     WS_REQUIRE(!d->w2 || d->ws || d->in_dim == d->out_dim, "shortcut needs a projection (ws) when in_dim != out_dim");
     WS_REQUIRE(!d->strided || !d->w2 || (d->pooled && d->arg), "strided block: pooled / arg buffers missing");
     WS_REQUIRE(d->strided || d->nq == d->ns, "non-strided block: nq must equal ns");
+    // queries without a single support: the forward would be act(bias) rows whose bias gradients are live -- no caller sends it
+    if (d->ns == 0 && d->nq > 0)
+        return ws_fail(WS_ERR_UNSUPPORTED, "block with queries but no supports (nq=%lld ns=%lld)", (long long)d->nq, (long long)d->ns);
     if (d->conv_out % 4 || d->out_dim % 4 || (d->w1 && d->conv_in % 4) || (d->w2 && d->in_dim % 4))
         return ws_fail(WS_ERR_UNSUPPORTED, "block widths must be multiples of 4 (in=%d conv=%d->%d out=%d)", d->in_dim, d->conv_in,
                        d->conv_out, d->out_dim);
@@ -294,8 +297,8 @@ int kpblock_bwd(const ws_kpblock* d, Arena& ar, hipStream_t st, bool run)
     WS_REQUIRE(!d->w1 || d->dw1, "dw1 missing");
     WS_REQUIRE(!d->w2 || d->dw2, "dw2 missing");
     WS_REQUIRE(!d->ws || !d->w2 || d->dws, "dws missing");
-    if (nq == 0 || ns == 0) {
-        // no rows: every gradient is zero
+    if (nq == 0) {
+        // no output rows (ns == 0 with nq > 0 is refused by check_kpblock): every gradient is zero
         WS_HIP(hipMemsetAsync(d->dwk, 0, sizeof(float) * (size_t)kc * d->conv_out, st));
         if (d->dbk) WS_HIP(hipMemsetAsync(d->dbk, 0, sizeof(float) * d->conv_out, st));
         if (d->w1) { WS_HIP(hipMemsetAsync(d->dw1, 0, sizeof(float) * (size_t)d->conv_in * d->in_dim, st)); if (d->db1) WS_HIP(hipMemsetAsync(d->db1, 0, sizeof(float) * d->conv_in, st)); }
@@ -440,6 +443,9 @@ int check_upunary(const ws_upunary* d)
     WS_REQUIRE(d->drop_p >= 0.0f && d->drop_p < 1.0f, "bad drop probability %g", (double)d->drop_p);
     if (d->drop_p > 0.0f && !d->relu) return ws_fail(WS_ERR_UNSUPPORTED, "decoder step: the fused dropout follows a LeakyReLU (relu = 0)");
     WS_REQUIRE(!(d->dout_pregated && !d->relu), "dout_pregated needs this step's LeakyReLU");
+    // fine rows without a single coarse row: out = act(skip @ Ws^T + b), whose gradients are live -- no caller sends it
+    if (d->nc == 0 && d->nf > 0)
+        return ws_fail(WS_ERR_UNSUPPORTED, "decoder step with fine rows but no coarse rows (nc=%lld nf=%lld)", (long long)d->nc, (long long)d->nf);
     return WS_OK;
 }
 
@@ -450,10 +456,10 @@ int upunary_fwd(const ws_upunary* d, Arena& ar, hipStream_t st, bool run)
     void* tmp = ar.take<char>(tmp_bytes);
     if (!run || d->nf == 0) return WS_OK;
     WS_REQUIRE(d->yc, "yc buffer missing");
-    if (d->nc > 0)
-        WS_TRY(ws_gemm_xb_epilogue_strided(d->xc, d->nc, d->c_up, d->c_up, d->w, 1, d->ldw, d->out_dim, nullptr, nullptr, 0, 0, 0.0f, d->yc,
-                                           d->out_dim, tmp, tmp_bytes, st));
-    if (ws_block_gather_residual && d->nc > 0)
+    // (nf > 0 here, so nc > 0: check_upunary refuses fine rows without coarse rows)
+    WS_TRY(ws_gemm_xb_epilogue_strided(d->xc, d->nc, d->c_up, d->c_up, d->w, 1, d->ldw, d->out_dim, nullptr, nullptr, 0, 0, 0.0f, d->yc,
+                                       d->out_dim, tmp, tmp_bytes, st));
+    if (ws_block_gather_residual)
         // nearest upsampling (closest_pool) read by the epilogue: out row r adds yc[ups[r, 0]] (nothing for the shadow index);
         // the droplayer in front of the head (drop_p > 0) rides on the same epilogue
         return ws_priv_gemm_xb_ex(d->skip, d->nf, d->c_skip, d->c_skip, d->w + d->c_up, 1, d->ldw, d->out_dim, d->b, d->yc, d->out_dim,
@@ -483,11 +489,11 @@ int upunary_bwd(const ws_upunary* d, Arena& ar, hipStream_t st, bool run)
     if (!run) return WS_OK;
     WS_REQUIRE(d->dout && d->dw && d->dxc && d->dskip && d->t_offsets && d->t_pairs, "NULL gradient buffer / table");
     const int64_t cw = d->c_up + d->c_skip;
-    if (d->nf == 0 || d->nc == 0) {
+    if (d->nf == 0) {
+        // no output rows (nc == 0 with nf > 0 is refused by check_upunary): every gradient is zero
         WS_HIP(hipMemsetAsync(d->dw, 0, sizeof(float) * (size_t)d->out_dim * cw, st));
         if (d->db) WS_HIP(hipMemsetAsync(d->db, 0, sizeof(float) * d->out_dim, st));
         if (d->nc > 0) WS_HIP(hipMemsetAsync(d->dxc, 0, sizeof(float) * (size_t)d->nc * d->c_up, st));
-        if (d->nf > 0) WS_HIP(hipMemsetAsync(d->dskip, 0, sizeof(float) * (size_t)d->nf * d->c_skip, st));
         return WS_OK;
     }
     // dz = dout * lrelu'(out) (identity when !relu), db

@@ -276,6 +276,30 @@ const int32_t* ws_radius_neighbors_counts(const ws_neighbors_ws* ws);
 int ws_radius_neighbors_fill_variant(int32_t cap, int32_t out_i32, int32_t beside, char* out, int32_t out_cap);
 int ws_radius_neighbors_last_fills(const ws_neighbors_ws* ws, int32_t* caps, int32_t max, int32_t* n);
 
+/* Exact nearest neighbour, no radius -- replaces sklearn's KDTree.query(points, k=1) where the reference asks for the nearest
+ * sub-cloud point of every original point (datasets/DALES_PseudoLabel.py:888-893 and its sibling dataset files; the round
+ * trip of pseudoLabel_refinement.py:112-125).  For query q of batch element b: the support j of the same element that
+ * minimises the key (d2, j),
+ *   d2 = fl(fl(fl(dx*dx)+fl(dy*dy))+fl(dz*dz)) in FLOAT64,  dx = (double)q.x - (double)s.x     (no FMA contraction)
+ * -- the arithmetic of the tree, so the index equals KDTree.query wherever the two nearest float64 distances differ; exact
+ * float64 ties go to the smallest global index.  out [nq] = the global support index, or ns when the element has no
+ * supports; out_d2 (optional, DEVICE float64 [nq]) = the winning d2, +inf beside ns.  Any query is answered, however far
+ * from the supports; a query with a non-finite coordinate gets ns / +inf and sets WS_NN_STATUS_NONFINITE_QUERY in *d_status
+ * (optional DEVICE int32, OR-ed into: the caller zeroes it); a non-finite support is never chosen.  The result is a pure
+ * function of the inputs: no atomics on the result path, bit-identical from run to run, independent of `cell`.
+ * cell: the cell size of the workspace's counting-sort grid the search walks (the grid's own caps may enlarge it);
+ * 0 = chosen by the library per element from its bounding box and support count.  Only the speed depends on it.
+ * Exactly one of out_i32 / out_i64 is non-NULL.  nq == 0: WS_OK, nothing queued.  ns == 0 with nq > 0: ns everywhere (NOT
+ * WS_ERR_EMPTY: a batch with one empty element still gets its other elements).  NULL required pointers, both outputs or
+ * none, negative lengths, lengths that do not sum to nq / ns: WS_ERR_INVALID, found before the device is touched.
+ * Queued on `stream` without any device-to-host read; nothing synchronises beyond the staging copy of the per-element table
+ * for nb > 48.  The plan state of `ws` (counts, a pending fill, the reusable grid) is gone afterwards. */
+#define WS_NN_STATUS_NONFINITE_QUERY 1
+int ws_nearest_neighbors(ws_neighbors_ws* ws,
+                         const float* queries, int64_t nq, const float* supports, int64_t ns,
+                         const int32_t* h_q_lens, const int32_t* h_s_lens, int32_t nb,
+                         float cell, int32_t* out_i32, int64_t* out_i64, double* out_d2, int32_t* d_status, void* stream);
+
 /* Table-free backward of self-query KPConv layers (queries == supports): the cell grid of the last search and the
  * key of the last neighbour kept per query replace the transposed table (ws_transpose_build).
  *   ws_radius_neighbors_set_key_last  one-shot request: the NEXT search/fill also writes key_last[nq]

@@ -121,7 +121,6 @@ def reprojection_indices(root, cloud_name, file_path, sub_points, dl):
             return z['proj_inds'], z['labels']
     points, labels = read_tile(file_path)
     P = torch.from_numpy(points).to(sub_points.device)
-    # every point lies within one cell diagonal of its own cell's barycentre
-    proj = nearest_projection(P, sub_points, dl * 1.7321 * 1.001).cpu().numpy().astype(np.int32)
+    proj = nearest_projection(P, sub_points).cpu().numpy().astype(np.int32)        # exact, float64 like the tree: no radius
     np.savez(proj_file, proj_inds=proj, labels=labels)
     return proj, labels

@@ -13,8 +13,10 @@
 // Pass A (plan) only counts (-> max_count, the data-dependent width, neighbors.cpp:296-304),
 // pass B (fill) sorts and writes int32 or int64 rows padded with ns (neighbors.cpp:324).
 // The kernels are in neighbors_kernels.h (the walk they share with the grid-walk KPConv backward: ws_grid.h); here the
-// workspace, the fill plan (nb_fill_plan) and the entries.
+// workspace, the fill plan (nb_fill_plan) and the entries.  The exact nearest-neighbour search without a radius
+// (ws_nearest_neighbors, kernels in nearest_kernels.h) walks the same grid and is the last entry of this file.
 #include "neighbors_kernels.h"
+#include "nearest_kernels.h"
 #include "ws_dispatch.h"
 #include <vector>
 #include <algorithm>
@@ -59,6 +61,7 @@ struct ws_neighbors_ws {
     bool reuse_next = false;                   // one-shot: the next plan keeps the support grid (ws_radius_neighbors_reuse_grid)
     const float* supports = nullptr;           // supports of the current grid
     float radius = 0.f;
+    bool auto_cell = false;                    // the current grid's cell was chosen per element (ws_nearest_neighbors, cell = 0)
     std::vector<int32_t> s_lens;               // per-element support counts of the current grid
     std::vector<int32_t> fills;                // caps of the fill launches of the last public entry (0: nb_nearest_kernel)
 };
@@ -84,7 +87,8 @@ void ws_neighbors_ws_destroy(ws_neighbors_ws* ws)
 // bounding boxes, cell grids and the counting sort of the supports (no query work, no sync
 // besides the staging copy of the per-element table)
 static int nb_prepare(ws_neighbors_ws* ws, const float* queries, int64_t nq, const float* supports, int64_t ns,
-                      const int32_t* h_q_lens, const int32_t* h_s_lens, int32_t nb, float radius, hipStream_t st)
+                      const int32_t* h_q_lens, const int32_t* h_s_lens, int32_t nb, float radius, hipStream_t st,
+                      bool auto_cell = false)      // auto_cell: nn_grid_setup_kernel picks the cell per element, `radius` is not read
 {
     WS_REQUIRE(ws && h_q_lens && h_s_lens, "NULL argument");
     ws->fills.clear();
@@ -93,8 +97,8 @@ static int nb_prepare(ws_neighbors_ws* ws, const float* queries, int64_t nq, con
     ws->max_count_host = 0;
     const bool reuse = ws->reuse_next;
     ws->reuse_next = false;
-    if (reuse && ws->supports == supports && ws->ns == ns && ws->nb == nb && ws->radius == radius && nb <= GRID_TABLE_MAX &&
-        ws->max_count_word && nq > 0 && (int)ws->s_lens.size() == nb &&
+    if (reuse && ws->supports == supports && ws->ns == ns && ws->nb == nb && ws->radius == radius && ws->auto_cell == auto_cell &&
+        nb <= GRID_TABLE_MAX && ws->max_count_word && nq > 0 && (int)ws->s_lens.size() == nb &&
         std::equal(ws->s_lens.begin(), ws->s_lens.end(), h_s_lens)) {
         // same supports, same radius as the previous plan (the caller vouches that the support DATA is unchanged):
         // bounding boxes, bins and the cell-sorted copy stay; only the query ranges and the counters are new
@@ -160,7 +164,8 @@ static int nb_prepare(ws_neighbors_ws* ws, const float* queries, int64_t nq, con
     }
     nb_bbox_kernel<<<nb, 1024, 0, st>>>(supports, ws->grids.p, ws->bbox.p);
     WS_LAUNCH_CHECK();
-    nb_grid_setup_kernel<<<(nb + 63) / 64, 64, 0, st>>>(ws->grids.p, ws->bbox.p, nb, radius);
+    if (auto_cell) nn_grid_setup_kernel<<<(nb + 63) / 64, 64, 0, st>>>(ws->grids.p, ws->bbox.p, nb);
+    else nb_grid_setup_kernel<<<(nb + 63) / 64, 64, 0, st>>>(ws->grids.p, ws->bbox.p, nb, radius);
     WS_LAUNCH_CHECK();
     // one memset clears the cell histogram AND the max-count word (kept in the spare slot behind the scan output)
     WS_HIP(hipMemsetAsync(ws->cell_start.p, 0, sizeof(int32_t) * (size_t)(cells + 2), st));
@@ -178,7 +183,7 @@ static int nb_prepare(ws_neighbors_ws* ws, const float* queries, int64_t nq, con
     WS_LAUNCH_CHECK();
     ws->self_query = (queries == supports && nq == ns);
     ws->queries = queries; ws->nq = nq; ws->ns = ns; ws->nb = nb; ws->cells = cells;
-    ws->supports = supports; ws->radius = radius;
+    ws->supports = supports; ws->radius = radius; ws->auto_cell = auto_cell;
     ws->s_lens.assign(h_s_lens, h_s_lens + nb);
     ws->r2 = radius * radius;   // neighbors.cpp:226
     return WS_OK;
@@ -186,9 +191,10 @@ static int nb_prepare(ws_neighbors_ws* ws, const float* queries, int64_t nq, con
 
 // the opening of every entry that builds a plan: a prepare that fails leaves no plan behind
 static int nb_begin(ws_neighbors_ws* ws, const float* queries, int64_t nq, const float* supports, int64_t ns,
-                    const int32_t* h_q_lens, const int32_t* h_s_lens, int32_t nb, float radius, hipStream_t st)
+                    const int32_t* h_q_lens, const int32_t* h_s_lens, int32_t nb, float radius, hipStream_t st,
+                    bool auto_cell = false)
 {
-    const int rc = nb_prepare(ws, queries, nq, supports, ns, h_q_lens, h_s_lens, nb, radius, st);
+    const int rc = nb_prepare(ws, queries, nq, supports, ns, h_q_lens, h_s_lens, nb, radius, st, auto_cell);
     if (rc && ws) ws->nq = 0;
     return rc;
 }
@@ -457,6 +463,54 @@ int ws_radius_neighbors_grid_export(const ws_neighbors_ws* ws, void* blob, void*
                           hipMemcpyDeviceToDevice, st));
     WS_HIP(hipMemcpyAsync(base + ws_grid_blob_sorted_off(ws->nb, ws->cells), ws->sorted.p, sizeof(float4) * (size_t)ws->ns,
                           hipMemcpyDeviceToDevice, st));
+    return WS_OK;
+}
+
+// Exact nearest support of every query (nearest_kernels.h).  The grid is K1's: nb_prepare with radius = cell builds it for any
+// cell size (its cap loop may enlarge the cell: the walk reads the grid's own inv_cell), cell = 0 lets nn_grid_setup_kernel
+// choose.  The edge contract differs from the radius entries', so the arguments are checked here first: nb_prepare then
+// only ever sees nq > 0 and ns > 0.
+int ws_nearest_neighbors(ws_neighbors_ws* ws, const float* queries, int64_t nq, const float* supports, int64_t ns,
+                         const int32_t* h_q_lens, const int32_t* h_s_lens, int32_t nb, float cell, int32_t* out_i32,
+                         int64_t* out_i64, double* out_d2, int32_t* d_status, void* stream)
+{
+    KeyLastGuard guard{ws};
+    WS_REQUIRE(ws && h_q_lens && h_s_lens, "NULL argument");
+    WS_REQUIRE((out_i32 != nullptr) != (out_i64 != nullptr), "exactly one of out_i32 / out_i64 must be given");
+    WS_REQUIRE(nb >= 1 && nq >= 0 && ns >= 0, "bad sizes nb=%d nq=%lld ns=%lld", nb, (long long)nq, (long long)ns);
+    WS_REQUIRE(ns < (1ll << 30) && nq < (1ll << 31), "point count exceeds int32 range");
+    WS_REQUIRE(cell >= 0.f && cell < 3.0e38f, "cell must be finite and >= 0 (0: chosen by the library)");
+    int64_t qsum = 0, ssum = 0;
+    for (int b = 0; b < nb; ++b) {
+        WS_REQUIRE(h_q_lens[b] >= 0 && h_s_lens[b] >= 0, "negative batch length");
+        qsum += h_q_lens[b]; ssum += h_s_lens[b];
+    }
+    WS_REQUIRE(qsum == nq && ssum == ns, "batch lengths do not sum to the point counts (%lld/%lld, %lld/%lld)",
+               (long long)qsum, (long long)nq, (long long)ssum, (long long)ns);
+    WS_REQUIRE(nq == 0 || queries, "NULL argument");
+    WS_REQUIRE(nq == 0 || ns == 0 || supports, "NULL argument");
+    if (nq == 0) return WS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    ws->reuse_next = false;       // a grid of this entry is never taken from a radius plan
+    if (ns > 0) {
+        const int rc = nb_begin(ws, queries, nq, supports, ns, h_q_lens, h_s_lens, nb, cell, st, cell == 0.f);
+        if (rc) return rc;
+    }
+    const int grid = ws_grid(nq, 256);
+    dispatch([&](auto i32) {
+        using OT = std::conditional_t<i32.value != 0, int32_t, int64_t>;
+        OT* out = i32.value ? (OT*)out_i32 : (OT*)out_i64;
+        if (ns == 0)
+            nn_none_kernel<OT><<<grid, 256, 0, st>>>(nq, ns, out, out_d2);
+        else
+            nn_exact_kernel<OT><<<grid, 256, 0, st>>>(queries, nq, ws->grids.p, nb, ws->cell_start.p, ws->sorted.p, ns,
+                                                      ws->self_query ? ws->order.p : nullptr, out, out_d2, d_status);
+    }, Flag{out_i32 != nullptr});
+    WS_LAUNCH_CHECK();
+    // no counts, no rows, and a cell that may differ per element: nothing a fill, an export or a reused grid could continue from
+    ws->nq = 0;
+    ws->fills.clear();
+    ws->supports = nullptr;
     return WS_OK;
 }
 

@@ -1001,6 +1001,39 @@ def radius_neighbors_histogram(queries, supports, q_lens, s_lens, radius, hist):
     return hist
 
 
+NN_STATUS_NONFINITE_QUERY = 1        # weasal_hip.h: WS_NN_STATUS_NONFINITE_QUERY
+
+
+def nearest_neighbors(queries, supports, q_lens, s_lens, cell=0.0, dtype=torch.int32, return_d2=False, status=None):
+    """Exact nearest support of every query, no radius (ws_nearest_neighbors; reference: KDTree.query(points, k=1),
+    datasets/DALES_PseudoLabel.py:888-893).  queries / supports: device float32 [N, 3], stacked batch elements with the HOST
+    lengths q_lens / s_lens.  -> [Nq] of `dtype`: the global index of the support of the same element with the smallest
+    float64 ((dx*dx + dy*dy) + dz*dz), ties to the smallest index; Ns where the element has no supports.  return_d2: also
+    the winning float64 squared distance (+inf beside Ns).  cell: cell size of the grid the search walks, 0 = chosen by
+    the library; the result does not depend on it.  status: device int32 [1] the launch ORs NN_STATUS_* bits into (the
+    caller zeroes it and reads it when it chooses to).  Queued on the current stream; nothing is read back."""
+    import ctypes as C
+    lib = _lib.lib()
+    _need_cuda(queries, supports, status)
+    q = _f32c(queries)
+    s = _f32c(supports)
+    ql, sl = _host_lens(q_lens), _host_lens(s_lens)
+    if ql.shape[0] != sl.shape[0]:
+        raise RuntimeError("Wrong number of batch elements: different for queries and supports ")
+    if dtype not in (torch.int32, torch.int64):
+        raise ValueError("dtype must be torch.int32 or torch.int64")
+    if status is not None and (status.dtype != torch.int32 or status.numel() != 1):
+        raise ValueError("status must be one int32 word on the device")
+    with torch.cuda.device(q.device):
+        out = torch.empty(q.shape[0], dtype=dtype, device=q.device)
+        d2 = torch.empty(q.shape[0], dtype=torch.float64, device=q.device) if return_d2 else None
+        o32, o64 = (ptr(out), None) if dtype == torch.int32 else (None, ptr(out))
+        check(lib.ws_nearest_neighbors(_ws.neighbors(q.device), ptr(q), q.shape[0], ptr(s), s.shape[0],
+                                       C.c_void_p(ql.ctypes.data), C.c_void_p(sl.ctypes.data), ql.shape[0],
+                                       float(np.float32(cell)), o32, o64, ptr(d2), ptr(status), current_stream()))
+    return (out, d2) if return_d2 else out
+
+
 def widen_async_slabs(max_count):
     """a row overflowed the width-sized slab of the asynchronous search (ws_radius_neighbors_async_cap: 5/4 of the limit): this
     data has longer tails than that -- from now on the process uses the full 1024-entry slab for wide rows, so that the

@@ -204,7 +204,7 @@ def write_class_weights(path, weights):
 def roundtrip_projection(full_points, sub_points, dl):
     """-> int32 [N_sub]: the index map of the reference's detour through the full-resolution prediction cloud
     (pseudoLabel_refinement.py:112-125): sub point -> its nearest full point -> that point's nearest sub point, each
-    cloud reduced by its own minimum first (:112, :120).  dl: the cell of the grid subsampling that made sub_points.
+    cloud reduced by its own minimum first (:112, :120).  dl: the cell of the grid subsampling that made sub_points (kept for the callers; the exact search does not read it).
     Optional: proj=None refines the sub-cloud votes directly, which is what tester.VoteAccumulator holds."""
     from . import tester
     ops._need_cuda(full_points, sub_points)
@@ -212,7 +212,6 @@ def roundtrip_projection(full_points, sub_points, dl):
     sub = ops._f32c(sub_points)
     full = full - full.amin(dim=0)
     sub = sub - sub.amin(dim=0)
-    radius = float(dl) * 3.0 ** 0.5
-    to_full = tester.nearest_projection(sub, full, radius)
-    back = tester.nearest_projection(full, sub, radius)
+    to_full = tester.nearest_projection(sub, full)           # the exact search: no radius to derive from dl
+    back = tester.nearest_projection(full, sub)
     return back[to_full.long()].contiguous()

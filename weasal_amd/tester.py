@@ -7,9 +7,11 @@ of every full-cloud point against the sub-sampled cloud) and :335-350 (Tukey upd
 The reference does these on the CPU with sklearn KDTrees that it unpickles from `input_{dl}/`; those pickles are code-
 bearing files and are not read here.  The searches run on the GPU instead:
 
-  * `nearest_projection`  = the K1 radius search with one column (rows are sorted by distance, so column 0 is the nearest
-    sub-cloud point).  A point of a grid-subsampled cloud is never farther than one cell diagonal (dl * sqrt(3)) from its
-    cell's barycentre; rows that find nothing inside the radius are searched again with a doubled radius.
+  * `nearest_projection`  = the exact nearest-neighbour search (ws_nearest_neighbors: float64 distances, any query, one
+    launch).  With a radius: the earlier route, the K1 radius search with one column (rows are
+    sorted by distance, so column 0 is the nearest sub-cloud point).  A point of a grid-subsampled cloud is never farther
+    than one cell diagonal (dl * sqrt(3)) from its cell's barycentre; rows that find nothing inside the radius are
+    searched again with a doubled radius.
   * `VoteAccumulator`     = per-cloud class probabilities resident in HBM; one fused kernel per sphere does softmax + radius
     mask + exponential smoothing at the sphere's input indices (ws_vote_update); re-projection + arg-max + confusion matrix
     in one kernel (ws_project_confusion).
@@ -84,16 +86,21 @@ def IoU_from_confusions(confusions):
 # ---------------------------------------------------------------------------------------------------------------
 # nearest-neighbour projection (DALES_PseudoLabel.py:888-892)
 # ---------------------------------------------------------------------------------------------------------------
-def nearest_projection(points, sub_points, radius, chunk=1 << 22):
+def nearest_projection(points, sub_points, radius=None, chunk=1 << 22):
     """int32 [N]: index of the sub-cloud point nearest to every point (KDTree.query(points, k=1) of the reference), on the
-    device.  `radius`: a distance within which every point is expected to have a neighbour (dl * sqrt(3) for a cloud that
-    was grid-subsampled with cell dl); points that find none are searched again with the radius doubled."""
+    device.  radius=None: the exact search (ops.nearest_neighbors) -- one call for all points, the tree's float64
+    arithmetic, no host read; a point with a non-finite coordinate gets len(sub_points).
+    `radius`: the earlier route through the K1 radius search, float32: a distance within which every point is expected to
+    have a neighbour (dl * sqrt(3) for a cloud that was grid-subsampled with cell dl); points that find none are searched
+    again with the radius doubled."""
     ops._need_cuda(points, sub_points)
     P = ops._f32c(points)
     S = ops._f32c(sub_points)
     n, m = P.shape[0], S.shape[0]
     if m == 0:
         raise RuntimeError("nearest_projection: empty sub-cloud")
+    if radius is None:
+        return ops.nearest_neighbors(P, S, [n], [m])
     out = torch.empty(n, dtype=torch.int32, device=P.device)
     for a in range(0, n, chunk):
         q = P[a:a + chunk]

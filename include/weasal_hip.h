@@ -1359,6 +1359,50 @@ int ws_bce_heads_fwd(const float* x, int64_t r, int32_t c, int32_t heads, int64_
 int ws_bce_heads_bwd(const float* x, int64_t r, int32_t c, int32_t heads, int64_t ldx, const float* target, const float* weight,
                      const float* g_heads, const float* g_sum, float* dx, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Batch normalisation over the point axis of the stacked batch, with the residual sum and the LeakyReLU that follow it in
+ * the blocks: weasal_amd/csrc/batchnorm.hip.  Stands for the BatchNormBlock of models/blocks.py:430-470 run the way KPConv
+ * applies nn.BatchNorm1d to [N, C] features (the reference constructs the module and returns 2-D inputs untouched; that
+ * identity stays this project's default, these entries are what `batch_norm_mode = points` runs).
+ * y, out, residual, dout, dy, dresidual: [n, c] float32 rows of unit column stride at the given pitch (>= c); gamma, beta,
+ * running_mean, running_var, save_mean, save_rstd, dgamma, dbeta: [c] float32; num_batches_tracked: one int64 (NULL = none).
+ * act: 0 none, 1 LeakyReLU(slope).  Any c >= 1 up to 2^20.  16-byte accesses when c % 4 == 0 and every pitch is a multiple
+ * of 4 and every [n, c] pointer is 16-byte aligned; scalar accesses otherwise.  float32 arithmetic, centred variance
+ * (two passes over registers, Chan's merge of (count, mean, M2) beyond), no float atomics, every merge in an order fixed by
+ * the shapes: run-to-run bit-identical.  The plan depends on shapes, pitches and pointer alignment only.  Argument checks
+ * need no device.  n == 0: WS_OK, no kernel, statistics untouched (ws_bn_bwd zeroes dgamma / dbeta).
+ *
+ * ws_bn_scratch_bytes: bytes of `scratch` for either entry at these sizes, whatever the alignment; -1 for bad sizes.
+ * ws_bn_fwd (nn.BatchNorm1d.forward, then `+ residual`, then nn.LeakyReLU -- models/blocks.py:430-470, :497-506):
+ *   training != 0: mean_c, biased var_c over the n rows; out = act((y - mean) * rstd * gamma + beta [+ residual]) with
+ *     rstd = 1 / sqrt(var + eps); save_mean, save_rstd are written for ws_bn_bwd; on the device, nothing read back:
+ *     running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with var n / (n - 1),
+ *     *num_batches_tracked += 1.  n == 1 is WS_ERR_INVALID, as torch refuses it.  Three launches.
+ *   training == 0: the same with mean = running_mean, var = running_var; nothing else is written (save_mean, save_rstd and
+ *     scratch may be NULL).  One launch.
+ * ws_bn_bwd: dz = dout * (out > 0 ? 1 : slope) -- the gate is taken from the OUTPUT -- or dout when act == 0 (out may then
+ *   be NULL); dbeta = column sums of dz, dgamma = column sums of dz * xhat; dresidual = dz unless NULL;
+ *   training != 0: dy = gamma rstd (dz - dbeta / n - xhat dgamma / n) with save_mean / save_rstd of the forward call;
+ *   training == 0 (BN frozen, gradients wanted): dy = gamma rstd dz with running_mean / running_var and eps.
+ *   One reduction pass for both column sums, a finish kernel, one apply pass.
+ * ws_bn_variant: the branch a call takes, from the launchers' own plan function; nothing is read or launched.  backward
+ *   == 0: ws_bn_fwd (dout, dy unused); != 0: ws_bn_bwd (residual / ldr stand for dresidual / lddr).  Pointers are tested
+ *   for NULL and alignment only.  Text: "kernels<V=..> vector|scalar rows=<rows per chunk> chunks=.. depth=<merge levels>
+ *   tile=<columns per workgroup> lanes=<row lanes> ctiles=.. mode=training|evaluation residual=0|1 act=0|1".
+ * ------------------------------------------------------------------------------------------ */
+int64_t ws_bn_scratch_bytes(int64_t n, int32_t c);
+int ws_bn_fwd(const float* y, int64_t n, int32_t c, int64_t ldy, const float* gamma, const float* beta, float eps, int32_t training,
+              float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked, const float* residual,
+              int64_t ldr, int32_t act, float slope, float* out, int64_t ldo, float* save_mean, float* save_rstd, void* scratch,
+              void* stream);
+int ws_bn_bwd(const float* dout, int64_t lddo, const float* out, int64_t ldo, const float* y, int64_t ldy, int64_t n, int32_t c,
+              const float* gamma, const float* save_mean, const float* save_rstd, const float* running_mean,
+              const float* running_var, float eps, int32_t training, int32_t act, float slope, float* dy, int64_t lddy,
+              float* dresidual, int64_t lddr, float* dgamma, float* dbeta, void* scratch, void* stream);
+int ws_bn_variant(int32_t backward, int64_t n, int32_t c, const void* y, int64_t ldy, const void* out, int64_t ldo,
+                  const void* residual, int64_t ldr, const void* dout, int64_t lddo, const void* dy, int64_t lddy, int32_t training,
+                  int32_t act, char* text, int32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

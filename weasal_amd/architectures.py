@@ -134,6 +134,7 @@ class KPFCNN(nn.Module):
         # BASELINE config 5: feature rows (activations, their gradients, weighted features) bf16 in HBM, fp32 accumulate,
         # fp32 master weights; the 3-channel input layer and the 9 logits stay f32
         self.feature_dtype = torch.bfloat16 if getattr(config, 'feature_dtype', 'f32') == 'bf16' else torch.float32
+        self.batch_norm_mode = _blocks.bn_mode(config)       # 'reference' | 'points'; raises for 'points' with bf16 rows
         if self.feature_dtype == torch.bfloat16:
             self.head_softmax.out_f32 = True
 
@@ -144,8 +145,10 @@ class KPFCNN(nn.Module):
         c_up = x.shape[1]
         w = unary.mlp.weight
         y = closest_pool(ops.linear(x, w[:, :c_up]), batch.upsamples[up_block.layer_ind - 1])
-        return ops.matmul_epilogue(skip, w[:, c_up:].t(), bias=unary.batch_norm.epilogue_bias(), residual=y,
-                                   slope=None if unary.no_relu else 0.1)
+        # (`y` is part of the product: in 'points' mode the normalisation follows the whole sum)
+        return unary.batch_norm.epilogue(lambda bias, _res, slope: ops.matmul_epilogue(skip, w[:, c_up:].t(), bias=bias, residual=y,
+                                                                                       slope=slope),
+                                         None, None if unary.no_relu else 0.1)
 
     def forward(self, batch, config):
         if hasattr(batch, "activate"):

@@ -12,7 +12,9 @@ them in the blocks applied in the GEMM epilogue.
 
 Quirks of the reference that are preserved on purpose:
   * BatchNormBlock is an identity for 2-D inputs when use_bn is set (blocks.py:454-463); the
-    BatchNorm1d parameters exist in the state_dict but never run;
+    BatchNorm1d parameters exist in the state_dict but never run.  This is the default; a configuration
+    that sets `batch_norm_mode = 'points'` runs them over the point axis instead (ops.batch_norm_act,
+    weasal_amd/csrc/batchnorm.hip), the way KPConv applies nn.BatchNorm1d;
   * shadow neighbours (index == number of supports) are the point (1e6,1e6,1e6) with a zero
     feature row (blocks.py:278,357); max_pool includes that zero row (blocks.py:104).
 """
@@ -206,9 +208,23 @@ _RESNETB = ('resnetb', 'resnetb_invariant', 'resnetb_equivariant', 'resnetb_defo
             'resnetb_deformable_strided', 'resnetb_equivariant_strided', 'resnetb_invariant_strided')
 
 
+BN_MODES = ('reference', 'points')
+
+
+def bn_mode(config):
+    """the configuration's `batch_norm_mode` ('reference' when it has none); 'points' with bf16 feature rows is refused:
+    the normalisation kernels take float32 rows only"""
+    mode = getattr(config, 'batch_norm_mode', 'reference')
+    if mode not in BN_MODES:
+        raise ValueError("batch_norm_mode must be one of %s (got %r)" % (BN_MODES, mode))
+    if mode == 'points' and config.use_batch_norm and getattr(config, 'feature_dtype', 'f32') == 'bf16':
+        raise ValueError("batch_norm_mode = 'points' needs float32 feature rows (feature_dtype = 'bf16')")
+    return mode
+
+
 def block_decider(block_name, radius, in_dim, out_dim, layer_ind, config):
     if block_name == 'unary':
-        return UnaryBlock(in_dim, out_dim, config.use_batch_norm, config.batch_norm_momentum)
+        return UnaryBlock(in_dim, out_dim, config.use_batch_norm, config.batch_norm_momentum, bn_mode=bn_mode(config))
     if block_name in _SIMPLE:
         return SimpleBlock(block_name, in_dim, out_dim, radius, layer_ind, config)
     if block_name in _RESNETB:
@@ -224,13 +240,18 @@ def block_decider(block_name, radius, in_dim, out_dim, layer_ind, config):
 
 class BatchNormBlock(nn.Module):
     """BatchNorm1d holder that is an identity on [N,C] inputs when use_bn (blocks.py:453-463),
-    a learned bias otherwise (:465)."""
+    a learned bias otherwise (:465).  mode = 'points' (with use_bn): the BatchNorm1d runs over the point axis of [N, C]
+    inputs -- batch statistics when training, running statistics in evaluation -- as KPConv applies it; same parameters,
+    buffers and state_dict keys.  Callers go through `epilogue`, which makes the choice for them."""
 
-    def __init__(self, in_dim, use_bn, bn_momentum):
+    def __init__(self, in_dim, use_bn, bn_momentum, mode='reference'):
         super(BatchNormBlock, self).__init__()
+        if mode not in BN_MODES:
+            raise ValueError("BatchNormBlock mode must be one of %s (got %r)" % (BN_MODES, mode))
         self.bn_momentum = bn_momentum
         self.use_bn = use_bn
         self.in_dim = in_dim
+        self.mode = mode
         if self.use_bn:
             self.batch_norm = nn.BatchNorm1d(in_dim, momentum=bn_momentum)
         else:
@@ -243,11 +264,34 @@ class BatchNormBlock(nn.Module):
         """what this block adds to a 2-D input: nothing with use_bn (identity), the bias otherwise"""
         return None if self.use_bn else self.bias
 
+    def live(self):
+        """whether the BatchNorm1d runs on [N, C] inputs ('points' mode with use_bn)"""
+        return self.use_bn and self.mode == 'points'
+
+    def epilogue(self, product, residual=None, slope=None):
+        """what follows a block's product: `product(bias, residual, slope)` is the caller's GEMM / KPConv with this epilogue.
+        Reference mode and bias blocks: one call with epilogue_bias(), the residual and the slope.  Live: the raw product,
+        then the normalisation with the residual sum and the LeakyReLU in one operator."""
+        if not self.live():
+            return product(self.epilogue_bias(), residual, slope)
+        return self.normalise(product(None, None, None), residual, slope)
+
+    def normalise(self, y, residual=None, slope=None):
+        """act(batch_norm(y) [+ residual]) on [N, C]: ops.batch_norm_act for float32 device rows; CPU tensors
+        (oracle.kpconv_ref.cpu_reference_mode), other dtypes and WEASAL_BN_KERNELS=0 run the framework's operators"""
+        if ops.BN_KERNELS and y.is_cuda and y.dtype == torch.float32 and y.dim() == 2 \
+                and (residual is None or (residual.is_cuda and residual.dtype == torch.float32)):
+            return ops.batch_norm_act(y, self.batch_norm, residual=residual, slope=slope)
+        z = self.batch_norm(y)
+        if residual is not None:
+            z = z + residual
+        return z if slope is None else nn.functional.leaky_relu(z, slope)
+
     def forward(self, x):
         if not self.use_bn:
             return x + self.bias
         if x.dim() < 3:
-            return x
+            return self.normalise(x) if self.live() else x
         # 3-D inputs never occur on this path; kept for interface parity (blocks.py:458-462)
         y = self.batch_norm(x.unsqueeze(2).transpose(0, 2))
         return y.transpose(0, 2)
@@ -260,7 +304,7 @@ class BatchNormBlock(nn.Module):
 class UnaryBlock(nn.Module):
     """Linear(no bias) -> BatchNormBlock -> LeakyReLU(0.1) unless no_relu (blocks.py:473-507)"""
 
-    def __init__(self, in_dim, out_dim, use_bn, bn_momentum, no_relu=False):
+    def __init__(self, in_dim, out_dim, use_bn, bn_momentum, no_relu=False, bn_mode='reference'):
         super(UnaryBlock, self).__init__()
         self.bn_momentum = bn_momentum
         self.use_bn = use_bn
@@ -268,7 +312,7 @@ class UnaryBlock(nn.Module):
         self.in_dim = in_dim
         self.out_dim = out_dim
         self.mlp = nn.Linear(in_dim, out_dim, bias=False)
-        self.batch_norm = BatchNormBlock(out_dim, self.use_bn, self.bn_momentum)
+        self.batch_norm = BatchNormBlock(out_dim, self.use_bn, self.bn_momentum, mode=bn_mode)
         if not no_relu:
             self.leaky_relu = nn.LeakyReLU(0.1)
         self.out_f32 = False     # bf16 feature rows only: keep this block's output in f32 (the logits)
@@ -281,6 +325,10 @@ class UnaryBlock(nn.Module):
         slope_override: activation applied although the block itself has no_relu (the residual sum of
         ResnetBottleneckBlock, blocks.py:709)."""
         slope = slope_override if slope_override is not None else (None if self.no_relu else 0.1)
+        if self.batch_norm.live():
+            # 'points' mode: the raw product, then the normalisation with the residual and the slope (no gate links)
+            return self.batch_norm.epilogue(lambda bias, res, sl: ops.matmul_epilogue(x, self.mlp.weight.t(), bias=bias, residual=res,
+                                                                                     slope=sl), residual, slope)
         if x.dtype == torch.bfloat16:
             return ops.matmul_epilogue(x, self.mlp.weight.t(), bias=self.batch_norm.epilogue_bias(), residual=residual,
                                        slope=slope, out_f32=self.out_f32)
@@ -330,14 +378,14 @@ class SimpleBlock(nn.Module):
         self.in_dim = in_dim
         self.out_dim = out_dim
         self.KPConv = _make_kpconv(block_name, in_dim, out_dim // 2, radius, config)
-        self.batch_norm = BatchNormBlock(out_dim // 2, self.use_bn, self.bn_momentum)
+        self.batch_norm = BatchNormBlock(out_dim // 2, self.use_bn, self.bn_momentum, mode=bn_mode(config))
         self.leaky_relu = nn.LeakyReLU(0.1)
 
     def forward(self, x, batch):
         q_pts, s_pts, inds = _layer_geometry(self.block_name, self.layer_ind, batch)
         if fused.kpblock_eligible(self, x):
             return fused.simple_block(self, x, batch, q_pts, s_pts, inds)      # one C call each way (csrc/blocks.hip)
-        return self.KPConv(q_pts, s_pts, inds, x, _bias=self.batch_norm.epilogue_bias(), _slope=0.1)
+        return self.batch_norm.epilogue(lambda bias, _res, slope: self.KPConv(q_pts, s_pts, inds, x, _bias=bias, _slope=slope), None, 0.1)
 
 
 class SimpleBlock2(nn.Module):
@@ -352,14 +400,14 @@ class SimpleBlock2(nn.Module):
         self.in_dim = in_dim
         self.out_dim = out_dim
         self.KPConv = _make_kpconv(block_name, in_dim, out_dim, radius, config)
-        self.batch_norm = BatchNormBlock(out_dim, self.use_bn, self.bn_momentum)
+        self.batch_norm = BatchNormBlock(out_dim, self.use_bn, self.bn_momentum, mode=bn_mode(config))
         self.leaky_relu = nn.LeakyReLU(0.1)
 
     def forward(self, x, batch):
         q_pts, s_pts, inds = _layer_geometry(self.block_name, self.layer_ind, batch)
         if fused.kpblock_eligible(self, x):
             return fused.simple_block(self, x, batch, q_pts, s_pts, inds)      # one C call each way (csrc/blocks.hip)
-        return self.KPConv(q_pts, s_pts, inds, x, _bias=self.batch_norm.epilogue_bias(), _slope=0.1)
+        return self.batch_norm.epilogue(lambda bias, _res, slope: self.KPConv(q_pts, s_pts, inds, x, _bias=bias, _slope=slope), None, 0.1)
 
 
 class ResnetBottleneckBlock(nn.Module):
@@ -375,12 +423,13 @@ class ResnetBottleneckBlock(nn.Module):
         self.in_dim = in_dim
         self.out_dim = out_dim
         mid = out_dim // 4
-        self.unary1 = UnaryBlock(in_dim, mid, self.use_bn, self.bn_momentum) if in_dim != mid else nn.Identity()
+        mode = bn_mode(config)
+        self.unary1 = UnaryBlock(in_dim, mid, self.use_bn, self.bn_momentum, bn_mode=mode) if in_dim != mid else nn.Identity()
         self.KPConv = _make_kpconv(block_name, mid, mid, radius, config)
-        self.batch_norm_conv = BatchNormBlock(mid, self.use_bn, self.bn_momentum)
-        self.unary2 = UnaryBlock(mid, out_dim, self.use_bn, self.bn_momentum, no_relu=True)
+        self.batch_norm_conv = BatchNormBlock(mid, self.use_bn, self.bn_momentum, mode=mode)
+        self.unary2 = UnaryBlock(mid, out_dim, self.use_bn, self.bn_momentum, no_relu=True, bn_mode=mode)
         if in_dim != out_dim:
-            self.unary_shortcut = UnaryBlock(in_dim, out_dim, self.use_bn, self.bn_momentum, no_relu=True)
+            self.unary_shortcut = UnaryBlock(in_dim, out_dim, self.use_bn, self.bn_momentum, no_relu=True, bn_mode=mode)
         else:
             self.unary_shortcut = nn.Identity()
         self.leaky_relu = nn.LeakyReLU(0.1)
@@ -390,7 +439,7 @@ class ResnetBottleneckBlock(nn.Module):
         if fused.kpblock_eligible(self, features):
             return fused.resnetb_block(self, features, batch, q_pts, s_pts, inds)   # one C call each way (csrc/blocks.hip)
         x = self.unary1(features)
-        x = self.KPConv(q_pts, s_pts, inds, x, _bias=self.batch_norm_conv.epilogue_bias(), _slope=0.1)
+        x = self.batch_norm_conv.epilogue(lambda bias, _res, slope: self.KPConv(q_pts, s_pts, inds, x, _bias=bias, _slope=slope), None, 0.1)
         shortcut = max_pool(features, inds) if 'strided' in self.block_name else features
         # leaky_relu(unary2(x) + unary_shortcut(shortcut)) with the sum and the activation in unary2's GEMM
         return self.unary2.forward_fused(x, residual=self.unary_shortcut(shortcut), slope_override=0.1)
@@ -467,9 +516,9 @@ class spatial_att(nn.Module):
         self.in_dim = in_dim
         self.out_dim = out_dim
         self.simple1 = SimpleBlock2(block_name, in_dim, out_dim, radius, layer_ind, config)
-        self.unary1 = UnaryBlock(out_dim, out_dim // 8, self.use_bn, self.bn_momentum)
-        self.unary2 = UnaryBlock(out_dim, out_dim // 8, self.use_bn, self.bn_momentum)
-        self.unary3 = UnaryBlock(out_dim, out_dim, self.use_bn, self.bn_momentum)
+        self.unary1 = UnaryBlock(out_dim, out_dim // 8, self.use_bn, self.bn_momentum, bn_mode=bn_mode(config))
+        self.unary2 = UnaryBlock(out_dim, out_dim // 8, self.use_bn, self.bn_momentum, bn_mode=bn_mode(config))
+        self.unary3 = UnaryBlock(out_dim, out_dim, self.use_bn, self.bn_momentum, bn_mode=bn_mode(config))
         self.gamma = nn.Parameter(torch.zeros(1))
         self.softmax = nn.Softmax(dim=-1)
         self.simple2 = SimpleBlock2(block_name, in_dim, out_dim, radius, layer_ind, config)
@@ -504,8 +553,8 @@ class channel_att(nn.Module):
         self.in_dim = in_dim
         self.out_dim = out_dim
         self.simple1 = SimpleBlock2(block_name, in_dim, out_dim // 8, radius, layer_ind, config)
-        self.unary1 = UnaryBlock(out_dim // 8, out_dim // 8, self.use_bn, self.bn_momentum)
-        self.unary2 = UnaryBlock(out_dim // 8, out_dim // 8, self.use_bn, self.bn_momentum)
+        self.unary1 = UnaryBlock(out_dim // 8, out_dim // 8, self.use_bn, self.bn_momentum, bn_mode=bn_mode(config))
+        self.unary2 = UnaryBlock(out_dim // 8, out_dim // 8, self.use_bn, self.bn_momentum, bn_mode=bn_mode(config))
         self.gamma = nn.Parameter(torch.zeros(1))
         self.softmax = nn.Softmax(dim=-1)
         self.simple2 = SimpleBlock2(block_name, out_dim // 8, out_dim, radius, layer_ind, config)
@@ -541,10 +590,10 @@ class multi_path_att(nn.Module):
         self.sa_f = spatial_att(block_name, in_dim, out_dim, radius, layer_ind, config)
         self.ca_f = channel_att(block_name, in_dim, out_dim, radius, layer_ind, config)
         self.simple1 = SimpleBlock2(block_name, in_dim + out_dim, out_dim, radius, layer_ind, config)
-        self.sa_unary = UnaryBlock(out_dim, fdim, self.use_bn, self.bn_momentum)
-        self.ca_unary = UnaryBlock(out_dim, fdim, self.use_bn, self.bn_momentum)
-        self.no_unary = UnaryBlock(in_dim, fdim, self.use_bn, self.bn_momentum)
-        self.pa_unary = UnaryBlock(out_dim, fdim, self.use_bn, self.bn_momentum)
+        self.sa_unary = UnaryBlock(out_dim, fdim, self.use_bn, self.bn_momentum, bn_mode=bn_mode(config))
+        self.ca_unary = UnaryBlock(out_dim, fdim, self.use_bn, self.bn_momentum, bn_mode=bn_mode(config))
+        self.no_unary = UnaryBlock(in_dim, fdim, self.use_bn, self.bn_momentum, bn_mode=bn_mode(config))
+        self.pa_unary = UnaryBlock(out_dim, fdim, self.use_bn, self.bn_momentum, bn_mode=bn_mode(config))
 
     def forward(self, features, batch):
         sa, sa_x = self.sa_f(features, batch)
@@ -582,8 +631,8 @@ class ele_att(nn.Module):
         self.block_name = block_name
         self.in_dim = in_dim
         self.out_dim = out_dim
-        self.unary1 = UnaryBlock(in_dim, out_dim, self.use_bn, self.bn_momentum)
-        self.unary2 = UnaryBlock(in_dim, out_dim, self.use_bn, self.bn_momentum)
+        self.unary1 = UnaryBlock(in_dim, out_dim, self.use_bn, self.bn_momentum, bn_mode=bn_mode(config))
+        self.unary2 = UnaryBlock(in_dim, out_dim, self.use_bn, self.bn_momentum, bn_mode=bn_mode(config))
         self.gamma = nn.Parameter(torch.zeros(1))
         self.softmax = nn.Softmax(dim=-1)
         self.simple2 = SimpleBlock2(block_name, out_dim, out_dim, radius, layer_ind, config)

@@ -8,7 +8,9 @@ launches its 6-7 kernels from C, its backward one call that launches 10-14; the 
 to add with separate kernels (shortcut + main branch into the block input) are residual operands of GEMM epilogues.
 Same arithmetic as weasal_amd.blocks' operator-by-operator path (same kernels, same order inside every sum), which
 stays in place for everything these calls do not cover (deformable / modulated KPConv, bf16 rows, non-linear influence,
-CPU oracle mode).
+CPU oracle mode, and any block one of whose BatchNormBlocks is live -- `batch_norm_mode = 'points'` with use_batch_norm:
+every route of this module declines then -- block calls, decoder steps, gate links, skip slots, the forward-only fused
+layer -- and the operators run the raw products followed by ops.batch_norm_act).
 """
 import ctypes as C
 import os
@@ -344,9 +346,25 @@ def _geometry(conv, q_pts, s_pts, inds, strided):
 MIN_ROWS = int(os.environ.get("WEASAL_FUSED_MIN_ROWS", "0"))
 
 
+def bn_live(*modules):
+    """whether a BatchNormBlock of these blocks (their own `batch_norm` / `batch_norm_conv`, or their unary blocks') runs
+    over the points: the block calls know the identity and the bias only"""
+    for m in modules:
+        for name in ("batch_norm", "batch_norm_conv", "unary1", "unary2", "unary_shortcut"):
+            sub = getattr(m, name, None)
+            if sub is None:
+                continue
+            if hasattr(sub, "live"):
+                if sub.live():
+                    return True
+            elif hasattr(sub, "batch_norm") and hasattr(sub.batch_norm, "live") and sub.batch_norm.live():
+                return True
+    return False
+
+
 def kpblock_eligible(block, x):
     conv = block.KPConv
-    if not _conv_ok(conv, x) or x.shape[0] < MIN_ROWS:
+    if not _conv_ok(conv, x) or x.shape[0] < MIN_ROWS or bn_live(block):
         return False
     dims = [conv.out_channels]
     if hasattr(block, "unary2"):
@@ -465,7 +483,7 @@ class _UpUnaryFn(torch.autograd.Function):
 def upunary_eligible(x, skip, unary):
     return (FUSED_BLOCKS and x.is_cuda and x.dtype == torch.float32 and skip.dtype == torch.float32
             and ops.kpconv_gather is _KPCONV_GATHER and x.shape[1] % 32 == 0 and skip.shape[1] % 32 == 0
-            and unary.out_dim % 32 == 0 and x.shape[0] > 0 and skip.shape[0] >= MIN_ROWS)
+            and unary.out_dim % 32 == 0 and x.shape[0] > 0 and skip.shape[0] >= MIN_ROWS and not bn_live(unary))
 
 
 def upunary(x, skip, unary, ups, drop=None, batch=None):

@@ -1892,3 +1892,77 @@ def side_by_side(tensors):
                 or t.stride() != base.stride() or t.storage_offset() != base.storage_offset() + k * c or t.dtype != base.dtype):
             return None
     return base
+
+
+# ------------------------------------------------------------------------------------------------
+# batch normalisation over the points (weasal_amd/csrc/batchnorm.hip): what a BatchNormBlock in 'points' mode runs
+# ------------------------------------------------------------------------------------------------
+BN_KERNELS = os.environ.get("WEASAL_BN_KERNELS", "1") != "0"       # A/B switch: 0 = 'points' mode runs F.batch_norm + add + F.leaky_relu
+
+
+class _BatchNormAct(torch.autograd.Function):
+    """out = act(BN(y) [+ residual]) over ws_bn_fwd / ws_bn_bwd; saves y, out, save_mean, save_rstd"""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, residual, bn, slope):
+        lib = _lib.lib()
+        yc, ldy = _rows_f32(y)
+        n, c = int(yc.shape[0]), int(yc.shape[1])
+        rc, ldr = _rows_f32(residual) if residual is not None else (None, 0)
+        training = bool(bn.training)
+        act, sl = _act_args(slope)
+        dev = y.device
+        out = torch.empty((n, c), dtype=torch.float32, device=dev)
+        save_mean = torch.empty((c,), dtype=torch.float32, device=dev) if training else None
+        save_rstd = torch.empty((c,), dtype=torch.float32, device=dev) if training else None
+        scratch = _scratch(lib.ws_bn_scratch_bytes(n, c), dev)
+        g, b = _f32c(gamma), _f32c(beta)
+        check(lib.ws_bn_fwd(ptr(yc), n, c, ldy, ptr(g), ptr(b), float(bn.eps), 1 if training else 0, float(bn.momentum),
+                            ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked), ptr(rc), ldr, act, sl,
+                            ptr(out), c, ptr(save_mean), ptr(save_rstd), ptr(scratch), current_stream()))
+        ctx.save_for_backward(yc, out, save_mean, save_rstd, g)
+        ctx.bn, ctx.training, ctx.act, ctx.ldy, ctx.has_res = bn, training, (act, sl), ldy, residual is not None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        lib = _lib.lib()
+        yc, out, save_mean, save_rstd, g = ctx.saved_tensors
+        bn = ctx.bn
+        n, c = int(yc.shape[0]), int(yc.shape[1])
+        d, lddo = _rows_f32(dout)
+        dev = yc.device
+        dy = torch.empty((n, c), dtype=torch.float32, device=dev)
+        dres = torch.empty((n, c), dtype=torch.float32, device=dev) if (ctx.has_res and ctx.needs_input_grad[3]) else None
+        dgamma = torch.empty((c,), dtype=torch.float32, device=dev)
+        dbeta = torch.empty((c,), dtype=torch.float32, device=dev)
+        scratch = _scratch(lib.ws_bn_scratch_bytes(n, c), dev)
+        act, sl = ctx.act
+        check(lib.ws_bn_bwd(ptr(d), lddo, ptr(out), c, ptr(yc), ctx.ldy, n, c, ptr(g), ptr(save_mean), ptr(save_rstd),
+                            ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), 1 if ctx.training else 0, act, sl,
+                            ptr(dy), c, ptr(dres), c, ptr(dgamma), ptr(dbeta), ptr(scratch), current_stream()))
+        return dy, dgamma, dbeta, dres, None, None
+
+
+def batch_norm_act(y, bn_module, residual=None, slope=None):
+    """act(BatchNorm1d(y) [+ residual]) for y [N, C] float32 on the device: what `nn.BatchNorm1d` (bn_module: its weight, bias,
+    running buffers, eps, momentum and training flag, all read at this call) followed by `+ residual` and LeakyReLU(slope)
+    give, up to float32 summation order (models/blocks.py:430-470 as KPConv runs it).  Training updates the running buffers
+    and num_batches_tracked on the device.  Differentiable once in y, weight, bias and residual; N = 0 returns an empty
+    tensor and touches nothing.  Refused: CPU tensors, bf16 rows, momentum None, training with a single row (ValueError, as
+    torch raises)."""
+    _need_cuda(y, residual, bn_module.weight)
+    if y.dim() != 2 or y.shape[1] != bn_module.num_features:
+        raise ValueError("batch_norm_act: y must be [N, %d]" % bn_module.num_features)
+    if y.dtype != torch.float32 or (residual is not None and residual.dtype != torch.float32):
+        raise ValueError("batch_norm_act: float32 rows only (got %s)" % y.dtype)
+    if residual is not None and residual.shape != y.shape:
+        raise ValueError("batch_norm_act: residual must have the shape of y")
+    if bn_module.momentum is None:
+        raise ValueError("batch_norm_act: momentum=None (cumulative average) is not supported")
+    if bn_module.weight is None or bn_module.running_mean is None:
+        raise ValueError("batch_norm_act: the module must be affine and track running statistics")
+    if bn_module.training and y.shape[0] == 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(y.shape),))
+    return _BatchNormAct.apply(y, bn_module.weight, bn_module.bias, residual, bn_module, slope)

@@ -1403,6 +1403,48 @@ int ws_bn_variant(int32_t backward, int64_t n, int32_t c, const void* y, int64_t
                   const void* residual, int64_t ldr, const void* dout, int64_t lddo, const void* dy, int64_t lddy, int32_t training,
                   int32_t act, char* text, int32_t cap);
 
+/* ------------------------------------------------------------------------------------------
+ * Evaluation-mode batch normalisation folded into the product in front of it: weasal_amd/csrc/bn_fold.hip.  With running
+ * statistics BN is an affine map per output channel, rstd = 1 / sqrt(running_var + eps), a = gamma rstd,
+ * t = beta - running_mean a, and act(BN(x W^T) + residual) = act(x (a (.)rows W)^T + t + residual): the bias / residual /
+ * LeakyReLU epilogue every product and block call above already takes.
+ * A SITE is a weight seen as [outer, c, inner] float32, contiguous, the BN channel on the middle axis (nn.Linear.weight
+ * [c, k]: outer 1, inner k; KPConv weights [K, Ci, Co]: outer K Ci, inner 1) with gamma, beta, running_mean, running_var [c]
+ * and eps.  Both entries take a TABLE of `count` sites as HOST arrays (h_*) of device pointers, sizes and eps values, the
+ * idiom of ws_sgd_step; the table travels in the kernel arguments, WS_BN_FOLD_MAX sites per launch, and workgroups are dealt
+ * to the sites by a prefix over their element counts (4096 per workgroup).  A site with c == 0 is passed over; count == 0 or
+ * nothing but such sites: WS_OK, no launch.  outer c inner < 2^31 - 4096.  float32 arithmetic, every operation rounded on
+ * its own (the unit is compiled with -ffp-contract=off): rstd = 1 / sqrtf(var + eps), a = gamma * rstd.  16-byte accesses
+ * to the [outer, c, inner] tensors when they are 16-byte aligned and inner % 4 == 0 or (inner == 1 and c % 4 == 0); scalar
+ * accesses otherwise; [c] vectors may have any alignment.  Argument checks need no device.
+ *
+ * ws_bn_fold_fwd: w_out = a * w (a buffer of its own, the shape of w), t_out = beta - mean * a.  One launch per
+ *   WS_BN_FOLD_MAX sites.
+ * ws_bn_fold_bwd: dw = a * dw_out, dbeta = dt_out, dgamma_c = rstd_c * (sum over outer, inner of dw_out * w - mean_c *
+ *   dt_out_c); the running buffers get no gradient.  h_dw_out[t] / h_dt_out[t] NULL: zeros (a folded weight used without its
+ *   bias, a site whose output nobody differentiated).  h_dw[t] / h_dgamma[t] / h_dbeta[t] NULL: that output is not written
+ *   (all three NULL: the site is passed over).  The per-channel sum runs in an order fixed by the shapes -- inner > 1: a
+ *   wave per channel, lane l adds elements l, l + 64, ... of every outer slice in index order, lanes folded by xor-shuffles
+ *   (row sums); inner == 1: a workgroup per 64 columns (16 from 1024 rows on), row lane r adds rows r, r + lanes, ..., the
+ *   lanes of a column added in lane order (column sums) -- no float atomics, run-to-run bit-identical.  One launch per
+ *   WS_BN_FOLD_MAX sites holds the element-wise part and the sums.
+ * ws_bn_fold_variant: the branch ONE site takes and the launches of a table of `count` sites, from the launchers' own plan
+ *   function; nothing is read or launched.  src / dst: the pointers of the element-wise part (forward w, w_out; backward
+ *   dw_out, dw), tested for alignment only (NULL passes).  Text, forward: "bn_fold_fwd_kernel vector|scalar blocks=..
+ *   launches=.."; backward: "bn_fold_bwd_kernel vector|scalar row-sum|column-sum tile=<channels per workgroup>
+ *   ew_blocks=.. sum_blocks=.. launches=.."; c == 0 or count == 0: "none (..) launches=..".
+ * ------------------------------------------------------------------------------------------ */
+#define WS_BN_FOLD_MAX 32
+int ws_bn_fold_fwd(const float* const* h_w, const int64_t* h_outer, const int32_t* h_c, const int64_t* h_inner,
+                   const float* const* h_gamma, const float* const* h_beta, const float* const* h_mean, const float* const* h_var,
+                   const float* h_eps, float* const* h_w_out, float* const* h_t_out, int32_t count, void* stream);
+int ws_bn_fold_bwd(const float* const* h_w, const int64_t* h_outer, const int32_t* h_c, const int64_t* h_inner,
+                   const float* const* h_gamma, const float* const* h_mean, const float* const* h_var, const float* h_eps,
+                   const float* const* h_dw_out, const float* const* h_dt_out, float* const* h_dw, float* const* h_dgamma,
+                   float* const* h_dbeta, int32_t count, void* stream);
+int ws_bn_fold_variant(int32_t backward, int64_t outer, int32_t c, int64_t inner, const void* src, const void* dst, int32_t count,
+                       char* text, int32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,11 @@ class KPFCNN(nn.Module):
         assert drop is None
         c_up = x.shape[1]
         w = unary.mlp.weight
+        if fused.bn_folds(unary.batch_norm, x):
+            # an evaluation-mode BatchNormBlock is in the weight and the bias (both halves of the product share the scale)
+            w, t = fused.folded_operands(w, 0, unary.batch_norm, fused.fold_set(batch), x)
+            y = closest_pool(ops.linear(x, w[:, :c_up]), batch.upsamples[up_block.layer_ind - 1])
+            return ops.matmul_epilogue(skip, w[:, c_up:].t(), bias=t, residual=y, slope=None if unary.no_relu else 0.1)
         y = closest_pool(ops.linear(x, w[:, :c_up]), batch.upsamples[up_block.layer_ind - 1])
         # (`y` is part of the product: in 'points' mode the normalisation follows the whole sum)
         return unary.batch_norm.epilogue(lambda bias, _res, slope: ops.matmul_epilogue(skip, w[:, c_up:].t(), bias=bias, residual=y,
@@ -155,6 +160,15 @@ class KPFCNN(nn.Module):
             batch.activate()     # stream hand-over, scheduling hints and pre-built tables of the batch
         else:
             ops.clear_batch_hints()          # tables, grids and sorted rows belong to one batch
+        # every BatchNormBlock that folds (a 'points' BN in eval()), folded ONCE for this forward and hung on the batch for the
+        # blocks to look up; never kept beyond it: parameters and running buffers change under raw pointers between forwards
+        batch.bn_folds = fused.fold_network(self, batch.features)
+        try:
+            return self._forward(batch, config)
+        finally:
+            batch.bn_folds = None
+
+    def _forward(self, batch, config):
         x = batch.features.clone().detach()
         skips = []
         slots = []
@@ -430,6 +444,13 @@ class KPFCNN_mprm(nn.Module):
             batch.activate()
         else:
             ops.clear_batch_hints()
+        batch.bn_folds = fused.fold_network(self, batch.features)      # (as KPFCNN.forward: one fold per forward, none kept)
+        try:
+            return self._forward(batch, config)
+        finally:
+            batch.bn_folds = None
+
+    def _forward(self, batch, config):
         x = batch.features.clone().detach()
         ele_down = batch.points[2][:, -1].unsqueeze(-1).clone().detach()     # heights at the attention level (:672)
         for block_i, block_op in enumerate(self.encoder_blocks):

@@ -138,11 +138,13 @@ class KPConv(nn.Module):
         k_points = load_kernels(self.radius, self.K, dimension=self.p_dim, fixed=self.fixed_kernel_points)
         return Parameter(torch.tensor(k_points, dtype=torch.float32), requires_grad=False)
 
-    def forward(self, q_pts, s_pts, neighb_inds, x, _bias=None, _slope=None, _out_f32=False, _rows_sorted=None):
+    def forward(self, q_pts, s_pts, neighb_inds, x, _bias=None, _slope=None, _out_f32=False, _rows_sorted=None, _weights=None):
         """`_bias` / `_slope` (used by the blocks of this module only): the BatchNormBlock bias and the
         LeakyReLU that follow the convolution, applied in the epilogue of the contraction GEMM.
         bf16 feature rows (x.dtype bfloat16, BASELINE config 5) run the bf16-row kernels; `_out_f32` keeps the
-        output in f32 (the offsets of a deformable convolution: geometry stays f32)."""
+        output in f32 (the offsets of a deformable convolution: geometry stays f32).  `_weights`: what the contraction
+        uses in place of self.weights (the weights with an evaluation-mode BatchNormBlock folded in, fused.folded_operands)."""
+        weights = self.weights if _weights is None else _weights
         if self.KP_influence not in ops.INFLUENCE:
             raise ValueError('Unknown influence function type (config.KP_influence)')
         if self.aggregation_mode not in ops.AGGREGATION:
@@ -164,7 +166,7 @@ class KPConv(nn.Module):
             wf, self.min_d2 = ops.kpconv_gather_def(x, kp4, q_pts, s_pts, neighb_inds, self.KP_extent, kp_rmax=rmax,
                                                     rows_sorted=rows_sorted)
             return ops.matmul_epilogue(wf.reshape(wf.shape[0], -1),
-                                       self.weights.reshape(self.K * self.in_channels, self.out_channels),
+                                       weights.reshape(self.K * self.in_channels, self.out_channels),
                                        bias=_bias, slope=_slope, out_f32=_out_f32)
         if self.deformable:
             # offsets from a rigid KPConv on the same neighbourhood (blocks.py:244-267)
@@ -188,10 +190,10 @@ class KPConv(nn.Module):
         # dense contraction over (kernel point, input channel): blocks.py:370-374
         if wf.dtype == torch.bfloat16:
             return ops.matmul_epilogue(wf.reshape(wf.shape[0], -1),
-                                       self.weights.reshape(self.K * self.in_channels, self.out_channels),
+                                       weights.reshape(self.K * self.in_channels, self.out_channels),
                                        bias=_bias, slope=_slope, out_f32=_out_f32)
         return ops.matmul_epilogue(wf.reshape(wf.shape[0], -1),
-                                   self.weights.reshape(self.K * self.in_channels, self.out_channels),
+                                   weights.reshape(self.K * self.in_channels, self.out_channels),
                                    bias=_bias, slope=_slope)
 
     def __repr__(self):
@@ -268,6 +270,12 @@ class BatchNormBlock(nn.Module):
         """whether the BatchNorm1d runs on [N, C] inputs ('points' mode with use_bn)"""
         return self.use_bn and self.mode == 'points'
 
+    def foldable(self):
+        """whether this block, following a product, goes into that product's weight and bias (ops.bn_fold): it is live, its
+        BatchNorm1d is in eval() -- the module's own flag, so a user who freezes some of them gets exactly those -- and neither
+        WEASAL_BN_KERNELS nor WEASAL_BN_FOLD is 0"""
+        return self.live() and not self.batch_norm.training and ops.BN_KERNELS and ops.BN_FOLD
+
     def epilogue(self, product, residual=None, slope=None):
         """what follows a block's product: `product(bias, residual, slope)` is the caller's GEMM / KPConv with this epilogue.
         Reference mode and bias blocks: one call with epilogue_bias(), the residual and the slope.  Live: the raw product,
@@ -317,32 +325,32 @@ class UnaryBlock(nn.Module):
             self.leaky_relu = nn.LeakyReLU(0.1)
         self.out_f32 = False     # bf16 feature rows only: keep this block's output in f32 (the logits)
 
-    def forward(self, x, batch=None):
-        return self.forward_fused(x, batch=batch)
+    def forward(self, x, batch=None, folds=None):
+        return self.forward_fused(x, batch=batch, folds=folds)
 
-    def forward_fused(self, x, residual=None, slope_override=None, batch=None):
+    def forward_fused(self, x, residual=None, slope_override=None, batch=None, folds=None):
         """mlp -> batch_norm(identity | + bias) [-> + residual] -> LeakyReLU, in one GEMM.
         slope_override: activation applied although the block itself has no_relu (the residual sum of
-        ResnetBottleneckBlock, blocks.py:709)."""
+        ResnetBottleneckBlock, blocks.py:709).  A BatchNormBlock that folds (fused.bn_folds) hands over the folded weight and
+        bias -- from `folds` or the batch's set when the network's forward made them, made here otherwise -- and the block goes
+        down its ordinary float32 path."""
         slope = slope_override if slope_override is not None else (None if self.no_relu else 0.1)
-        if self.batch_norm.live():
+        weight, bias = fused.folded_operands(self.mlp.weight, 0, self.batch_norm, folds if folds is not None else fused.fold_set(batch), x)
+        if self.batch_norm.live() and not fused.bn_folds(self.batch_norm, x):
             # 'points' mode: the raw product, then the normalisation with the residual and the slope (no gate links)
             return self.batch_norm.epilogue(lambda bias, res, sl: ops.matmul_epilogue(x, self.mlp.weight.t(), bias=bias, residual=res,
                                                                                      slope=sl), residual, slope)
         if x.dtype == torch.bfloat16:
-            return ops.matmul_epilogue(x, self.mlp.weight.t(), bias=self.batch_norm.epilogue_bias(), residual=residual,
-                                       slope=slope, out_f32=self.out_f32)
+            return ops.matmul_epilogue(x, weight.t(), bias=bias, residual=residual, slope=slope, out_f32=self.out_f32)
         # gate links (fused.GateLink) when the caller has set them up on the batch (KPFCNN's head): float32 kernel path only
         links = None
         linked = batch is not None and residual is None and (getattr(batch, "gate_link_in", None) is not None
                                                              or getattr(batch, "gate_link_out", None) is not None)
         if linked and ops.matmul_epilogue is _MATMUL_EPILOGUE and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32:
-            from . import fused
             links = fused.linear_links(batch, x, True)
         if links is None:
-            return ops.matmul_epilogue(x, self.mlp.weight.t(), bias=self.batch_norm.epilogue_bias(), residual=residual, slope=slope)
-        out = ops.matmul_epilogue(x, self.mlp.weight.t(), bias=self.batch_norm.epilogue_bias(), residual=residual,
-                                  slope=slope, links=links)
+            return ops.matmul_epilogue(x, weight.t(), bias=bias, residual=residual, slope=slope)
+        out = ops.matmul_epilogue(x, weight.t(), bias=bias, residual=residual, slope=slope, links=links)
         fused.linear_links_done(batch, links, out, slope is not None)
         return out
 
@@ -366,6 +374,15 @@ def _make_kpconv(block_name, in_dim, out_dim, radius, config):
                   modulated=config.modulated)
 
 
+def _conv_bn(conv, bn_block, q_pts, s_pts, inds, x, batch):
+    """LeakyReLU(0.1)(bn_block(conv(x))), operator by operator: the bias and the slope ride in the contraction's epilogue; a
+    BatchNormBlock that folds goes into the contraction's weights and bias, one that is live otherwise follows the raw product"""
+    if fused.bn_folds(bn_block, x):
+        w, t = fused.folded_operands(conv.weights, 2, bn_block, fused.fold_set(batch), x)
+        return conv(q_pts, s_pts, inds, x, _bias=t, _slope=0.1, _weights=w)
+    return bn_block.epilogue(lambda bias, _res, slope: conv(q_pts, s_pts, inds, x, _bias=bias, _slope=slope), None, 0.1)
+
+
 class SimpleBlock(nn.Module):
     """KPConv(in -> out//2) -> BN -> LeakyReLU (blocks.py:510-564)"""
 
@@ -385,7 +402,7 @@ class SimpleBlock(nn.Module):
         q_pts, s_pts, inds = _layer_geometry(self.block_name, self.layer_ind, batch)
         if fused.kpblock_eligible(self, x):
             return fused.simple_block(self, x, batch, q_pts, s_pts, inds)      # one C call each way (csrc/blocks.hip)
-        return self.batch_norm.epilogue(lambda bias, _res, slope: self.KPConv(q_pts, s_pts, inds, x, _bias=bias, _slope=slope), None, 0.1)
+        return _conv_bn(self.KPConv, self.batch_norm, q_pts, s_pts, inds, x, batch)
 
 
 class SimpleBlock2(nn.Module):
@@ -407,7 +424,7 @@ class SimpleBlock2(nn.Module):
         q_pts, s_pts, inds = _layer_geometry(self.block_name, self.layer_ind, batch)
         if fused.kpblock_eligible(self, x):
             return fused.simple_block(self, x, batch, q_pts, s_pts, inds)      # one C call each way (csrc/blocks.hip)
-        return self.batch_norm.epilogue(lambda bias, _res, slope: self.KPConv(q_pts, s_pts, inds, x, _bias=bias, _slope=slope), None, 0.1)
+        return _conv_bn(self.KPConv, self.batch_norm, q_pts, s_pts, inds, x, batch)
 
 
 class ResnetBottleneckBlock(nn.Module):
@@ -438,11 +455,13 @@ class ResnetBottleneckBlock(nn.Module):
         q_pts, s_pts, inds = _layer_geometry(self.block_name, self.layer_ind, batch)
         if fused.kpblock_eligible(self, features):
             return fused.resnetb_block(self, features, batch, q_pts, s_pts, inds)   # one C call each way (csrc/blocks.hip)
-        x = self.unary1(features)
-        x = self.batch_norm_conv.epilogue(lambda bias, _res, slope: self.KPConv(q_pts, s_pts, inds, x, _bias=bias, _slope=slope), None, 0.1)
+        folds = fused.fold_set(batch)
+        x = self.unary1(features, folds=folds) if isinstance(self.unary1, UnaryBlock) else self.unary1(features)
+        x = _conv_bn(self.KPConv, self.batch_norm_conv, q_pts, s_pts, inds, x, batch)
         shortcut = max_pool(features, inds) if 'strided' in self.block_name else features
+        shortcut = self.unary_shortcut(shortcut, folds=folds) if isinstance(self.unary_shortcut, UnaryBlock) else self.unary_shortcut(shortcut)
         # leaky_relu(unary2(x) + unary_shortcut(shortcut)) with the sum and the activation in unary2's GEMM
-        return self.unary2.forward_fused(x, residual=self.unary_shortcut(shortcut), slope_override=0.1)
+        return self.unary2.forward_fused(x, residual=shortcut, slope_override=0.1, folds=folds)
 
 
 class GlobalAverageBlock(nn.Module):
@@ -525,7 +544,7 @@ class spatial_att(nn.Module):
 
     def forward(self, features, batch):
         features = self.simple1(features, batch)
-        q, k, v = self.unary1(features), self.unary2(features), self.unary3(features)
+        q, k, v = self.unary1(features, batch), self.unary2(features, batch), self.unary3(features, batch)
         spans = _per_cloud(_layer_lengths(batch, self.layer_ind))
         if _att_kernels(len(spans), q, k, v) and ops.sphere_attention_supported(q.shape[1], v.shape[1], len(spans), q.shape[0], v):
             x, xn = ops.sphere_attention(q, k, v, [b - a for a, b in spans])
@@ -561,7 +580,7 @@ class channel_att(nn.Module):
 
     def forward(self, features, batch):
         features = self.simple1(features, batch)
-        x1, x2 = self.unary1(features), self.unary2(features)
+        x1, x2 = self.unary1(features, batch), self.unary2(features, batch)
         spans = _per_cloud(_layer_lengths(batch, self.layer_ind))
         if _att_kernels(len(spans), x1, x2, features) and ops.channel_attention_supported(features.shape[1]):
             x = ops.channel_attention(x1, x2, features, [b - a for a, b in spans], True)
@@ -645,7 +664,7 @@ class ele_att(nn.Module):
         else:
             centre_z = h
         ele_f = torch.cat((h, h + centre_z), dim=1)
-        query, key = self.unary1(ele_f), self.unary2(ele_f)
+        query, key = self.unary1(ele_f, batch), self.unary2(ele_f, batch)
         if _att_kernels(len(spans), query, key, features) and ops.channel_attention_supported(features.shape[1]) \
                 and query.shape == features.shape:
             x = ops.channel_attention(query, key, features, [b - a for a, b in spans], False)

@@ -8,9 +8,11 @@ launches its 6-7 kernels from C, its backward one call that launches 10-14; the 
 to add with separate kernels (shortcut + main branch into the block input) are residual operands of GEMM epilogues.
 Same arithmetic as weasal_amd.blocks' operator-by-operator path (same kernels, same order inside every sum), which
 stays in place for everything these calls do not cover (deformable / modulated KPConv, bf16 rows, non-linear influence,
-CPU oracle mode, and any block one of whose BatchNormBlocks is live -- `batch_norm_mode = 'points'` with use_batch_norm:
-every route of this module declines then -- block calls, decoder steps, gate links, skip slots, the forward-only fused
-layer -- and the operators run the raw products followed by ops.batch_norm_act).
+CPU oracle mode, and any block one of whose BatchNormBlocks is live -- `batch_norm_mode = 'points'` with use_batch_norm --
+and does not fold: every route of this module declines then -- block calls, decoder steps, gate links, skip slots, the
+forward-only fused layer -- and the operators run the raw products followed by ops.batch_norm_act.  A live BatchNormBlock
+whose BatchNorm1d is in eval() folds (`folded_operands`: the running statistics go into the weight and a bias, ops.bn_fold),
+and a block all of whose live sites fold runs the routes of this module as a bias block does).
 """
 import ctypes as C
 import os
@@ -346,25 +348,86 @@ def _geometry(conv, q_pts, s_pts, inds, strided):
 MIN_ROWS = int(os.environ.get("WEASAL_FUSED_MIN_ROWS", "0"))
 
 
-def bn_live(*modules):
-    """whether a BatchNormBlock of these blocks (their own `batch_norm` / `batch_norm_conv`, or their unary blocks') runs
-    over the points: the block calls know the identity and the bias only"""
+def _bn_sites(*modules):
+    """the BatchNormBlocks of these blocks: their own `batch_norm` / `batch_norm_conv` and their unary blocks'"""
     for m in modules:
         for name in ("batch_norm", "batch_norm_conv", "unary1", "unary2", "unary_shortcut"):
             sub = getattr(m, name, None)
             if sub is None:
                 continue
             if hasattr(sub, "live"):
-                if sub.live():
-                    return True
-            elif hasattr(sub, "batch_norm") and hasattr(sub.batch_norm, "live") and sub.batch_norm.live():
-                return True
-    return False
+                yield sub
+            elif hasattr(sub, "batch_norm") and hasattr(sub.batch_norm, "live"):
+                yield sub.batch_norm
+
+
+def bn_live(*modules):
+    """whether a BatchNormBlock of these blocks (their own `batch_norm` / `batch_norm_conv`, or their unary blocks') runs
+    over the points: the block calls know the identity and the bias only"""
+    return any(site.live() for site in _bn_sites(*modules))
+
+
+def bn_declines(*modules):
+    """whether a BatchNormBlock of these blocks keeps them off the fused routes: one that runs over the points and cannot be
+    folded into its product (batch statistics, WEASAL_BN_FOLD=0 or WEASAL_BN_KERNELS=0).  A block all of whose live sites are
+    foldable runs the reference-mode launch sequence with folded weights and biases."""
+    return any(site.live() and not site.foldable() for site in _bn_sites(*modules))
+
+
+def bn_folds(bn_block, x):
+    """whether the product in front of `bn_block`, applied to the rows x, takes folded operands: the site is foldable and x is
+    a float32 device tensor on the kernel path (CPU tensors -- oracle.kpconv_ref.cpu_reference_mode -- and bf16 rows never)"""
+    return (bn_block.foldable() and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32
+            and ops.kpconv_gather is _KPCONV_GATHER)
+
+
+def fold_set(batch):
+    """the folded operands the network's forward hung on the batch ({id(BatchNormBlock): (w, t)}), or None"""
+    return getattr(batch, "bn_folds", None) if batch is not None else None
+
+
+def folded_operands(weight, axis, bn_block, folds, x):
+    """(weight, bias) of a product followed by `bn_block`: the folded pair for a site that folds (from `folds` when the
+    network's forward made it there, made on the spot otherwise), and (weight, epilogue_bias()) as ever otherwise"""
+    if not bn_folds(bn_block, x):
+        return weight, bn_block.epilogue_bias()
+    if folds is not None:
+        pair = folds.get(id(bn_block))
+        if pair is not None:
+            return pair
+    return ops.bn_fold([(weight, axis, bn_block.batch_norm)])[0]
+
+
+def network_sites(net):
+    """[(weight, channel axis, BatchNormBlock)] of every product of `net` that a BatchNormBlock follows (the module tree is
+    static: scanned once; the list holds modules and parameters, never a folded value)"""
+    sites = getattr(net, "_bn_fold_sites", None)
+    if sites is None:
+        sites = []
+        for m in net.modules():
+            if hasattr(m, "mlp") and hasattr(m, "batch_norm") and hasattr(m.batch_norm, "live"):
+                sites.append((m.mlp.weight, 0, m.batch_norm))
+            elif hasattr(m, "KPConv"):
+                bn = getattr(m, "batch_norm_conv", None) or getattr(m, "batch_norm", None)
+                if bn is not None and hasattr(bn, "live"):
+                    sites.append((m.KPConv.weights, 2, bn))
+        net._bn_fold_sites = sites
+    return sites
+
+
+def fold_network(net, x):
+    """ONE ops.bn_fold over every site of `net` that folds for the rows x -> {id(BatchNormBlock): (w, t)}, or None when there
+    is none (reference mode, batch statistics, a switch at 0, CPU tensors): then nothing is launched"""
+    todo = [(w, axis, bn) for w, axis, bn in network_sites(net) if bn_folds(bn, x)]
+    if not todo:
+        return None
+    pairs = ops.bn_fold([(w, axis, bn.batch_norm) for w, axis, bn in todo])
+    return {id(bn): pair for (_, _, bn), pair in zip(todo, pairs)}
 
 
 def kpblock_eligible(block, x):
     conv = block.KPConv
-    if not _conv_ok(conv, x) or x.shape[0] < MIN_ROWS or bn_live(block):
+    if not _conv_ok(conv, x) or x.shape[0] < MIN_ROWS or bn_declines(block):
         return False
     dims = [conv.out_channels]
     if hasattr(block, "unary2"):
@@ -383,7 +446,8 @@ def simple_block(block, x, batch, q_pts, s_pts, inds):
         g.table = ops.transposed_table(g.inds, g.s_pts.shape[0])
     if getattr(batch, "skip_slot", None) is None:      # (a skip tensor has a second reader this block knows nothing about)
         g.link_in = _link_in(batch, x)
-    out = _KPBlockFn.apply(x, None, None, conv.weights, block.batch_norm.epilogue_bias(), None, None, None, None, g)
+    wk, bk = folded_operands(conv.weights, 2, block.batch_norm, fold_set(batch), x)
+    out = _KPBlockFn.apply(x, None, None, wk, bk, None, None, None, None, g)
     g.link_out = _link_out(batch, out)
     return out
 
@@ -406,12 +470,12 @@ def resnetb_block(block, x, batch, q_pts, s_pts, inds):
     if getattr(batch, "skip_slot", None) is None or g.skip_slot is not None:
         # (a skip tensor has a second reader: only with its slot armed does this block get to see that share)
         g.link_in = _link_in(batch, x)
-    out = _KPBlockFn.apply(x,
-                           u1.mlp.weight if u1 is not None else None, u1.batch_norm.epilogue_bias() if u1 is not None else None,
-                           conv.weights, block.batch_norm_conv.epilogue_bias(),
-                           block.unary2.mlp.weight, block.unary2.batch_norm.epilogue_bias(),
-                           us.mlp.weight if us is not None else None, us.batch_norm.epilogue_bias() if us is not None else None,
-                           g)
+    folds = fold_set(batch)
+    w1, b1 = folded_operands(u1.mlp.weight, 0, u1.batch_norm, folds, x) if u1 is not None else (None, None)
+    wk, bk = folded_operands(conv.weights, 2, block.batch_norm_conv, folds, x)
+    w2, b2 = folded_operands(block.unary2.mlp.weight, 0, block.unary2.batch_norm, folds, x)
+    wsc, bsc = folded_operands(us.mlp.weight, 0, us.batch_norm, folds, x) if us is not None else (None, None)
+    out = _KPBlockFn.apply(x, w1, b1, wk, bk, w2, b2, wsc, bsc, g)
     g.link_out = _link_out(batch, out)
     return out
 
@@ -483,7 +547,7 @@ class _UpUnaryFn(torch.autograd.Function):
 def upunary_eligible(x, skip, unary):
     return (FUSED_BLOCKS and x.is_cuda and x.dtype == torch.float32 and skip.dtype == torch.float32
             and ops.kpconv_gather is _KPCONV_GATHER and x.shape[1] % 32 == 0 and skip.shape[1] % 32 == 0
-            and unary.out_dim % 32 == 0 and x.shape[0] > 0 and skip.shape[0] >= MIN_ROWS and not bn_live(unary))
+            and unary.out_dim % 32 == 0 and x.shape[0] > 0 and skip.shape[0] >= MIN_ROWS and not bn_declines(unary))
 
 
 def upunary(x, skip, unary, ups, drop=None, batch=None):
@@ -492,17 +556,18 @@ def upunary(x, skip, unary, ups, drop=None, batch=None):
     ups = ops._as_index(ups)
     table = ops.col0_table(ups, x.shape[0]) if torch.is_grad_enabled() else None      # (only the backward reads it)
     links = [_link_in(batch, x) if batch is not None else None, None]
+    w, b = folded_operands(unary.mlp.weight, 0, unary.batch_norm, fold_set(batch), x)
     if drop is not None:
         if unary.no_relu:
             raise _lib.WeasalHipError("upunary: the fused dropout follows the unary's LeakyReLU")
-        out = _UpUnaryFn.apply(x, skip, unary.mlp.weight, unary.batch_norm.epilogue_bias(), ups, table, True, float(drop[0]), int(drop[1]),
+        out = _UpUnaryFn.apply(x, skip, w, b, ups, table, True, float(drop[0]), int(drop[1]),
                                links)
         if batch is not None:
             links[1] = _link_out(batch, out)
             if links[1] is not None:
                 links[1].drop = (float(drop[0]), int(drop[1]))
         return out
-    out = _UpUnaryFn.apply(x, skip, unary.mlp.weight, unary.batch_norm.epilogue_bias(), ups, table, not unary.no_relu, 0.0, 0, links)
+    out = _UpUnaryFn.apply(x, skip, w, b, ups, table, not unary.no_relu, 0.0, 0, links)
     if batch is not None:
         links[1] = _link_out(batch, out, relu=not unary.no_relu)
     return out

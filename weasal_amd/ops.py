@@ -1966,3 +1966,130 @@ def batch_norm_act(y, bn_module, residual=None, slope=None):
     if bn_module.training and y.shape[0] == 1:
         raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(y.shape),))
     return _BatchNormAct.apply(y, bn_module.weight, bn_module.bias, residual, bn_module, slope)
+
+
+# ------------------------------------------------------------------------------------------------
+# evaluation-mode batch normalisation folded into the weights in front of it (weasal_amd/csrc/bn_fold.hip)
+# ------------------------------------------------------------------------------------------------
+BN_FOLD = os.environ.get("WEASAL_BN_FOLD", "1") != "0"       # A/B switch: 0 = a 'points' BN in eval() runs ws_bn_fwd's evaluation launch after the raw product
+bn_fold_launches = 0      # (tests, tools) library launches of ops.bn_fold so far, both directions
+
+
+def _fold_col(kind, values):
+    """a ctypes column for the C entries: `kind` None = device pointers (ints, or None for NULL), else a typed array"""
+    import ctypes as C
+    return ((C.c_void_p if kind is None else kind) * len(values))(*values)
+
+
+def _fold_ptrs(tensors):
+    return [None if t is None else t.data_ptr() for t in tensors]
+
+
+class _BnFold(torch.autograd.Function):
+    """(w_0, gamma_0, beta_0, w_1, ...) -> (w_out_0, t_0, w_out_1, ...) over ws_bn_fold_fwd / _bwd: one launch sequence each way.
+    The outputs are views of ONE buffer (segments of whole 16 bytes): the host work per forward is one allocation and the
+    pointer table, which matters in the forward-only passes, where the fold stands in front of the first launch."""
+
+    @staticmethod
+    def forward(ctx, meta, *tensors):
+        import ctypes as C
+        global bn_fold_launches
+        lib = _lib.lib()
+        ws, gammas, betas = tensors[0::3], tensors[1::3], tensors[2::3]
+        shapes, bns = meta
+        n = len(ws)
+        wc = [w if w.is_contiguous() else w.contiguous() for w in ws]
+        sizes = []
+        for (outer, c, inner) in shapes:
+            sizes += [(outer * c * inner + 3) & ~3, (c + 3) & ~3]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=ws[0].device)
+        base, offs, o = flat.data_ptr(), [], 0
+        for sz in sizes:
+            offs.append(base + 4 * o)
+            o += sz
+        means, variances = [bn.running_mean for bn in bns], [bn.running_var for bn in bns]
+        eps = [float(bn.eps) for bn in bns]
+        dims = (_fold_col(C.c_int64, [s[0] for s in shapes]), _fold_col(C.c_int32, [s[1] for s in shapes]),
+                _fold_col(C.c_int64, [s[2] for s in shapes]))
+        before = lib.ws_launch_count()
+        check(lib.ws_bn_fold_fwd(_fold_col(None, _fold_ptrs(wc)), *dims, _fold_col(None, _fold_ptrs(gammas)), _fold_col(None, _fold_ptrs(betas)),
+                                 _fold_col(None, _fold_ptrs(means)), _fold_col(None, _fold_ptrs(variances)), _fold_col(C.c_float, eps),
+                                 _fold_col(None, offs[0::2]), _fold_col(None, offs[1::2]), n, current_stream()))
+        bn_fold_launches += lib.ws_launch_count() - before
+        ctx.set_materialize_grads(False)
+        if any(ctx.needs_input_grad):
+            ctx.shapes, ctx.eps, ctx.n = shapes, eps, n
+            ctx.save_for_backward(*wc, *gammas, *means, *variances)
+        out = []
+        for i, seg in enumerate(flat.split(sizes)):
+            w = ws[i // 2]
+            if i % 2 == 0:
+                out.append((seg if seg.numel() == w.numel() else seg[:w.numel()]).view(w.shape))
+            else:
+                out.append(seg if seg.numel() == shapes[i // 2][1] else seg[:shapes[i // 2][1]])
+        return tuple(out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        import ctypes as C
+        global bn_fold_launches
+        lib = _lib.lib()
+        n, shapes = ctx.n, ctx.shapes
+        saved = ctx.saved_tensors
+        ws, gammas, means, variances = saved[:n], saved[n:2 * n], saved[2 * n:3 * n], saved[3 * n:]
+        need = ctx.needs_input_grad
+        dw_out = [None if g is None else g.contiguous() for g in grads[0::2]]
+        dt_out = [None if g is None else g.contiguous() for g in grads[1::2]]
+        dw = [torch.empty_like(ws[i]) if need[1 + 3 * i] else None for i in range(n)]
+        dgamma = [torch.empty_like(gammas[i]) if need[2 + 3 * i] else None for i in range(n)]
+        dbeta = [torch.empty_like(gammas[i]) if need[3 + 3 * i] else None for i in range(n)]
+        before = lib.ws_launch_count()
+        check(lib.ws_bn_fold_bwd(_fold_col(None, _fold_ptrs(ws)), _fold_col(C.c_int64, [s[0] for s in shapes]),
+                                 _fold_col(C.c_int32, [s[1] for s in shapes]), _fold_col(C.c_int64, [s[2] for s in shapes]),
+                                 _fold_col(None, _fold_ptrs(gammas)), _fold_col(None, _fold_ptrs(means)), _fold_col(None, _fold_ptrs(variances)),
+                                 _fold_col(C.c_float, ctx.eps), _fold_col(None, _fold_ptrs(dw_out)), _fold_col(None, _fold_ptrs(dt_out)),
+                                 _fold_col(None, _fold_ptrs(dw)), _fold_col(None, _fold_ptrs(dgamma)), _fold_col(None, _fold_ptrs(dbeta)), n,
+                                 current_stream()))
+        bn_fold_launches += lib.ws_launch_count() - before
+        out = [None]
+        for i in range(n):
+            out += [dw[i], dgamma[i], dbeta[i]]
+        return tuple(out)
+
+
+def bn_fold(sites):
+    """[(weight, channel_axis, nn.BatchNorm1d)] -> [(w_folded, t)]: the BatchNorm1d in evaluation (running statistics, read at
+    this call) folded into the weight of the product in front of it, act(BN(x W^T) + r) = act(x w_folded^T + t + r) with
+    w_folded = a * W along `channel_axis`, a = gamma / sqrt(running_var + eps), t = beta - running_mean * a.  The whole list is
+    ONE autograd node: one launch of ws_bn_fold_fwd per WS_BN_FOLD_MAX sites, likewise backward; gradients reach the weights
+    and gamma / beta where they require them, never the running buffers.  Nothing is cached: parameters and buffers are
+    updated through raw pointers elsewhere, so a folded weight is good for the forward it was made in.  Float32 device
+    tensors only (ValueError otherwise)."""
+    if not sites:
+        return []
+    tensors, shapes, bns = [], [], []
+    f32 = torch.float32
+    for w, axis, bn in sites:
+        gamma, beta, mean, var = bn.weight, bn.bias, bn.running_mean, bn.running_var
+        if gamma is None or mean is None:
+            raise ValueError("bn_fold: the module must be affine and track running statistics")
+        if not (w.is_cuda and gamma.is_cuda and beta.is_cuda and mean.is_cuda and var.is_cuda):
+            _need_cuda(w, gamma, beta, mean, var)
+        if not (w.dtype == f32 and gamma.dtype == f32 and beta.dtype == f32 and mean.dtype == f32 and var.dtype == f32):
+            raise ValueError("bn_fold: float32 tensors only (got %s)" % w.dtype)
+        shape = w.shape
+        axis = axis % len(shape)
+        c = shape[axis]
+        if c != bn.num_features:
+            raise ValueError("bn_fold: axis %d of the weight has %d channels, the BatchNorm1d %d" % (axis, c, bn.num_features))
+        outer = inner = 1
+        for d in shape[:axis]:
+            outer *= d
+        for d in shape[axis + 1:]:
+            inner *= d
+        shapes.append((outer, c, inner))
+        tensors += [w, gamma, beta]
+        bns.append(bn)
+    out = _BnFold.apply((shapes, bns), *tensors)
+    return [(out[2 * i], out[2 * i + 1]) for i in range(len(bns))]

@@ -1404,6 +1404,53 @@ int ws_bn_variant(int32_t backward, int64_t n, int32_t c, const void* y, int64_t
                   int32_t act, char* text, int32_t cap);
 
 /* ------------------------------------------------------------------------------------------
+ * The same normalisation with batch statistics over the rows of SEVERAL ranks (data parallelism; what torch users know as
+ * SyncBatchNorm): the training launch sequence of ws_bn_fwd / ws_bn_bwd cut at the two points where a collective goes.
+ * The library moves nothing between ranks: the caller gathers the records (ops.batch_norm_act(group=...): one
+ * all_gather_into_tensor per direction).  Every rank runs the two finishing entries on the same gathered bytes, merging
+ * in rank order, so every rank gets the same bits in save_mean, save_rstd, the running statistics and num_batches_tracked.
+ * A rank may hold no row (n == 0).  Conventions, pitches, alignment rule and plan as above.
+ *
+ * ws_bn_moments: this rank's record [5, c] float32 = n, sum, hi, lo, M2 per column (mean = hi + lo for merging, the
+ *   centred M2; see batchnorm.hip), the chunks merged in the order ws_bn_fwd merges them.  n == 0: the record is zeroed, no
+ *   kernel.  The count is a float: n up to 2^24 per rank (WS_ERR_UNSUPPORTED beyond).  scratch: ws_bn_scratch_bytes(n, c).
+ *   Two launches.
+ * ws_bn_moments_finish: records [world, 5, c] (rank order) -> N = the integer sum of the counts, written to *n_global (one
+ *   int64 on the device, read by ws_bn_bwd_apply); the ranks merged with Chan's formula in rank order; save_mean = sum / N,
+ *   save_rstd = 1 / sqrt(M2 / N + eps); running_mean / running_var as ws_bn_fwd with the factor N / (N - 1);
+ *   *num_batches_tracked += 1.  The count lives on the device, so the refusal of a single row cannot be a status: with
+ *   N < 2 ONLY *n_global is written, and a caller that cannot rule N == 1 out by its own n >= 2 reads it and refuses
+ *   (ops does, on every rank, after the gather).  One launch.
+ * ws_bn_apply: out = act((y - mean) * rstd * gamma + beta [+ residual]) with the given mean and rstd: the kernel ws_bn_fwd
+ *   launches last in training.  n == 0: nothing.  One launch.
+ * ws_bn_bwd_sums: this rank's record [2, c] = column sums of dz, of dz * xhat (dz as in ws_bn_bwd, xhat from save_mean /
+ *   save_rstd): the LOCAL dbeta and dgamma, which are what autograd gets (gradient averaging then treats them like every
+ *   other gradient).  n == 0: zeroed, no kernel.  Two launches.
+ * ws_bn_bwd_apply: records [world, 2, c] added in rank order -> S1, S2; dy = gamma rstd (dz - S1 / N - xhat S2 / N) with N
+ *   read from *n_global; dresidual = dz unless NULL.  n == 0: nothing.  scratch: ws_bn_scratch_bytes(n, c).  Two launches.
+ * With world == 1 the sequence gives the bits of ws_bn_fwd / ws_bn_bwd.
+ * ws_bn_sync_variant: the branch of one of them, from the same plan function; nothing is read or launched.  stage: 0
+ *   moments, 1 moments_finish, 2 apply, 3 bwd_sums, 4 bwd_apply (residual / ldr stand for dresidual / lddr).  Text:
+ *   "kernels<V=..> vector|scalar rows=.. chunks=.. depth=.. tile=.. lanes=.. ctiles=.. world=.. residual=0|1 act=0|1";
+ *   stage 1: "bn_sync_finish_kernel world=.. blocks=..".
+ * ------------------------------------------------------------------------------------------ */
+int ws_bn_moments(const float* y, int64_t n, int32_t c, int64_t ldy, float* record, void* scratch, void* stream);
+int ws_bn_moments_finish(const float* records, int32_t world, int32_t c, float eps, float momentum, float* running_mean,
+                         float* running_var, int64_t* num_batches_tracked, float* save_mean, float* save_rstd, int64_t* n_global,
+                         void* stream);
+int ws_bn_apply(const float* y, int64_t n, int32_t c, int64_t ldy, const float* mean, const float* rstd, const float* gamma,
+                const float* beta, const float* residual, int64_t ldr, int32_t act, float slope, float* out, int64_t ldo, void* stream);
+int ws_bn_bwd_sums(const float* dout, int64_t lddo, const float* out, int64_t ldo, const float* y, int64_t ldy, int64_t n, int32_t c,
+                   const float* save_mean, const float* save_rstd, int32_t act, float slope, float* record, void* scratch, void* stream);
+int ws_bn_bwd_apply(const float* dout, int64_t lddo, const float* out, int64_t ldo, const float* y, int64_t ldy, int64_t n, int32_t c,
+                    const float* gamma, const float* save_mean, const float* save_rstd, const float* records, int32_t world,
+                    const int64_t* n_global, int32_t act, float slope, float* dy, int64_t lddy, float* dresidual, int64_t lddr,
+                    void* scratch, void* stream);
+int ws_bn_sync_variant(int32_t stage, int64_t n, int32_t c, int32_t world, const void* y, int64_t ldy, const void* out, int64_t ldo,
+                       const void* residual, int64_t ldr, const void* dout, int64_t lddo, const void* dy, int64_t lddy, int32_t act,
+                       char* text, int32_t cap);
+
+/* ------------------------------------------------------------------------------------------
  * Evaluation-mode batch normalisation folded into the product in front of it: weasal_amd/csrc/bn_fold.hip.  With running
  * statistics BN is an affine map per output channel, rstd = 1 / sqrt(running_var + eps), a = gamma rstd,
  * t = beta - running_mean a, and act(BN(x W^T) + residual) = act(x (a (.)rows W)^T + t + residual): the bias / residual /

@@ -254,6 +254,7 @@ class BatchNormBlock(nn.Module):
         self.use_bn = use_bn
         self.in_dim = in_dim
         self.mode = mode
+        self.sync_group = None      # dp.sync_batch_norm: the process group whose ranks share this block's batch statistics
         if self.use_bn:
             self.batch_norm = nn.BatchNorm1d(in_dim, momentum=bn_momentum)
         else:
@@ -286,7 +287,11 @@ class BatchNormBlock(nn.Module):
 
     def normalise(self, y, residual=None, slope=None):
         """act(batch_norm(y) [+ residual]) on [N, C]: ops.batch_norm_act for float32 device rows; CPU tensors
-        (oracle.kpconv_ref.cpu_reference_mode), other dtypes and WEASAL_BN_KERNELS=0 run the framework's operators"""
+        (oracle.kpconv_ref.cpu_reference_mode), other dtypes and WEASAL_BN_KERNELS=0 run the framework's operators.  With a
+        `sync_group` (dp.sync_batch_norm) a training call takes its statistics from the rows of all ranks of the group,
+        whatever the device (ops.batch_norm_act(group=...)); evaluation reads the buffers, which are then equal on all ranks"""
+        if self.sync_group is not None and self.batch_norm.training and y.dtype == torch.float32 and y.dim() == 2:
+            return ops.batch_norm_act(y, self.batch_norm, residual=residual, slope=slope, group=self.sync_group)
         if ops.BN_KERNELS and y.is_cuda and y.dtype == torch.float32 and y.dim() == 2 \
                 and (residual is None or (residual.is_cuda and residual.dtype == torch.float32)):
             return ops.batch_norm_act(y, self.batch_norm, residual=residual, slope=slope)

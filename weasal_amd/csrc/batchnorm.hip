@@ -6,6 +6,19 @@
 //   ws_bn_bwd   bn_reduce_bwd_kernel -> bn_finish_bwd_kernel -> bn_apply_bwd_kernel
 //   ws_bn_variant   the reporter; bn_plan is the ONE plan function of the three entries
 //
+// The same launch sequence CUT where a collective goes, for batch statistics over the rows of several ranks (the caller
+// gathers the records between the entries; ops.batch_norm_act(group=...)):
+//   ws_bn_moments          bn_stats_kernel -> bn_local_fwd_kernel: this rank's record [5, c] = n, sum, hi, lo, M2
+//   ws_bn_moments_finish   bn_sync_finish_kernel: the gathered records [world, 5, c] merged in rank order, save_mean / save_rstd,
+//                          the running statistics with the GLOBAL count, which it also leaves on the device (n_global)
+//   ws_bn_apply            bn_apply_fwd_kernel with a given mean and rstd
+//   ws_bn_bwd_sums         bn_reduce_bwd_kernel -> bn_finish_bwd_kernel: this rank's record [2, c] = sum dz, sum dz * xhat
+//   ws_bn_bwd_apply        bn_sync_sums_kernel (the gathered records [world, 2, c] added in rank order) -> bn_apply_bwd_kernel
+//                          with the global sums and the global count
+//   ws_bn_sync_variant     their reporter, over the same bn_plan
+// With one rank the cut sequence gives the bits of ws_bn_fwd / ws_bn_bwd: the local finish merges the chunks in the order of
+// bn_finish_fwd_kernel, and a merge over one record is that record.
+//
 // Streaming kernels: threads = column groups (V = 4 floats, 16 bytes per lane, or V = 1) x row lanes; a workgroup owns
 // a chunk of rows and a tile of up to 64 column groups.  The variance is CENTRED: a thread holds up to BN_T rows in
 // registers, takes their mean, then the squares of the differences from it -- two passes over registers, one over memory --
@@ -435,7 +448,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_bwd_kernel(const float* _
                                                                   const float* __restrict__ gamma, const float* __restrict__ dgamma,
                                                                   const float* __restrict__ dbeta, int training, int act, float slope,
                                                                   float* __restrict__ dy, int64_t lddy, float* __restrict__ dres,
-                                                                  int64_t lddr)
+                                                                  int64_t lddr, const long long* __restrict__ n_stat)
 {
     typedef float vec_t __attribute__((ext_vector_type(V)));
     const int t = threadIdx.x, rl = t / per, cgl = t % per;
@@ -445,7 +458,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_bwd_kernel(const float* _
     const int64_t beg = (int64_t)blockIdx.x * rows;
     const int64_t end = beg + rows < n ? beg + rows : n;
     float mu[V], rs[V], gr[V], k1[V], k2[V];
-    const float fn = (float)n;
+    const float fn = (float)(n_stat ? (int64_t)*n_stat : n);      // the rows the sums run over: this call's, or all ranks'
 #pragma unroll
     for (int e = 0; e < V; ++e) {
         const int cc = col + e < c ? col + e : c - 1;
@@ -484,6 +497,106 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_bwd_kernel(const float* _
             }
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// the cut sequence.  bn_local_fwd_kernel is bn_finish_fwd_kernel up to the merged moments of a column -- the same run per lane,
+// the same tree, so the same bits -- and stops there: the record of this rank's rows.  (Its own copy of the tree, not a
+// function shared with bn_finish_fwd_kernel: that kernel's code object stays what it was.)
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(BN_THREADS) void bn_local_fwd_kernel(const float* __restrict__ psum, const float* __restrict__ phi,
+                                                                  const float* __restrict__ plo, const float* __restrict__ pm2,
+                                                                  int64_t n, int c, int64_t rows, int chunks, float* __restrict__ rec)
+{
+    __shared__ float sn[BN_THREADS], ss[BN_THREADS], sh[BN_THREADS], sl[BN_THREADS], s2[BN_THREADS];
+    const int t = threadIdx.x, cl = t % BN_FC, lane = t / BN_FC;
+    const int col = (int)blockIdx.x * BN_FC + cl;
+    const int run = (chunks + BN_FL - 1) / BN_FL;
+    Moments a{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (col < c) {
+        const int jend = (lane + 1) * run < chunks ? (lane + 1) * run : chunks;
+        for (int j = lane * run; j < jend; ++j) {
+            const int64_t left = n - (int64_t)j * rows;
+            const Moments b{(float)(left < rows ? left : rows), psum[(int64_t)j * c + col], phi[(int64_t)j * c + col],
+                            plo[(int64_t)j * c + col], pm2[(int64_t)j * c + col]};
+            a = bn_merge(a, b);
+        }
+    }
+    sn[t] = a.n;
+    ss[t] = a.sum;
+    sh[t] = a.hi;
+    sl[t] = a.lo;
+    s2[t] = a.m2;
+    for (int s = BN_FL / 2; s >= 1; s >>= 1) {
+        __syncthreads();
+        if (lane < s) {
+            const int o = t + s * BN_FC;
+            const Moments m = bn_merge(Moments{sn[t], ss[t], sh[t], sl[t], s2[t]}, Moments{sn[o], ss[o], sh[o], sl[o], s2[o]});
+            sn[t] = m.n;
+            ss[t] = m.sum;
+            sh[t] = m.hi;
+            sl[t] = m.lo;
+            s2[t] = m.m2;
+        }
+    }
+    if (lane == 0 && col < c) {
+        rec[col] = (float)n;      // exact: the entry takes up to 2^24 rows
+        rec[(int64_t)c + col] = ss[t];
+        rec[(int64_t)2 * c + col] = sh[t];
+        rec[(int64_t)3 * c + col] = sl[t];
+        rec[(int64_t)4 * c + col] = s2[t];
+    }
+}
+
+// the records of all ranks [world, 5, c] -> save_mean / save_rstd and the running statistics of the union of their rows; a
+// thread owns a column and merges the ranks in rank order.  N, the global count, is the integer sum of the records' counts; it
+// goes to *n_global, and with N < 2 nothing else is written
+__global__ __launch_bounds__(BN_THREADS) void bn_sync_finish_kernel(const float* __restrict__ rec, int world, int c, float eps,
+                                                                    float momentum, float* __restrict__ running_mean,
+                                                                    float* __restrict__ running_var, long long* __restrict__ nbt,
+                                                                    float* __restrict__ save_mean, float* __restrict__ save_rstd,
+                                                                    long long* __restrict__ n_global)
+{
+    const int col = (int)blockIdx.x * BN_THREADS + (int)threadIdx.x;
+    if (col >= c) return;
+    Moments a{rec[col], rec[(int64_t)c + col], rec[(int64_t)2 * c + col], rec[(int64_t)3 * c + col], rec[(int64_t)4 * c + col]};
+    long long total = (long long)a.n;
+    for (int r = 1; r < world; ++r) {
+        const float* q = rec + (int64_t)r * 5 * c;
+        const Moments b{q[col], q[(int64_t)c + col], q[(int64_t)2 * c + col], q[(int64_t)3 * c + col], q[(int64_t)4 * c + col]};
+        total += (long long)b.n;
+        a = bn_merge(a, b);
+    }
+    if (total >= 2) {
+        const float fn = (float)total;
+        const float mean = a.sum / fn, var = a.m2 / fn;
+        save_mean[col] = mean;
+        save_rstd[col] = 1.0f / sqrtf(var + eps);
+        running_mean[col] = (1.0f - momentum) * running_mean[col] + momentum * mean;
+        running_var[col] = (1.0f - momentum) * running_var[col] + momentum * (var * (fn / (fn - 1.0f)));
+    }
+    if (col == 0) {
+        *n_global = total;
+        if (total >= 2 && nbt) *nbt += 1;
+    }
+}
+
+// the backward records of all ranks [world, 2, c] added in rank order -> sums [2, c]: sum dz, sum dz * xhat over all rows
+__global__ __launch_bounds__(BN_THREADS) void bn_sync_sums_kernel(const float* __restrict__ rec, int world, int c,
+                                                                  float* __restrict__ sums)
+{
+    const int col = (int)blockIdx.x * BN_THREADS + (int)threadIdx.x;
+    if (col >= c) return;
+    float a1 = rec[col], a2 = rec[(int64_t)c + col];
+    for (int r = 1; r < world; ++r) {
+        a1 += rec[(int64_t)r * 2 * c + col];
+        a2 += rec[(int64_t)r * 2 * c + c + col];
+    }
+    sums[col] = a1;
+    sums[(int64_t)c + col] = a2;
+}
+
+constexpr int64_t BN_SYNC_MAX_N = (int64_t)1 << 24;      // a record's count is a float: exact up to here
+constexpr int BN_SYNC_MAX_WORLD = 1 << 16;
 
 int bn_check_shape(int64_t n, int32_t c)
 {
@@ -586,10 +699,10 @@ int ws_bn_bwd(const float* dout, int64_t lddo, const float* out, int64_t ldo, co
     WS_LAUNCH_CHECK();
     if (p.v == 4)
         bn_apply_bwd_kernel<4><<<grid, BN_THREADS, 0, st>>>(dout, lddo, out, ldo, y, ldy, n, c, p.per, p.lanes, p.rows, mean, stat2, isvar, eps,
-                                                            gamma, dgamma, dbeta, training ? 1 : 0, act, slope, dy, lddy, dresidual, lddr);
+                                                            gamma, dgamma, dbeta, training ? 1 : 0, act, slope, dy, lddy, dresidual, lddr, nullptr);
     else
         bn_apply_bwd_kernel<1><<<grid, BN_THREADS, 0, st>>>(dout, lddo, out, ldo, y, ldy, n, c, p.per, p.lanes, p.rows, mean, stat2, isvar, eps,
-                                                            gamma, dgamma, dbeta, training ? 1 : 0, act, slope, dy, lddy, dresidual, lddr);
+                                                            gamma, dgamma, dbeta, training ? 1 : 0, act, slope, dy, lddy, dresidual, lddr, nullptr);
     WS_LAUNCH_CHECK();
     return WS_OK;
 }
@@ -621,6 +734,173 @@ int ws_bn_variant(int32_t backward, int64_t n, int32_t c, const void* y, int64_t
     snprintf(text, (size_t)cap, "%s<V=%d> %s rows=%lld chunks=%d depth=%d tile=%d lanes=%d ctiles=%d mode=%s residual=%d act=%d", kernels,
              p.v, p.v == 4 ? "vector" : "scalar", (long long)p.rows, p.chunks, merges ? p.depth : 0, p.per * p.v, p.lanes, p.ctiles,
              training ? "training" : "evaluation", residual ? 1 : 0, act ? 1 : 0);
+    return WS_OK;
+}
+
+int ws_bn_moments(const float* y, int64_t n, int32_t c, int64_t ldy, float* record, void* scratch, void* stream)
+{
+    if (int rc = bn_check_shape(n, c)) return rc;
+    WS_REQUIRE(ldy >= c, "row stride below the width %d", c);
+    WS_REQUIRE(record, "NULL argument");
+    if (n > BN_SYNC_MAX_N)
+        return ws_fail(WS_ERR_UNSUPPORTED, "a record counts up to %lld rows of one rank (got %lld)", (long long)BN_SYNC_MAX_N, (long long)n);
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        WS_HIP(hipMemsetAsync(record, 0, sizeof(float) * 5 * (size_t)c, st));
+        return WS_OK;
+    }
+    WS_REQUIRE(y && scratch, "NULL argument");
+    const void* ptrs[1] = {y};
+    const int64_t lds[1] = {ldy};
+    const BnPlan p = bn_plan(n, c, ptrs, lds, 1);
+    const dim3 grid(p.chunks, p.ctiles);
+    float* psum = (float*)scratch;
+    float* phi = psum + (int64_t)p.chunks * c;
+    float* plo = phi + (int64_t)p.chunks * c;
+    float* pm2 = plo + (int64_t)p.chunks * c;
+    if (p.v == 4) bn_stats_kernel<4><<<grid, BN_THREADS, 0, st>>>(y, n, c, ldy, p.per, p.lanes, p.rows, psum, phi, plo, pm2);
+    else bn_stats_kernel<1><<<grid, BN_THREADS, 0, st>>>(y, n, c, ldy, p.per, p.lanes, p.rows, psum, phi, plo, pm2);
+    WS_LAUNCH_CHECK();
+    bn_local_fwd_kernel<<<p.fin_blocks, BN_THREADS, 0, st>>>(psum, phi, plo, pm2, n, c, p.rows, p.chunks, record);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+int ws_bn_moments_finish(const float* records, int32_t world, int32_t c, float eps, float momentum, float* running_mean,
+                         float* running_var, int64_t* num_batches_tracked, float* save_mean, float* save_rstd, int64_t* n_global,
+                         void* stream)
+{
+    if (int rc = bn_check_shape(0, c)) return rc;
+    WS_REQUIRE(world >= 1 && world <= BN_SYNC_MAX_WORLD, "world %d: 1 .. %d ranks", world, BN_SYNC_MAX_WORLD);
+    WS_REQUIRE(eps >= 0.0f, "negative eps");
+    WS_REQUIRE(records && running_mean && running_var && save_mean && save_rstd && n_global, "NULL argument");
+    bn_sync_finish_kernel<<<(c + BN_THREADS - 1) / BN_THREADS, BN_THREADS, 0, (hipStream_t)stream>>>(
+        records, world, c, eps, momentum, running_mean, running_var, (long long*)num_batches_tracked, save_mean, save_rstd,
+        (long long*)n_global);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+int ws_bn_apply(const float* y, int64_t n, int32_t c, int64_t ldy, const float* mean, const float* rstd, const float* gamma,
+                const float* beta, const float* residual, int64_t ldr, int32_t act, float slope, float* out, int64_t ldo, void* stream)
+{
+    if (int rc = bn_check_shape(n, c)) return rc;
+    WS_REQUIRE(ldy >= c && ldo >= c && (!residual || ldr >= c), "row stride below the width %d", c);
+    WS_REQUIRE(act == 0 || act == 1, "act %d: 0 none, 1 LeakyReLU", act);
+    if (n == 0) return WS_OK;
+    WS_REQUIRE(y && mean && rstd && gamma && beta && out, "NULL argument");
+    const void* ptrs[3] = {y, out, residual};
+    const int64_t lds[3] = {ldy, ldo, ldr};
+    const BnPlan p = bn_plan(n, c, ptrs, lds, 3);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(p.chunks, p.ctiles);
+    if (p.v == 4)
+        bn_apply_fwd_kernel<4><<<grid, BN_THREADS, 0, st>>>(y, n, c, ldy, p.per, p.lanes, p.rows, mean, rstd, 0, 0.0f, gamma, beta, residual,
+                                                            ldr, act, slope, out, ldo);
+    else
+        bn_apply_fwd_kernel<1><<<grid, BN_THREADS, 0, st>>>(y, n, c, ldy, p.per, p.lanes, p.rows, mean, rstd, 0, 0.0f, gamma, beta, residual,
+                                                            ldr, act, slope, out, ldo);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+int ws_bn_bwd_sums(const float* dout, int64_t lddo, const float* out, int64_t ldo, const float* y, int64_t ldy, int64_t n, int32_t c,
+                   const float* save_mean, const float* save_rstd, int32_t act, float slope, float* record, void* scratch, void* stream)
+{
+    if (int rc = bn_check_shape(n, c)) return rc;
+    WS_REQUIRE(lddo >= c && ldy >= c && (!act || ldo >= c), "row stride below the width %d", c);
+    WS_REQUIRE(act == 0 || act == 1, "act %d: 0 none, 1 LeakyReLU", act);
+    WS_REQUIRE(record, "NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        WS_HIP(hipMemsetAsync(record, 0, sizeof(float) * 2 * (size_t)c, st));
+        return WS_OK;
+    }
+    WS_REQUIRE(dout && y && save_mean && save_rstd && scratch && (!act || out), "NULL argument");
+    const void* ptrs[3] = {dout, act ? out : nullptr, y};
+    const int64_t lds[3] = {lddo, ldo, ldy};
+    const BnPlan p = bn_plan(n, c, ptrs, lds, 3);
+    const dim3 grid(p.chunks, p.ctiles);
+    float* p1 = (float*)scratch;
+    float* p2 = p1 + (int64_t)p.chunks * c;
+    if (p.v == 4)
+        bn_reduce_bwd_kernel<4><<<grid, BN_THREADS, 0, st>>>(dout, lddo, out, ldo, y, ldy, n, c, p.per, p.lanes, p.rows, save_mean, save_rstd,
+                                                             0, 0.0f, act, slope, p1, p2);
+    else
+        bn_reduce_bwd_kernel<1><<<grid, BN_THREADS, 0, st>>>(dout, lddo, out, ldo, y, ldy, n, c, p.per, p.lanes, p.rows, save_mean, save_rstd,
+                                                             0, 0.0f, act, slope, p1, p2);
+    WS_LAUNCH_CHECK();
+    bn_finish_bwd_kernel<<<p.fin_blocks, BN_THREADS, 0, st>>>(p1, p2, c, p.chunks, record + c, record);      // (dgamma, dbeta)
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+int ws_bn_bwd_apply(const float* dout, int64_t lddo, const float* out, int64_t ldo, const float* y, int64_t ldy, int64_t n, int32_t c,
+                    const float* gamma, const float* save_mean, const float* save_rstd, const float* records, int32_t world,
+                    const int64_t* n_global, int32_t act, float slope, float* dy, int64_t lddy, float* dresidual, int64_t lddr,
+                    void* scratch, void* stream)
+{
+    if (int rc = bn_check_shape(n, c)) return rc;
+    WS_REQUIRE(lddo >= c && ldy >= c && lddy >= c && (!act || ldo >= c) && (!dresidual || lddr >= c), "row stride below the width %d", c);
+    WS_REQUIRE(act == 0 || act == 1, "act %d: 0 none, 1 LeakyReLU", act);
+    WS_REQUIRE(world >= 1 && world <= BN_SYNC_MAX_WORLD, "world %d: 1 .. %d ranks", world, BN_SYNC_MAX_WORLD);
+    if (n == 0) return WS_OK;
+    WS_REQUIRE(dout && y && gamma && save_mean && save_rstd && records && n_global && dy && scratch && (!act || out), "NULL argument");
+    const void* ptrs[5] = {dout, act ? out : nullptr, y, dy, dresidual};
+    const int64_t lds[5] = {lddo, ldo, ldy, lddy, lddr};
+    const BnPlan p = bn_plan(n, c, ptrs, lds, 5);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(p.chunks, p.ctiles);
+    float* sums = (float*)scratch;      // [2, c]: within ws_bn_scratch_bytes for any n >= 1
+    bn_sync_sums_kernel<<<(c + BN_THREADS - 1) / BN_THREADS, BN_THREADS, 0, st>>>(records, world, c, sums);
+    WS_LAUNCH_CHECK();
+    const long long* ng = (const long long*)n_global;
+    if (p.v == 4)
+        bn_apply_bwd_kernel<4><<<grid, BN_THREADS, 0, st>>>(dout, lddo, out, ldo, y, ldy, n, c, p.per, p.lanes, p.rows, save_mean, save_rstd, 0,
+                                                            0.0f, gamma, sums + c, sums, 1, act, slope, dy, lddy, dresidual, lddr, ng);
+    else
+        bn_apply_bwd_kernel<1><<<grid, BN_THREADS, 0, st>>>(dout, lddo, out, ldo, y, ldy, n, c, p.per, p.lanes, p.rows, save_mean, save_rstd, 0,
+                                                            0.0f, gamma, sums + c, sums, 1, act, slope, dy, lddy, dresidual, lddr, ng);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+int ws_bn_sync_variant(int32_t stage, int64_t n, int32_t c, int32_t world, const void* y, int64_t ldy, const void* out, int64_t ldo,
+                       const void* residual, int64_t ldr, const void* dout, int64_t lddo, const void* dy, int64_t lddy, int32_t act,
+                       char* text, int32_t cap)
+{
+    WS_REQUIRE(text && cap > 0, "bad argument");
+    WS_REQUIRE(stage >= 0 && stage <= 4, "stage %d: 0 moments, 1 moments_finish, 2 apply, 3 bwd_sums, 4 bwd_apply", stage);
+    if (int rc = bn_check_shape(n, c)) return rc;
+    if (stage == 1) {
+        WS_REQUIRE(world >= 1 && world <= BN_SYNC_MAX_WORLD, "world %d: 1 .. %d ranks", world, BN_SYNC_MAX_WORLD);
+        snprintf(text, (size_t)cap, "bn_sync_finish_kernel world=%d blocks=%d", world, (c + BN_THREADS - 1) / BN_THREADS);
+        return WS_OK;
+    }
+    if (n == 0) {
+        snprintf(text, (size_t)cap, "%s (n == 0)", stage == 0 || stage == 3 ? "memset" : "none");
+        return WS_OK;
+    }
+    const void* ptrs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int64_t lds[5] = {0, 0, 0, 0, 0};
+    const char* kernels = "";
+    if (stage == 0) {
+        if (n > BN_SYNC_MAX_N) return ws_fail(WS_ERR_UNSUPPORTED, "a record counts up to %lld rows of one rank", (long long)BN_SYNC_MAX_N);
+        ptrs[0] = y, lds[0] = ldy;
+        kernels = "bn_stats_kernel+bn_local_fwd_kernel";
+    } else if (stage == 2) {
+        ptrs[0] = y, lds[0] = ldy, ptrs[1] = out, lds[1] = ldo, ptrs[2] = residual, lds[2] = ldr;
+        kernels = "bn_apply_fwd_kernel";
+    } else {
+        ptrs[0] = dout, lds[0] = lddo, ptrs[1] = act ? out : nullptr, lds[1] = ldo, ptrs[2] = y, lds[2] = ldy;
+        if (stage == 4) ptrs[3] = dy, lds[3] = lddy, ptrs[4] = residual, lds[4] = ldr;
+        kernels = stage == 3 ? "bn_reduce_bwd_kernel+bn_finish_bwd_kernel" : "bn_sync_sums_kernel+bn_apply_bwd_kernel";
+    }
+    const BnPlan p = bn_plan(n, c, ptrs, lds, 5);
+    const bool merges = stage == 0 || stage == 3;
+    snprintf(text, (size_t)cap, "%s<V=%d> %s rows=%lld chunks=%d depth=%d tile=%d lanes=%d ctiles=%d world=%d residual=%d act=%d", kernels,
+             p.v, p.v == 4 ? "vector" : "scalar", (long long)p.rows, p.chunks, merges ? p.depth : 0, p.per * p.v, p.lanes, p.ctiles, world,
+             residual ? 1 : 0, act ? 1 : 0);
     return WS_OK;
 }
 

@@ -3,8 +3,15 @@ per rank, ONE flat gradient all-reduce per step (RCCL over xGMI via torch.distri
 "nccl" == RCCL on ROCm; "gloo" on CPU for tests).
 
 The reference is single-process (utils/trainer_PseudoLabel.py:90-94); the exchange sits between
-``loss.backward()`` and ``clip_grad_value_`` (:214-218).  BatchNorm is an identity on this path
-(models/blocks.py:453-463), so gradients are the only cross-rank state.
+``loss.backward()`` and ``clip_grad_value_`` (:214-218).  In the reference configuration BatchNorm is an identity on this
+path (models/blocks.py:453-463), and gradients are the only cross-rank state.
+
+With ``batch_norm_mode = 'points'`` that no longer holds: every live BatchNormBlock has batch statistics and running
+buffers.  Left alone, each rank normalises with the statistics of its own spheres, the buffers drift apart from the first
+step (``broadcast_parameters`` aligns them once) and rank 0's checkpoint holds one replica's statistics.
+``sync_batch_norm`` (configuration key ``batch_norm_sync``) makes the statistics those of the rows of ALL ranks and the
+buffers bit-identical on every rank: two small all-gathers per BN site per step, on a process group of BN's own.  It adds
+one requirement: all ranks run the same sequence of BN sites per step -- a rank that skips a batch stalls the others.
 """
 import os
 
@@ -35,6 +42,37 @@ def broadcast_parameters(net, src=0):
     if dist.is_initialized() and dist.get_world_size() > 1:
         for t in list(net.parameters()) + list(net.buffers()):
             dist.broadcast(t.data, src)
+
+
+def sync_batch_norm(net, group=None):
+    """Batch statistics over the rows of every rank, for each live BatchNormBlock of ``net`` ('points' mode with
+    use_batch_norm): what torch users know as SyncBatchNorm (ops.batch_norm_act(group=...)).  -> the number of blocks marked.
+
+    group None: a new process group over all ranks (``dist.new_group()``, so EVERY rank must make this call).  BN's
+    collectives run inside forward and backward; the overlapped ``GradSync(buckets > 1)`` issues its all-reduces from
+    autograd hooks during the same backward, and on a group of their own BN's gathers do not depend on how the two interleave.
+    Without an initialised process group, or with one rank, nothing is marked and 0 is returned.  ``unsync_batch_norm`` undoes it."""
+    from .blocks import BatchNormBlock
+    if not (dist.is_available() and dist.is_initialized()):
+        return 0
+    live = [m for m in net.modules() if isinstance(m, BatchNormBlock) and m.live()]
+    if group is None:
+        if dist.get_world_size() < 2:
+            return 0
+        group = dist.new_group()
+    elif dist.get_world_size(group) < 2:
+        return 0
+    for m in live:
+        m.sync_group = group
+    return len(live)
+
+
+def unsync_batch_norm(net):
+    """every BatchNormBlock of ``net`` back to the statistics of its own rank's rows"""
+    from .blocks import BatchNormBlock
+    for m in net.modules():
+        if isinstance(m, BatchNormBlock):
+            m.sync_group = None
 
 
 class GradSync:

@@ -186,6 +186,10 @@ class ModelTrainer:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.device = torch.device(device)
         net.to(self.device)
+        # `batch_norm_sync` (absent = off): the live BatchNormBlocks take their batch statistics over all ranks
+        if grad_sync is not None and getattr(config, 'batch_norm_sync', False):
+            from . import dp
+            dp.sync_batch_norm(net)
         self.optimizer = make_optimizer(net, config)
         if chkp_path is not None:         # :100-112
             checkpoint = torch.load(chkp_path, map_location=self.device, weights_only=True)

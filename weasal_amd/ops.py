@@ -1945,13 +1945,164 @@ class _BatchNormAct(torch.autograd.Function):
         return dy, dgamma, dbeta, dres, None, None
 
 
-def batch_norm_act(y, bn_module, residual=None, slope=None):
+def _bn_gather(record, group, world):
+    """[world, *record.shape]: every rank's record, in rank order -- ONE collective.  gloo gathers host tensors only: device
+    records of a gloo group (several ranks rehearsing on one card) go through the host"""
+    import torch.distributed as dist
+    flat = (world * record.shape[0],) + tuple(record.shape[1:])      # the concatenated form: the one every backend takes
+    out = torch.empty(flat, dtype=record.dtype, device=record.device)
+    if record.is_cuda and dist.get_backend(group) == "gloo":
+        host = torch.empty(flat, dtype=record.dtype)
+        dist.all_gather_into_tensor(host, record.cpu(), group=group)
+        out.copy_(host)
+    else:
+        dist.all_gather_into_tensor(out, record.contiguous(), group=group)
+    return out.view((world,) + tuple(record.shape))
+
+
+def _bn_single_row():
+    return ValueError("Expected more than 1 value per channel when training, got 1 row over all ranks of the group")
+
+
+class _BatchNormActSync(torch.autograd.Function):
+    """training BN with the statistics of ALL ranks of `group`: ws_bn_moments, all-gather, ws_bn_moments_finish, ws_bn_apply;
+    backward ws_bn_bwd_sums, all-gather, ws_bn_bwd_apply.  One collective per direction; the row counts travel in the records"""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, residual, bn, slope, group, world):
+        lib = _lib.lib()
+        yc, ldy = _rows_f32(y)
+        n, c = int(yc.shape[0]), int(yc.shape[1])
+        rc, ldr = _rows_f32(residual) if residual is not None else (None, 0)
+        act, sl = _act_args(slope)
+        dev = y.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        record = torch.empty((5, c), **f32)
+        scratch = _scratch(lib.ws_bn_scratch_bytes(n, c), dev)
+        check(lib.ws_bn_moments(ptr(yc), n, c, ldy, ptr(record), ptr(scratch), current_stream()))
+        records = _bn_gather(record, group, world)
+        save_mean, save_rstd = torch.empty((c,), **f32), torch.empty((c,), **f32)
+        n_global = torch.empty((1,), dtype=torch.int64, device=dev)
+        check(lib.ws_bn_moments_finish(ptr(records), world, c, float(bn.eps), float(bn.momentum), ptr(bn.running_mean),
+                                       ptr(bn.running_var), ptr(bn.num_batches_tracked), ptr(save_mean), ptr(save_rstd), ptr(n_global),
+                                       current_stream()))
+        # with N < 2 the kernel wrote n_global alone; a rank with two rows of its own knows N >= 2 without reading anything back,
+        # and N == 1 means n <= 1 on every rank: all of them read, all of them raise, after the collective
+        if n <= 1 and int(n_global) == 1:
+            raise _bn_single_row()
+        out = torch.empty((n, c), **f32)
+        g, b = _f32c(gamma), _f32c(beta)
+        check(lib.ws_bn_apply(ptr(yc), n, c, ldy, ptr(save_mean), ptr(save_rstd), ptr(g), ptr(b), ptr(rc), ldr, act, sl, ptr(out), c,
+                              current_stream()))
+        ctx.save_for_backward(yc, out, save_mean, save_rstd, g, n_global)
+        ctx.group, ctx.world, ctx.act, ctx.ldy, ctx.has_res = group, world, (act, sl), ldy, residual is not None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        lib = _lib.lib()
+        yc, out, save_mean, save_rstd, g, n_global = ctx.saved_tensors
+        n, c = int(yc.shape[0]), int(yc.shape[1])
+        d, lddo = _rows_f32(dout)
+        dev = yc.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        act, sl = ctx.act
+        record = torch.empty((2, c), **f32)
+        scratch = _scratch(lib.ws_bn_scratch_bytes(n, c), dev)
+        check(lib.ws_bn_bwd_sums(ptr(d), lddo, ptr(out), c, ptr(yc), ctx.ldy, n, c, ptr(save_mean), ptr(save_rstd), act, sl, ptr(record),
+                                 ptr(scratch), current_stream()))
+        records = _bn_gather(record, ctx.group, ctx.world)
+        dy = torch.empty((n, c), **f32)
+        dres = torch.empty((n, c), **f32) if (ctx.has_res and ctx.needs_input_grad[3]) else None
+        check(lib.ws_bn_bwd_apply(ptr(d), lddo, ptr(out), c, ptr(yc), ctx.ldy, n, c, ptr(g), ptr(save_mean), ptr(save_rstd), ptr(records),
+                                  ctx.world, ptr(n_global), act, sl, ptr(dy), c, ptr(dres), c, ptr(scratch), current_stream()))
+        return dy, record[1], record[0], dres, None, None, None, None      # this rank's own sums: GradSync averages them
+
+
+class _BatchNormActSyncTorch(torch.autograd.Function):
+    """the protocol of _BatchNormActSync stated in torch operators, over the same group: what CPU tensors
+    (oracle.kpconv_ref.cpu_reference_mode) and WEASAL_BN_KERNELS=0 run, and the protocol's reference"""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, residual, bn, slope, group, world):
+        y = y.detach()
+        n, c = y.shape
+        record = torch.zeros((5, c), dtype=torch.float32, device=y.device)
+        if n:
+            mean = y.sum(0) / n
+            record[0], record[1], record[2], record[4] = float(n), y.sum(0), mean, ((y - mean) ** 2).sum(0)
+        records = _bn_gather(record, group, world)
+        cnt, tot, hi, lo, m2 = (records[0, k].clone() for k in range(5))
+        for r in range(1, world):      # Chan's merge in rank order; the union keeps the first non-empty rank's hi
+            bn_, bs, bh, bl, b2 = (records[r, k] for k in range(5))
+            if float(bn_[0]) == 0.0:
+                continue
+            if float(cnt[0]) == 0.0:
+                cnt, tot, hi, lo, m2 = (t.clone() for t in (bn_, bs, bh, bl, b2))
+                continue
+            both = cnt + bn_
+            d, f = (bh - hi) + (bl - lo), bn_ / both
+            tot, lo, m2, cnt = tot + bs, lo + d * f, m2 + b2 + d * d * (cnt * f), both
+        total = cnt[:1].clone()      # the global row count, kept on the device
+        if n <= 1 and int(total) == 1:
+            raise _bn_single_row()
+        if n == 0 and int(total) == 0:
+            ctx.empty = True
+            return y.new_empty((0, c))
+        ctx.empty = False
+        mean, var = tot / total, m2 / total
+        rstd = 1.0 / torch.sqrt(var + bn.eps)
+        m = float(bn.momentum)
+        bn.running_mean.mul_(1.0 - m).add_(m * mean)
+        bn.running_var.mul_(1.0 - m).add_(m * (var * (total / (total - 1.0))))
+        bn.num_batches_tracked += 1
+        g = gamma.detach()
+        z = (y - mean) * rstd * g + beta.detach()
+        if residual is not None:
+            z = z + residual.detach()
+        out = z if slope is None else torch.where(z > 0, z, z * slope)
+        ctx.save_for_backward(y, out, mean, rstd, g, total)
+        ctx.group, ctx.world, ctx.slope, ctx.has_res = group, world, slope, residual is not None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        if ctx.empty:
+            return dout, None, None, (dout if ctx.needs_input_grad[3] else None), None, None, None, None
+        y, out, mean, rstd, g, total = ctx.saved_tensors
+        dz = dout if ctx.slope is None else torch.where(out > 0, dout, dout * ctx.slope)
+        xhat = (y - mean) * rstd
+        record = torch.stack((dz.sum(0), (dz * xhat).sum(0)))
+        records = _bn_gather(record, ctx.group, ctx.world)
+        s = records[0].clone()
+        for r in range(1, ctx.world):
+            s = s + records[r]
+        dy = g * rstd * (dz - s[0] / total - xhat * (s[1] / total))
+        dres = dz if (ctx.has_res and ctx.needs_input_grad[3]) else None
+        return dy, record[1], record[0], dres, None, None, None, None
+
+
+def batch_norm_act(y, bn_module, residual=None, slope=None, group=None):
     """act(BatchNorm1d(y) [+ residual]) for y [N, C] float32 on the device: what `nn.BatchNorm1d` (bn_module: its weight, bias,
     running buffers, eps, momentum and training flag, all read at this call) followed by `+ residual` and LeakyReLU(slope)
     give, up to float32 summation order (models/blocks.py:430-470 as KPConv runs it).  Training updates the running buffers
     and num_batches_tracked on the device.  Differentiable once in y, weight, bias and residual; N = 0 returns an empty
     tensor and touches nothing.  Refused: CPU tensors, bf16 rows, momentum None, training with a single row (ValueError, as
-    torch raises)."""
+    torch raises).
+
+    group: a torch.distributed process group.  With two or more ranks and the module in training, the batch statistics are
+    those of the rows of ALL ranks (SyncBatchNorm): one all-gather of a [5, C] record in the forward, one of a [2, C] record
+    in the backward, and save_* / running_* / num_batches_tracked come out bit-identical on every rank.  Every rank of the
+    group must make the call (a rank may bring N = 0 rows); a single row over all ranks raises on every rank, after the
+    gather.  weight.grad / bias.grad get this rank's own sums.  CPU tensors (and WEASAL_BN_KERNELS=0) run the same protocol
+    in torch operators.  None, a group of one rank, and evaluation: the path above, bit for bit."""
+    if group is not None and bn_module.training:
+        import torch.distributed as dist
+        world = dist.get_world_size(group) if dist.is_initialized() else 1
+        if world >= 2:
+            return _batch_norm_act_sync(y, bn_module, residual, slope, group, world)
     _need_cuda(y, residual, bn_module.weight)
     if y.dim() != 2 or y.shape[1] != bn_module.num_features:
         raise ValueError("batch_norm_act: y must be [N, %d]" % bn_module.num_features)
@@ -1966,6 +2117,21 @@ def batch_norm_act(y, bn_module, residual=None, slope=None):
     if bn_module.training and y.shape[0] == 1:
         raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(y.shape),))
     return _BatchNormAct.apply(y, bn_module.weight, bn_module.bias, residual, bn_module, slope)
+
+
+def _batch_norm_act_sync(y, bn_module, residual, slope, group, world):
+    if y.dim() != 2 or y.shape[1] != bn_module.num_features:
+        raise ValueError("batch_norm_act: y must be [N, %d]" % bn_module.num_features)
+    if y.dtype != torch.float32 or (residual is not None and residual.dtype != torch.float32):
+        raise ValueError("batch_norm_act: float32 rows only (got %s)" % y.dtype)
+    if residual is not None and (residual.shape != y.shape or residual.device != y.device):
+        raise ValueError("batch_norm_act: residual must have the shape and the device of y")
+    if bn_module.momentum is None:
+        raise ValueError("batch_norm_act: momentum=None (cumulative average) is not supported")
+    if bn_module.weight is None or bn_module.running_mean is None:
+        raise ValueError("batch_norm_act: the module must be affine and track running statistics")
+    fn = _BatchNormActSync if (y.is_cuda and BN_KERNELS) else _BatchNormActSyncTorch
+    return fn.apply(y, bn_module.weight, bn_module.bias, residual, bn_module, slope, group, world)
 
 
 # ------------------------------------------------------------------------------------------------

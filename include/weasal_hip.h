@@ -847,6 +847,37 @@ int ws_topk_select(const double* score, int64_t n, const int64_t* h_exclude, int
                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Selection with a minimum spacing between new labels ("spaced greedy"; opt-in, no counterpart in the reference).
+ * Contract: walk the candidates in the priority order of ws_topk_select (used ids removed, descending score, ascending
+ *   index among equal scores, -0.0 == +0.0, NaN below every number); accept a candidate iff no point accepted before it
+ *   and no used point blocks it; stop after k acceptances; ids = the accepted ids in acceptance order.  q blocks p iff
+ *   d2 < s * s, strict, with the coordinates widened to float64, d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded
+ *   on its own, and s * s formed in float64 from the float64 spacing s.  No float atomics; every run gives the same ids.
+ * ws_al_spaced_select: coords [n, 3] on the device, float32 (coords_f64 == 0) or float64 (!= 0).  cand [m]: device ids
+ *   ALREADY in priority order with the used ids removed (a prefix, or a further run, of ws_topk_select's output).
+ *   h_used [n_used]: the used ids, a HOST array like ws_topk_select's h_exclude, any order, duplicates allowed; it is
+ *   uploaded from pageable memory, so the call waits for its predecessors on the stream.  state: two int64 words on the
+ *   device, { acceptances so far, candidates consumed }; ids [k] on the device.  resume == 0 starts a walk (state is
+ *   zeroed); resume != 0 continues the walk recorded in state and ids [0, state[0]) with the further run `cand` and keeps
+ *   what was accepted.  The caller reads state[0]: below k means the run is used up (state[1] has grown by m).
+ *   Two launches (the blocking pass over the used points, skipped when n_used == 0, and the walk of one workgroup whose
+ *   accepted coordinates live in LDS) and nothing is read back.  scratch: ws_al_spaced_scratch_bytes(m, n_used, k).
+ *   Found before the device is touched: spacing not finite or <= 0, a negative size, a NULL required pointer, a used id
+ *   outside [0, n): WS_ERR_INVALID; k > WS_AL_SPACED_MAX_K: WS_ERR_UNSUPPORTED.  k == 0 or m == 0: WS_OK and nothing is
+ *   launched (resume == 0 with a non-NULL state zeroes it).  An id of cand outside [0, n) is never dereferenced or accepted.
+ * ws_al_spaced_variant: the launches a call takes, from the launcher's own plan; nothing is read or launched.  Text:
+ *   "spaced_used_kernel<float|double> blocks=.. tiles=..|no used pass + spaced_walk_kernel<float|double> chunks=..
+ *   tail=<m mod 1024> resume=0|1", or "none (k == 0|m == 0)".
+ * ------------------------------------------------------------------------------------------ */
+#define WS_AL_SPACED_MAX_K 6144
+int64_t ws_al_spaced_scratch_bytes(int64_t m, int64_t n_used, int64_t k);
+int ws_al_spaced_select(const void* coords, int32_t coords_f64, int64_t n, const int64_t* cand, int64_t m, const int64_t* h_used,
+                        int64_t n_used, double spacing, int64_t k, int64_t* ids, int64_t* state, int32_t resume, void* scratch,
+                        void* stream);
+int ws_al_spaced_variant(int32_t coords_f64, int64_t n, int64_t m, int64_t n_used, double spacing, int64_t k, int32_t resume,
+                         char* text, int32_t cap);
+
+/* ------------------------------------------------------------------------------------------
  * Pseudo-label refinement on the votes of a pass over the training clouds (csrc/refine.hip): pseudoLabel_refinement.py.
  * ws_weak_mask: :63-68 -- mask [n] uint32, bit k set while class k survives: every word starts as the low c bits
  *   (weak = ones) and takes the AND of anchor_bits[a] (the 0/1 label row of anchor a, bit k = column k, packed by the

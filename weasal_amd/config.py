@@ -45,7 +45,8 @@ _OTHER = (('sub_radius', 'f'), ('model_name', 's'), ('loss_type', 's'), ('contra
           ('initial_labels_per_file', 'd'), ('subsample_method', 's'), ('added_labels_per_epoch', 'd'),
           ('weak_label_log', 's'), ('dropout', 'f3'),
           ('batch_norm_mode', 's'),      # 'reference' (the identity of blocks.py:453-463, also when absent) | 'points': no class declares it
-          ('batch_norm_sync', 'b'))      # 'points' under data parallelism: batch statistics over all ranks (dp.sync_batch_norm); absent = off: no class declares it
+          ('batch_norm_sync', 'b'),      # 'points' under data parallelism: batch statistics over all ranks (dp.sync_batch_norm); absent = off: no class declares it
+          ('al_min_spacing', 'f'))       # minimum distance between new active-learning labels and to the used ones (active.spaced_top_k); absent or 0 = off: no class declares it
 _FILE_KEY = {'lr_decays': 'lr_decay_epochs', 'contrast_thd': 'contrast_thd[%]'}        # attribute -> its key in the file
 _DERIVED = ('num_layers',)
 _ONE = {'s': '{:s}', 'd': '{:d}', 'f': '{:.6f}', 'f3': '{:.3f}'}

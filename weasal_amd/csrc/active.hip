@@ -10,6 +10,9 @@
 //                        radix select of the k-th key, a compaction in index order (ws_scan.h) and a stable least-
 //                        significant-digit radix sort of the k survivors.  The reference removes the used ids with one
 //                        np.delete(np.where()) per id, O(used * N); here they are a bitmap and cost nothing per id.
+//   ws_al_spaced_select  no counterpart in the reference (opt-in, `al_min_spacing`): the greedy walk over the candidates in
+//                        ws_topk_select's order that accepts a candidate only when it keeps a minimum distance to every
+//                        point accepted before it and to every used point; float64 distances, exact and run-to-run equal
 // Order contract: descending score, ascending index among equal scores (stable), -0.0 == +0.0, NaN below every number.
 #include "ws_common.h"
 #include "ws_scan.h"
@@ -250,7 +253,161 @@ __global__ __launch_bounds__(64) void topk_sort_scatter_kernel(const u64* __rest
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// spaced greedy selection
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int SP_THREADS = 1024;          // the walk: one workgroup, one candidate per thread and chunk
+constexpr int SP_WAVES = SP_THREADS / 64;
+constexpr int SP_USED_TILE = 256;         // used coordinates staged in LDS per round of the blocking pass
+constexpr int SP_NONE = 1 << 30;          // "no live lane" in a wave's slot
+
+template <typename T>
+__device__ __forceinline__ void sp_load(const void* coords, int64_t i, double& x, double& y, double& z)
+{
+    const T* p = (const T*)coords + 3 * i;
+    x = (double)p[0]; y = (double)p[1]; z = (double)p[2];
+}
+
+// q blocks p: float64, every operation rounded on its own (-ffp-contract=off), strict
+__device__ __forceinline__ bool sp_blocks(double px, double py, double pz, double qx, double qy, double qz, double s2)
+{
+    const double dx = px - qx, dy = py - qy, dz = pz - qz;
+    const double d2 = (dx * dx + dy * dy) + dz * dz;
+    return d2 < s2;
+}
+
+// dead[i] = candidate i lies within the spacing of a used point (or its id is outside [0, n) and is never dereferenced).
+// One candidate per thread; the used coordinates stream through LDS in tiles and are read as broadcasts.
+template <typename T>
+__global__ __launch_bounds__(SP_USED_TILE) void spaced_used_kernel(const void* __restrict__ coords, int64_t n,
+                                                                   const int64_t* __restrict__ cand, int64_t m,
+                                                                   const int64_t* __restrict__ used, int64_t n_used, double s2,
+                                                                   uint8_t* __restrict__ dead)
+{
+    __shared__ double ux[SP_USED_TILE], uy[SP_USED_TILE], uz[SP_USED_TILE];
+    const int64_t chunks = (m + SP_USED_TILE - 1) / SP_USED_TILE;
+    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const int64_t i = c * SP_USED_TILE + threadIdx.x;
+        const int64_t id = i < m ? cand[i] : -1;
+        const bool ok = id >= 0 && id < n;
+        double px = 0.0, py = 0.0, pz = 0.0;
+        if (ok) sp_load<T>(coords, id, px, py, pz);
+        bool hit = false;
+        for (int64_t t0 = 0; t0 < n_used; t0 += SP_USED_TILE) {
+            const int64_t j = t0 + threadIdx.x;
+            double x = 0.0, y = 0.0, z = 0.0;
+            if (j < n_used) sp_load<T>(coords, used[j], x, y, z);          // the ids were range-checked on the host
+            ux[threadIdx.x] = x; uy[threadIdx.x] = y; uz[threadIdx.x] = z;
+            __syncthreads();
+            const int cnt = (int)(n_used - t0 < SP_USED_TILE ? n_used - t0 : SP_USED_TILE);
+            for (int e = 0; e < cnt; ++e) hit |= sp_blocks(px, py, pz, ux[e], uy[e], uz[e], s2);
+            __syncthreads();
+        }
+        if (i < m) dead[i] = (uint8_t)(!ok || hit);
+    }
+}
+
+// The walk.  state = { acceptances so far, candidates consumed }.  The accepted coordinates live in LDS (reloaded from
+// ids when a walk is resumed).  Per chunk of SP_THREADS candidates: every thread tests its candidate against what was
+// accepted before the chunk; then the chunk is resolved in order -- each wave posts its lowest live lane with its
+// coordinates, one barrier, every thread reads the SP_WAVES slots (the first occupied one is the lowest live candidate
+// of the workgroup), the winner is accepted and the other live lanes test against it.  The slots are double-buffered,
+// so a round is one barrier; the round that finds no live lane ends the chunk.
+template <typename T>
+__global__ __launch_bounds__(SP_THREADS) void spaced_walk_kernel(const void* __restrict__ coords, int64_t n,
+                                                                 const int64_t* __restrict__ cand, int64_t m,
+                                                                 const uint8_t* __restrict__ dead, double s2, int64_t k,
+                                                                 int64_t* __restrict__ ids, int64_t* __restrict__ state, int resume)
+{
+    __shared__ double ax[WS_AL_SPACED_MAX_K], ay[WS_AL_SPACED_MAX_K], az[WS_AL_SPACED_MAX_K];
+    __shared__ double wx[2][SP_WAVES], wy[2][SP_WAVES], wz[2][SP_WAVES];
+    __shared__ int wl[2][SP_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t acc = resume ? state[0] : 0, before = resume ? state[1] : 0;
+    if (acc < 0) acc = 0;
+    if (acc > k) acc = k;
+    for (int64_t j = tid; j < acc; j += SP_THREADS) {
+        const int64_t id = ids[j];
+        double x = 0.0, y = 0.0, z = 0.0;
+        if (id >= 0 && id < n) sp_load<T>(coords, id, x, y, z);
+        ax[j] = x; ay[j] = y; az[j] = z;
+    }
+    __syncthreads();
+    int64_t consumed = 0;
+    int round = 0;
+    for (int64_t base = 0; base < m && acc < k; base += SP_THREADS) {
+        const int64_t i = base + tid;
+        const int64_t id = i < m ? cand[i] : -1;
+        bool live = id >= 0 && id < n;
+        if (live && dead) live = dead[i] == 0;
+        double px = 0.0, py = 0.0, pz = 0.0;
+        if (live) sp_load<T>(coords, id, px, py, pz);
+        if (__any(live)) {
+            bool hit = false;
+            for (int64_t j = 0; j < acc; ++j) hit |= sp_blocks(px, py, pz, ax[j], ay[j], az[j], s2);
+            live = live && !hit;
+        }
+        int last = -1;
+        for (;;) {
+            const u64 b = __ballot(live);
+            const int buf = round & 1;
+            ++round;
+            const int first = b ? __ffsll((long long)b) - 1 : 0;
+            if (lane == first) {
+                wl[buf][wave] = b ? tid : SP_NONE;
+                wx[buf][wave] = px; wy[buf][wave] = py; wz[buf][wave] = pz;
+            }
+            __syncthreads();
+            int win = SP_NONE, ww = 0;
+#pragma unroll
+            for (int w = SP_WAVES - 1; w >= 0; --w) {
+                const int v = wl[buf][w];
+                if (v != SP_NONE) { win = v; ww = w; }
+            }
+            if (win == SP_NONE) break;
+            if (tid == win) {
+                ax[acc] = px; ay[acc] = py; az[acc] = pz;
+                ids[acc] = id;
+                live = false;
+            } else if (live && sp_blocks(px, py, pz, wx[buf][ww], wy[buf][ww], wz[buf][ww], s2)) {
+                live = false;
+            }
+            ++acc;
+            if (acc == k) { last = win; break; }
+        }
+        consumed = last >= 0 ? base + last + 1 : (base + SP_THREADS < m ? base + SP_THREADS : m);
+    }
+    if (tid == 0) {
+        state[0] = acc;
+        state[1] = before + consumed;
+    }
+}
+
 inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+
+// the launches of a spaced selection, from its sizes alone: shared by the launcher and its reporter
+struct SpacedPlan {
+    int f64, used_pass, used_blocks, used_tiles, tail, resume;
+    int64_t chunks, off_used, off_dead, total;
+};
+
+SpacedPlan spaced_plan(int32_t coords_f64, int64_t m, int64_t n_used, int32_t resume)
+{
+    SpacedPlan p;
+    if (m < 0) m = 0;
+    if (n_used < 0) n_used = 0;
+    p.f64 = coords_f64 != 0;
+    p.used_pass = n_used > 0 && m > 0;
+    p.used_blocks = p.used_pass ? ws_grid(m, SP_USED_TILE) : 0;
+    p.used_tiles = (int)ws_ceil_div(n_used, SP_USED_TILE);
+    p.chunks = ws_ceil_div(m, SP_THREADS);
+    p.tail = (int)(m % SP_THREADS);
+    p.resume = resume != 0;
+    p.off_used = 0;
+    p.off_dead = align256(n_used * 8);
+    p.total = p.off_dead + align256(m) + 256;
+    return p;
+}
 
 struct TopkLayout {
     int64_t excluded, keys, above, ties, scan, state, keys_a, keys_b, idx_a, idx_b, counts, total;
@@ -382,6 +539,74 @@ int ws_topk_select(const double* score, int64_t n, const int64_t* h_exclude, int
                                                     pass == 7 ? ids : nullptr);
         WS_LAUNCH_CHECK();
     }
+    return WS_OK;
+}
+
+int64_t ws_al_spaced_scratch_bytes(int64_t m, int64_t n_used, int64_t k)
+{
+    (void)k;                                   // the accepted coordinates live in LDS
+    return spaced_plan(0, m, n_used, 0).total;
+}
+
+// sizes and the spacing: what both the launcher and its reporter refuse, nothing of it on the device
+static int spaced_check(int64_t n, int64_t m, int64_t n_used, double spacing, int64_t k)
+{
+    WS_REQUIRE(spacing > 0.0 && spacing < __builtin_inf(), "spacing=%g: a finite spacing above 0 is required", spacing);
+    WS_REQUIRE(n >= 0 && m >= 0 && n_used >= 0 && k >= 0, "bad sizes n=%lld m=%lld n_used=%lld k=%lld", (long long)n, (long long)m,
+               (long long)n_used, (long long)k);
+    if (k > WS_AL_SPACED_MAX_K)
+        return ws_fail(WS_ERR_UNSUPPORTED, "ws_al_spaced_select: k=%lld (at most WS_AL_SPACED_MAX_K = %d: the accepted coordinates "
+                       "are resident in LDS)", (long long)k, WS_AL_SPACED_MAX_K);
+    return WS_OK;
+}
+
+int ws_al_spaced_select(const void* coords, int32_t coords_f64, int64_t n, const int64_t* cand, int64_t m, const int64_t* h_used,
+                        int64_t n_used, double spacing, int64_t k, int64_t* ids, int64_t* state, int32_t resume, void* scratch,
+                        void* stream)
+{
+    if (int rc = spaced_check(n, m, n_used, spacing, k)) return rc;
+    WS_REQUIRE(n_used == 0 || h_used, "NULL argument");
+    for (int64_t e = 0; e < n_used; ++e)
+        WS_REQUIRE(h_used[e] >= 0 && h_used[e] < n, "used[%lld] = %lld outside [0, %lld)", (long long)e, (long long)h_used[e],
+                   (long long)n);
+    hipStream_t st = (hipStream_t)stream;
+    if (k == 0 || m == 0) {
+        if (!resume && state) WS_HIP(hipMemsetAsync(state, 0, 2 * sizeof(int64_t), st));
+        return WS_OK;
+    }
+    WS_REQUIRE(coords && cand && ids && state && scratch, "NULL argument");
+    const SpacedPlan p = spaced_plan(coords_f64, m, n_used, resume);
+    const double s2 = spacing * spacing;
+    int64_t* used = (int64_t*)((char*)scratch + p.off_used);
+    uint8_t* dead = p.used_pass ? (uint8_t*)scratch + p.off_dead : nullptr;
+    if (p.used_pass) {
+        // pageable source, as in ws_topk_select: the copy has left h_used when the call returns
+        WS_HIP(hipMemcpyAsync(used, h_used, (size_t)n_used * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        if (p.f64) spaced_used_kernel<double><<<p.used_blocks, SP_USED_TILE, 0, st>>>(coords, n, cand, m, used, n_used, s2, dead);
+        else spaced_used_kernel<float><<<p.used_blocks, SP_USED_TILE, 0, st>>>(coords, n, cand, m, used, n_used, s2, dead);
+        WS_LAUNCH_CHECK();
+    }
+    if (p.f64) spaced_walk_kernel<double><<<1, SP_THREADS, 0, st>>>(coords, n, cand, m, dead, s2, k, ids, state, resume != 0);
+    else spaced_walk_kernel<float><<<1, SP_THREADS, 0, st>>>(coords, n, cand, m, dead, s2, k, ids, state, resume != 0);
+    WS_LAUNCH_CHECK();
+    return WS_OK;
+}
+
+int ws_al_spaced_variant(int32_t coords_f64, int64_t n, int64_t m, int64_t n_used, double spacing, int64_t k, int32_t resume,
+                         char* text, int32_t cap)
+{
+    WS_REQUIRE(text && cap > 0, "bad argument");
+    if (int rc = spaced_check(n, m, n_used, spacing, k)) return rc;
+    if (k == 0 || m == 0) {
+        snprintf(text, (size_t)cap, "none (%s)%s", k == 0 ? "k == 0" : "m == 0", resume ? "" : " state zeroed");
+        return WS_OK;
+    }
+    const SpacedPlan p = spaced_plan(coords_f64, m, n_used, resume);
+    char used[96] = "no used pass";
+    if (p.used_pass)
+        snprintf(used, sizeof used, "spaced_used_kernel<%s> blocks=%d tiles=%d", p.f64 ? "double" : "float", p.used_blocks, p.used_tiles);
+    snprintf(text, (size_t)cap, "%s + spaced_walk_kernel<%s> chunks=%lld tail=%d resume=%d", used, p.f64 ? "double" : "float",
+             (long long)p.chunks, p.tail, p.resume);
     return WS_OK;
 }
 

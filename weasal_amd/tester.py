@@ -333,14 +333,22 @@ def cloud_segmentation_test(net, batches, config, votes, test_radius_ratio=0.7, 
 # ---------------------------------------------------------------------------------------------------------------
 # active-learning selection after a pass over the training clouds (tester_PseudoLabel.py:393-438)
 # ---------------------------------------------------------------------------------------------------------------
-def active_learning_selection(votes, class_w, used_ids_per_cloud, k):
+def active_learning_selection(votes, class_w, used_ids_per_cloud, k, points=None, min_spacing=0.0):
     """The reference's `active_learning=True` branch on votes resident on the device: for every cloud the k points with
     the highest entropy score that carry no ground-truth label yet (weasal_amd.active.select_points).  used_ids_per_cloud:
     one id array per cloud (the `*_al_groundTruth_IDs` lists).  Returns the appended lists, host int64 arrays: the old ids
     followed by the new ones in selection order (:434).  Raises the reference's ValueError when a cloud has fewer than k
-    unlabelled points left."""
+    unlabelled points left.
+    min_spacing above 0 (opt-in, `al_min_spacing`): the spaced selection of active.select_points; points: one [N, 3]
+    coordinate array per cloud (sampler.sub_points), needed only then."""
     from . import active
     if len(used_ids_per_cloud) != len(votes.probs):
         raise ValueError("one list of used ids per cloud: got %d for %d clouds" % (len(used_ids_per_cloud), len(votes.probs)))
-    new = [active.select_points(votes, i, class_w, used, k) for i, used in enumerate(used_ids_per_cloud)]
+    if active._spacing(min_spacing) == 0.0:
+        new = [active.select_points(votes, i, class_w, used, k) for i, used in enumerate(used_ids_per_cloud)]
+    else:
+        if points is None or len(points) != len(votes.probs):
+            raise ValueError("a minimum spacing needs one coordinate array per cloud")
+        new = [active.select_points(votes, i, class_w, used, k, points=points[i], min_spacing=min_spacing)
+               for i, used in enumerate(used_ids_per_cloud)]
     return [np.append(active._host_ids(used), ids.cpu().numpy()).astype(np.int64) for used, ids in zip(used_ids_per_cloud, new)]

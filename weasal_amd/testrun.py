@@ -275,10 +275,19 @@ class ModelTester:
     def _save_extra(self, test_path, ts):
         pass
 
-    def _select(self, ts, **al):
-        """(:393-438) -> the appended id lists, one per cloud"""
+    def _min_spacing(self):
+        """`al_min_spacing` of the configuration (optional key of parameters.txt; absent, None or 0: off)"""
+        return float(getattr(self.config, "al_min_spacing", 0.0) or 0.0)
+
+    def _select(self, ts, sub_points=None, **al):
+        """(:393-438) -> the appended id lists, one per cloud.  sub_points: the sampler's tiles, read only when the
+        configuration sets `al_min_spacing`"""
         k = al.get("added_labels")
         k = self.config.added_labels_per_epoch if k is None else k
+        spacing = self._min_spacing()
+        if spacing:
+            return tester.active_learning_selection(self.votes, self.config.class_w, al["used_ids"], k, points=sub_points,
+                                                    min_spacing=spacing)
         return tester.active_learning_selection(self.votes, self.config.class_w, al["used_ids"], k)
 
     # ---------------------------------------------------------------------------------------------------------------
@@ -353,7 +362,7 @@ class ModelTester:
 
         print('\nReproject Vote #{:d}'.format(int(np.floor(new_min))))
         if active_learning:
-            return self._select(ts, **al)
+            return self._select(ts, sub_points=sampler.sub_points, **al)
         return self._finish(ts, tables, confusion, status, scored, test_path, sampler, test_on_train)
 
     def _finish(self, ts, tables, confusion, status, scored, test_path, sampler, test_on_train):
@@ -425,17 +434,20 @@ class ModelTesterWL(ModelTester):
         np.savez(os.path.join(test_path, 'pseudo.npz'), **{n: np.argmax(v, axis=1) for n, v in zip(names, votes)})
         np.savez(os.path.join(test_path, 'probs.npz'), **dict(zip(names, votes)))
 
-    def _select(self, ts, **al):
-        """(:403-474) -> the appended anchor index lists, one per cloud"""
+    def _select(self, ts, sub_points=None, **al):
+        """(:403-474) -> the appended anchor index lists, one per cloud.  With `al_min_spacing` the spacing holds between
+        the anchors' centres (AnchorSet.centres); the sampler's tiles are not needed"""
         from . import active
         k = al.get("added_labels")
         k = self.config.added_labels_per_epoch if k is None else k
         sets, used = al["anchor_sets"], al["used_anchors"]
         if len(sets) != len(self.votes.probs) or len(used) != len(sets):
             raise ValueError("one AnchorSet and one list of used anchors per cloud")
+        spacing = self._min_spacing()
         out = []
         for i, (a, u) in enumerate(zip(sets, used)):
             lb = a.lb.cpu().numpy() if isinstance(a.lb, torch.Tensor) else np.asarray(a.lb)
-            new = active.select_anchors(self.votes, i, a.ptr, a.idx, lb, u, k)
+            extra = dict(centres=a.centres, min_spacing=spacing) if spacing else {}
+            new = active.select_anchors(self.votes, i, a.ptr, a.idx, lb, u, k, **extra)
             out.append(np.append(active._host_ids(u), new.cpu().numpy()))
         return out
